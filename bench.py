@@ -15,7 +15,12 @@ chunk's pyramids on their GPU, search it as one batch, and finally gather
 the accepted constraints to rank 0 in submission order (RCCL). Node clouds
 are resident in HBM before timing; submap pyramids are built inside it.
 
-Secondary lines (rank 0, one GPU): C2 (500 x 50), the same C2 queue at
+A plain run does only that: it sets up, warms up, times the steps, writes
+the last step's outputs if --dump-outputs names a directory, and prints the
+line. Everything else is behind --full: the CPU baselines, the parity
+samples against the oracle, work_ratio, and the secondary lines.
+
+Secondary lines (--full; rank 0, one GPU): C2 (500 x 50), the same C2 queue at
 min_score 0.65 (a low-acceptance sweep), C1 RTCSM2D ms/scan-match,
 the drop-in's call patterns, voxel filter, Ceres refinement, C4 RTCSM3D and
 C5 FastCSM3D (500 nodes x 200 submaps, split over the ranks).
@@ -57,6 +62,18 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline's timed steps also run everything else: the CPU "
+                        "baselines, the parity samples against the oracle, work_ratio, the "
+                        "secondary legs (C2, C2 strict, C1, the drop-in's call patterns, voxel "
+                        "filter, Ceres, C4) and C5. Without it the run sets up, warms up, times "
+                        "the steps and prints the line; --no-cpu, --no-rt, --no-3d, "
+                        "--parity-pairs and --cpu-pairs select among what --full adds")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes what the headline's last timed step computed to DIR as "
+                        "float64 .npy files (dump_outputs): <workload>_results.npy, a row per "
+                        "pair of the step in queue order, and <workload>_records.npy, the "
+                        "accepted constraints gathered from it in submission order")
     p.add_argument("--workload", default="c3", choices=["c2", "c3"],
                    help="c3 (default): the fixed 2000-node x 1000-submap queue, a step = one "
                         "--c3-slice of it, claimed dynamically over the ranks; c2: 500 x 50 "
@@ -67,12 +84,14 @@ def parse():
     p.add_argument("--search-depth", type=int, default=0, help="0 = automatic (exact)")
     p.add_argument("--cpu-seconds", type=float, default=20.0)
     p.add_argument("--cpu-threads", type=int, default=0)
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true",
+                   help="with --full: skip the CPU baselines (and, at N = 1, the C3 parity sample)")
     p.add_argument("--no-rt", action="store_true",
-                   help="skip the secondary legs (C2, C2 strict, C1, C4); C5 runs unless --no-3d")
+                   help="with --full: skip the secondary legs (C2, C2 strict, C1, C4); C5 runs "
+                        "unless --no-3d")
     p.add_argument("--seed", type=int, default=20250127)
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
-    p.add_argument("--no-3d", action="store_true")
+    p.add_argument("--no-3d", action="store_true", help="with --full: skip C4 and C5")
     p.add_argument("--nodes3d", type=int, default=500)
     p.add_argument("--submaps3d", type=int, default=200,
                    help="C5 submaps in total, split over the ranks")
@@ -111,14 +130,19 @@ def parse():
                         "with gloo); rccl with gloo rehearses the RCCL branch on one GPU against "
                         "a library named by CSM_RCCL_LIB (tests/test_bench_multirank_gpu.py)")
     p.add_argument("--dump-records", default="",
-                   help="rank 0 writes the gathered C3 and C5 constraint records to this .npz")
+                   help="rank 0 writes the gathered C3 and (with --full) C5 constraint records to "
+                        "this .npz")
     p.add_argument("--cpu-pairs", type=int, default=0,
-                   help="CPU baseline sample size (0: 2000 for C3, sized to --cpu-seconds for C2)")
+                   help="with --full: CPU baseline sample size (0: 2000 for C3, sized to "
+                        "--cpu-seconds for C2)")
     p.add_argument("--parity-pairs", type=int, default=-1,
-                   help="C3 pairs of the timed run compared with the oracle afterwards (-1: the "
+                   help="with --full: C3 pairs of the timed run compared with the oracle afterwards (-1: the "
                         "CPU baseline's 2000 at N = 1, 500 at N > 1; 0: none). At N > 1 the rank "
                         "that claims a sampled pair keeps its result; rank 0 gathers and checks them")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -194,7 +218,8 @@ def main():
     else:
         out, errors = c2_run(csm, ctx, args, rank, world_size, dist, coll_dev, gather, transport,
                              barrier_sync, headline=True)
-    if rank == 0 and world_size == 1 and not args.no_rt:
+    # Everything below the headline is --full's (secondary legs, C5).
+    if args.full and rank == 0 and world_size == 1 and not args.no_rt:
         if args.workload == "c3":
             c2, c2_errors = c2_run(csm, ctx, args, rank, world_size, dist, coll_dev, gather,
                                    transport, barrier_sync, headline=False)
@@ -211,9 +236,9 @@ def main():
                                                     "errors_per_step")}
             out["c2_strict"]["kernel_ms"] = c2s["roofline"]["kernel_ms_avg"]
         out["rt2d"] = rt2d_bench(csm, ctx, args)
-    if rank == 0 and world_size == 1 and not args.no_3d and not args.no_rt:
+    if args.full and rank == 0 and world_size == 1 and not args.no_3d and not args.no_rt:
         out["rt3d"] = rt3d_bench(csm, ctx, args)
-    if not args.no_3d:  # collective over ranks: the C5 sweep, submap-sharded
+    if args.full and not args.no_3d:  # collective over ranks: the C5 sweep, submap-sharded
         f3 = fast3d_bench(csm, ctx, args, rank, world_size, dist, coll_dev, barrier_sync, cdist,
                           gather)
         if rank == 0:
@@ -336,9 +361,13 @@ def c2_run(csm, ctx, args, rank, world_size, dist, coll_dev, gather, transport, 
     if not headline:
         for k in ("metric", "higher_is_better", "vs_baseline", "dtype", "data"):
             out.pop(k)
-    if rank == 0 and world_size == 1 and headline and not args.no_cpu:
+    if headline and args.dump_outputs and rank == 0:
+        # Rank 0's share of the last timed step (a rank's results stay with it
+        # under weak scaling) and the constraints gathered from every rank.
+        dump_outputs(args.dump_outputs, "c2", results_table(res), rec, args.seed)
+    if args.full and rank == 0 and world_size == 1 and headline and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(world, my_submaps, args)
-    if rank == 0 and world_size == 1 and not args.no_rt and extras:
+    if args.full and rank == 0 and world_size == 1 and not args.no_rt and extras:
         out["dropin"] = dropin_bench(csm, ctx, matchers, scans, world, args)
         out["voxel_filter"] = voxel_filter_bench(csm, ctx, world, args)
         out["ceres2d"] = ceres_bench(csm, ctx, world, matchers, scans, pairs, res, my_submaps,
@@ -361,6 +390,35 @@ def roofline_fields(tm, achieved, peak, traffic, kernel_ms_avg, bytes_per_launch
                                 "16 grandchildren each)",
             # SURVEY §8(d)'s figure: candidates scored x N points x 1 B
             "candidate_equivalent_bytes_per_launch": candidate_bytes}
+
+
+RESULT_COLUMNS = ("status", "score", "x", "y", "theta", "tie")
+# --dump-outputs writes at most this much in all.
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def results_table(res):
+    """A csm_result2d batch (RESULT_DTYPE) as float64 rows of RESULT_COLUMNS;
+    every field converts exactly (int32, float32, float64)."""
+    return np.stack([res[name].astype(np.float64) for name in RESULT_COLUMNS], 1)
+
+
+def dump_outputs(directory, workload, results, records, seed):
+    """--dump-outputs: what the headline's last timed step handed its caller.
+    <workload>_results.npy holds the step's csm_fast2d_match_batch results, a
+    row of RESULT_COLUMNS per pair in queue order (submap-major); and
+    <workload>_records.npy the accepted constraints gathered from them, rows
+    of distributed.RECORD_FIELDS in submission order. Both float64. An array
+    over its half of DUMP_BUDGET_BYTES is cut to a sample of its rows, drawn
+    with the run's --seed and kept in order, so equal arguments write equal
+    rows."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in (("results", results), ("records", records)):
+        a = np.ascontiguousarray(a, np.float64)
+        cap = (DUMP_BUDGET_BYTES // 2) // max(a[:1].nbytes, 1)
+        if len(a) > cap:
+            a = a[np.sort(np.random.RandomState(seed % 2**32).choice(len(a), cap, replace=False))]
+        np.save(os.path.join(directory, f"{workload}_{name}.npy"), a)
 
 
 TRAFFIC_FILES = {"c2": os.path.join("profiles", "r6f", "traffic_c2.json"),
@@ -1288,6 +1346,26 @@ def gather_sample(sample, comm, csm):
         sample["have"][rows["i"]] = True
 
 
+def last_step_results(parts, comm, csm):
+    """The last timed step's results in queue order, from the (queue position,
+    csm_result2d rows) runs this rank kept of the chunks it claimed; at N > 1
+    every rank's runs go to rank 0 over the C-ABI communicator
+    (csm_comm_gather), as gather_sample's. None on the other ranks."""
+    row = np.dtype([("i", "<i8"), ("r", csm.RESULT_DTYPE)])
+    mine = np.zeros(sum(len(r) for _, r in parts), row)
+    at = 0
+    for pos, r in parts:
+        mine["i"][at:at + len(r)] = pos + np.arange(len(r))
+        mine["r"][at:at + len(r)] = r
+        at += len(r)
+    if comm is not None:
+        blobs = comm.gather(mine.tobytes())
+        if blobs is None:  # not rank 0
+            return None
+        mine = np.concatenate([np.frombuffer(b, row) for b in blobs])
+    return mine["r"][np.argsort(mine["i"], kind="stable")]
+
+
 def work_ratio(csm, ctx, world, opts, sample, ores, args, queue_levels):
     """SURVEY §8(d)'s reference lookup count next to the GPU's work, on the
     same sampled pairs. Reference side: the oracle's counters from the parity
@@ -1520,7 +1598,8 @@ def c3_run(csm, ctx, args, rank, world_size, dist, coll_dev, comm, gather, trans
     thread_pool.cc:80-106), builds the chunk's pyramids on its GPU, searches it
     as one batch and keeps the accepted constraints; at the end the records
     go to rank 0 in submission order (constraint_builder_2d.cc:279-300) over
-    RCCL. Warmup steps run one chunk each, untimed."""
+    RCCL. A warmup step runs one slice of the queue, untimed, so it takes as
+    long as a timed step."""
     cdist = importlib.import_module("cartographer_amd.distributed")
     N, S = args.c3_nodes, args.c3_submaps
     K = args.c3_chunk = args.c3_chunk or (4 if world_size == 1 else 2)
@@ -1581,7 +1660,7 @@ def c3_run(csm, ctx, args, rank, world_size, dist, coll_dev, comm, gather, trans
     # the same pair (parity_sample). At N = 1 the oracle's run on the sample is
     # also the CPU baseline.
     sample = None
-    k_s = args.parity_pairs
+    k_s = args.parity_pairs if args.full else 0  # the oracle's run is --full's
     if k_s < 0:
         k_s = 0 if (world_size == 1 and args.no_cpu) else \
             (args.cpu_pairs or 2000) if world_size == 1 else 500
@@ -1595,15 +1674,36 @@ def c3_run(csm, ctx, args, rank, world_size, dist, coll_dev, comm, gather, trans
             want.setdefault(int(a), []).append((i, int(b)))
         sample = {"sub": s_sub, "node": s_node, "want": want,
                   "gpu": np.zeros(k_s, csm.RESULT_DTYPE), "have": np.zeros(k_s, bool)}
-    for w in range(args.warmup):  # one chunk each: module load, staging buffers
-        for i in range(len(ctxs)):
-            run_chunk(chunks[(rank + w) % n_chunks], 0, i)
+    # A warmup step is a step's worth of work, untimed (module load, staging
+    # buffers, clocks): the queue's first slice in chunks, dealt out over the
+    # ranks and their contexts; every context runs at least one chunk, and
+    # several contexts run theirs on a thread each, as in the timed region.
+    wq = (np.arange(slice_) % S).astype(np.int64)
+    wchunks = [wq[i:i + K] for i in range(0, len(wq), K)]
+    mine_w = wchunks[rank::world_size] or [wchunks[rank % len(wchunks)]]
+
+    def warm(i):
+        for ch in mine_w[i::len(ctxs)] or mine_w[:1]:
+            run_chunk(ch, 0, i)
+
+    for w in range(args.warmup):
+        if len(ctxs) == 1:
+            warm(0)
+        else:
+            threads = [threading.Thread(target=warm, args=(i,)) for i in range(len(ctxs))]
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join()
     for c in ctxs:
         c.reset_timing()
         c.enable_timing(True)
     barrier_sync()
     t_start = time.perf_counter()
-    done = {"errors": 0, "mine": 0, "recs": [], "ties": []}
+    done = {"errors": 0, "mine": 0, "recs": [], "ties": [], "last": []}
+    # --dump-outputs: queue position of the last step's first pair (a chunk
+    # may straddle two steps).
+    last_from = (args.steps - 1) * slice_ * N if args.dump_outputs else None
 
     def worker(w):
         while True:
@@ -1612,6 +1712,10 @@ def c3_run(csm, ctx, args, rank, world_size, dist, coll_dev, comm, gather, trans
                 return
             res, rec = run_chunk(chunks[c], np.int64(c) * K * N, w)
             tied = np.nonzero((res["status"] == 0) & (res["tie"] != 0))[0]
+            if last_from is not None and c * K * N + len(res) > last_from:
+                lo = max(last_from - c * K * N, 0)
+                with claim_lock:
+                    done["last"].append((c * K * N + lo, res[lo:]))
             if sample is not None:
                 for j, sm in enumerate(chunks[c]):
                     for i, n in sample["want"].get(int(sm), ()):
@@ -1647,6 +1751,11 @@ def c3_run(csm, ctx, args, rank, world_size, dist, coll_dev, comm, gather, trans
     if sample is not None and comm is not None:
         # After the timed region: every rank's results of sampled pairs to rank 0.
         gather_sample(sample, comm, csm)
+    if last_from is not None:
+        last = last_step_results(done["last"], comm, csm)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, "c3", results_table(last),
+                         allrec[allrec[:, 0] >= last_from], args.seed)
     for c in ctxs:
         c.enable_timing(False)
     tm = sum_timing(csm, [c.timing() for c in ctxs])

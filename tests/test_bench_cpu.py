@@ -65,6 +65,64 @@ def test_oracle_work_counters_and_work_ratio_fields():
     assert wr["gpu_queue_candidates_per_pair"] == 3.0
 
 
+def test_dump_outputs_writes_float64_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: both arrays as float64 .npy, every result field exact;
+    an array over its half of the budget is cut to a seeded sample of its rows,
+    kept in order and the same from run to run."""
+    ensure_built()
+    csm = load_package()
+    res = np.zeros(1000, csm.RESULT_DTYPE)
+    res["status"] = np.arange(1000) % 2
+    res["score"] = np.float32(0.1) * np.arange(1000, dtype=np.float32)
+    res["x"] = np.arange(1000) + 1.0 / 3.0
+    res["tie"] = np.arange(1000) % 3
+    table = bench.results_table(res)
+    assert table.dtype == np.float64 and table.shape == (1000, len(bench.RESULT_COLUMNS))
+    assert np.array_equal(table[:, 1].astype(np.float32), res["score"])
+    assert np.array_equal(table[:, 2], res["x"]) and np.array_equal(table[:, 5], res["tie"])
+    rec = np.arange(27, dtype=np.float64).reshape(3, 9)
+    bench.dump_outputs(str(tmp_path / "a"), "c3", table, rec, 20250127)
+    assert sorted(os.listdir(tmp_path / "a")) == ["c3_records.npy", "c3_results.npy"]
+    assert np.array_equal(np.load(tmp_path / "a" / "c3_results.npy"), table)
+    assert np.array_equal(np.load(tmp_path / "a" / "c3_records.npy"), rec)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 100 * table[:1].nbytes)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "c3", table, rec, 20250127)
+    cut = np.load(tmp_path / "b" / "c3_results.npy")
+    assert cut.dtype == np.float64 and cut.shape == (100, table.shape[1])
+    assert np.all(np.diff(cut[:, 2]) > 0)  # rows of the table, in order
+    assert np.array_equal(cut, table[(cut[:, 2] - 1.0 / 3.0).round().astype(int)])
+    assert np.array_equal(cut, np.load(tmp_path / "c" / "c3_results.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "c3_records.npy"), rec)
+
+
+def test_last_step_results_merge_ranks_in_queue_order():
+    """--dump-outputs at N > 1: each rank keeps (queue position, rows) runs of
+    the chunks it claimed; rank 0 receives every rank's through csm_comm_gather
+    and orders them by queue position (bench.last_step_results). A fake
+    communicator stands in for the 2-rank gather."""
+    ensure_built()
+    csm = load_package()
+    full = np.zeros(10, csm.RESULT_DTYPE)
+    full["score"] = np.arange(10, dtype=np.float32)
+    alone = bench.last_step_results([(104, full[4:7]), (100, full[0:4]), (107, full[7:])], None, csm)
+    assert np.array_equal(alone, full)
+
+    class FakeComm:
+        def __init__(self, blobs):
+            self.blobs = blobs
+
+        def gather(self, blob):
+            return None if self.blobs is None else [blob] + self.blobs
+
+    row = np.dtype([("i", "<i8"), ("r", csm.RESULT_DTYPE)])
+    other = np.zeros(6, row)
+    other["i"], other["r"] = 100 + np.array([7, 8, 9, 0, 1, 2]), full[[7, 8, 9, 0, 1, 2]]
+    merged = bench.last_step_results([(103, full[3:7])], FakeComm([other.tobytes()]), csm)
+    assert np.array_equal(merged, full)
+    assert bench.last_step_results([(103, full[3:7])], FakeComm(None), csm) is None
+
+
 @pytest.mark.parametrize("bad", [{"gpus": 3}])
 def test_launch_ranks_rejects_mismatch(monkeypatch, bad):
     monkeypatch.setenv("WORLD_SIZE", "2")

@@ -33,7 +33,7 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 STANDIN = os.path.join(ROOT, "tests", "comm_standin", "librccl_standin.so")
-SMALL = ["--workload", "c3", "--c3-nodes", "48", "--c3-submaps", "12", "--c3-slice", "4",
+SMALL = ["--full", "--workload", "c3", "--c3-nodes", "48", "--c3-submaps", "12", "--c3-slice", "4",
          "--steps", "3", "--warmup", "1", "--no-rt", "--no-cpu", "--nodes3d", "40",
          "--submaps3d", "6", "--steps3d", "1", "--parity-pairs", "24"]
 
@@ -46,7 +46,8 @@ def test_two_ranks_rccl_branch_equal_single_rank(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONUNBUFFERED="1")
     one = tmp_path / "one.npz"
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL,
-                         "--dump-records", str(one)], capture_output=True, text=True, timeout=240,
+                         "--dump-records", str(one), "--dump-outputs", str(tmp_path / "one")],
+                        capture_output=True, text=True, timeout=240,
                         cwd=ROOT, env=env)
     assert r1.returncode == 0, r1.stderr[-3000:]
     j1 = _json_line(r1.stdout)
@@ -56,8 +57,8 @@ def test_two_ranks_rccl_branch_equal_single_rank(tmp_path):
         env2.pop(var, None)
     r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL,
                          "--dist-backend", "gloo", "--comm-backend", "rccl",
-                         "--dump-records", str(two)], capture_output=True, text=True,
-                        timeout=300, cwd=ROOT, env=env2)
+                         "--dump-records", str(two), "--dump-outputs", str(tmp_path / "two")],
+                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env2)
     assert r2.returncode == 0, r2.stderr[-3000:]
     assert "starting 2 ranks" in r2.stderr
     j2 = _json_line(r2.stdout)
@@ -78,6 +79,12 @@ def test_two_ranks_rccl_branch_equal_single_rank(tmp_path):
         assert a[key].shape == b[key].shape and len(a[key]) > 0, key
         assert np.array_equal(a[key], b[key]), key          # same records, submission order
         assert np.all(np.diff(b[key][:, 0]) > 0), key
+    # The last timed step's per-pair results (--dump-outputs), gathered from
+    # whichever rank claimed each chunk, equal the single rank's.
+    for name in ("c3_results.npy", "c3_records.npy"):
+        x, y = np.load(tmp_path / "one" / name), np.load(tmp_path / "two" / name)
+        assert x.shape == y.shape and np.array_equal(x, y), name
+    assert len(np.load(tmp_path / "one" / "c3_results.npy")) == 4 * 48
     # Strong-scaling accounting: the same fixed queue, every chunk claimed
     # once over the ranks, value = all pairs / the slowest rank's time.
     for j in (j1, j2):

@@ -1,12 +1,12 @@
 #!/bin/bash
 # Round-2 measurement set on one MI355X box. Usage: tools/gpu_measure.sh OUT STAGE...
 #   tests   pytest -m gpu (all GPU tests)
-#   bench   bench.py defaults (C2 + C1 + voxel + Ceres + C4 + C5, CPU baselines)
+#   bench   bench.py --full (C3 + C2 + C1 + voxel + Ceres + C4 + C5, CPU baselines)
 #   trace   rocprofv3 --kernel-trace --stats of the C2 leg alone
 #   pmc     rocprofv3 --pmc passes on the C2 leg (one counter group per pass)
 #   gloo2   2-rank rehearsal (torch.distributed.run, gloo, both ranks on the GPU)
-#   c3      bench.py --workload c3 (2000 x 1000 queue, 1 GPU) + CPU baseline
-#   c3trace rocprofv3 --kernel-trace --stats of two 16-submap slices of the C3 queue (8 chunk launches)
+#   c3      bench.py --full --workload c3 (2000 x 1000 queue, 1 GPU) + CPU baseline
+#   c3trace rocprofv3 --kernel-trace --stats of two 16-submap slices of the C3 queue (8 chunk launches, after the warmup slice's 4)
 #   c3pmc   FETCH_SIZE pass on one 16-submap slice of the C3 queue (4 chunk launches)
 #   c5      C5 probe (builds inside the step), its kernel trace and PMC passes of fast3d_search
 set -u
@@ -22,7 +22,7 @@ for st in "$@"; do
         > $OUT/gpu_tests.log 2>&1 || { tail -30 $OUT/gpu_tests.log; exit 1; } ;;
     bench)
       t0=$(date +%s)
-      timeout -k 10 700 python -u bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err \
+      timeout -k 10 700 python -u bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err \
         || { tail -30 $OUT/bench_full.err; exit 1; }
       echo "bench.py wall seconds: $(( $(date +%s) - t0 ))" | tee $OUT/bench_full.wall ;;
     trace)
@@ -43,11 +43,11 @@ for st in "$@"; do
       python3 tools/traffic_json.py $OUT/pmc/p3 $OUT/traffic_c2.json $(python3 -c "import sys; sys.path.insert(0,'.'); import bench; print(bench.KERNEL_TAG)") 0 ;;
     gloo2)
       timeout -k 10 400 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --dist-backend gloo --no-cpu --no-rt \
+        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --dist-backend gloo --no-cpu --no-rt \
         --steps 1 --warmup 1 > $OUT/rehearsal_2rank.json 2> $OUT/rehearsal_2rank.err \
         || { tail -30 $OUT/rehearsal_2rank.err; exit 1; } ;;
     c3)
-      timeout -k 10 1000 python -u bench.py --workload c3 > $OUT/bench_c3.json 2> $OUT/bench_c3.err \
+      timeout -k 10 1000 python -u bench.py --full --workload c3 > $OUT/bench_c3.json 2> $OUT/bench_c3.err \
         || { tail -30 $OUT/bench_c3.err; exit 1; } ;;
     c3trace)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/c3trace \

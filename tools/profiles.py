@@ -229,10 +229,15 @@ def build_traffic3d(base, spec):
 
 def build_trace_summary(base, spec):
     """trace_summary.json: the timed C3 chunk launches' average duration in
-    the kernel trace of a default bench.py run, next to the run's own
+    the kernel trace of a `bench.py --full` run (the committed traces'
+    default run, from before the option), next to the run's own
     HIP-event figure. The timed launches are the search dispatches longer
     than min_ms, less the first `skip_first` (warm-up chunks) and the last
-    `skip_last` (the C2 legs' launches)."""
+    `skip_last` (the C2 legs' launches). The defaults (2 and 4) fit the
+    committed traces, whose two warmup steps ran one chunk each; a warmup
+    step now runs a whole slice, so a manifest for a new trace sets
+    `skip_first` to its warmup launches (13 per step at the default
+    --c3-slice 50 and 4-submap chunks)."""
     d = [dur / 1e6 for _, _, dur in read_trace(os.path.join(base, spec["trace"]), "fast2d_search")
          if dur / 1e6 > spec.get("min_ms", 300.0)]
     timed = d[spec.get("skip_first", 2):len(d) - spec.get("skip_last", 4)]

@@ -1,4 +1,4 @@
-"""Reads a rocprofv3 kernel trace of a default bench.py run and reports
+"""Reads a rocprofv3 kernel trace of a `bench.py --full` run and reports
 (1) the C3 chunk launches of fast2d_search_v4 (dispatches over --c3-min-ms)
 against the bench line's kernel_ms_avg, and (2) the timeline of each C5 step:
 wall from its first to its last kernel, the union of busy time, the time
