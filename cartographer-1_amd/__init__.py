@@ -67,6 +67,12 @@ class RtOptions(C.Structure):
                 ("rotation_delta_cost_weight", C.c_double)]
 
 
+class Inserter2DOptions(C.Structure):
+    """csm_inserter2d_options (ProbabilityGridRangeDataInserterOptions2D)."""
+    _fields_ = [("hit_probability", C.c_float), ("miss_probability", C.c_float),
+                ("insert_free_space", C.c_int32)]
+
+
 class Pair2D(C.Structure):
     _fields_ = [("submap", C.c_int32), ("scan", C.c_int32), ("full_submap", C.c_int32),
                 ("min_score", C.c_float), ("initial", Pose2D)]
@@ -335,6 +341,28 @@ _SIGNATURES = {
                                             C.POINTER(C.c_int32), C.POINTER(MapLimits)]),
     "csm_grid2d_crop": (C.c_int, [C.POINTER(MapLimits), C.POINTER(C.c_uint16),
                                   C.POINTER(MapLimits), C.POINTER(C.c_uint16), C.c_int64]),
+    "csm_probability_grid_create": (C.c_int, [C.c_void_p, C.POINTER(MapLimits),
+                                              C.POINTER(C.c_uint16), C.POINTER(C.c_void_p)]),
+    "csm_probability_grid_destroy": (None, [C.c_void_p]),
+    "csm_probability_grid_limits": (C.c_int, [C.c_void_p, C.POINTER(MapLimits)]),
+    "csm_probability_grid_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.c_int64]),
+    "csm_probability_grid_insert": (C.c_int, [C.c_void_p, C.POINTER(Inserter2DOptions),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                              C.c_int32, C.POINTER(C.c_float), C.c_int32]),
+    "csm_probability_grid_insert_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
+                                                    C.POINTER(Inserter2DOptions), C.c_int32,
+                                                    C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                                    C.POINTER(C.c_float), C.POINTER(C.c_int64),
+                                                    C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "csm_probability_grid_finish": (C.c_int, [C.c_void_p]),
+    "csm_fast2d_create_from_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Fast2DOptions),
+                                              C.POINTER(C.c_void_p)]),
+    "csm_rt2d_match_grid": (C.c_int, [C.c_void_p, C.POINTER(RtOptions), C.c_void_p,
+                                      C.POINTER(Pose2D), C.POINTER(C.c_float), C.c_int32,
+                                      C.POINTER(C.c_double), C.POINTER(Pose2D)]),
+    "csm_ray_to_pixel_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
+    "csm_inserter2d_lookup_table": (C.c_int, [C.c_float, C.POINTER(C.c_uint16)]),
     "csm_pbstream_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "csm_pbstream_close": (None, [C.c_void_p]),
     "csm_pbstream_format_version": (C.c_uint32, [C.c_void_p]),
@@ -680,6 +708,140 @@ def default_context(device: int = 0) -> Context:
     return _default_contexts[device]
 
 
+def _pack_scans(scans):
+    """[(origin xyz, returns (n,3), misses (m,3) or None)] -> the flat arrays
+    csm_probability_grid_insert_batch takes."""
+    origins = np.zeros((len(scans), 3), np.float32)
+    rets, miss = [], []
+    ro = np.zeros(len(scans) + 1, np.int64)
+    mo = np.zeros(len(scans) + 1, np.int64)
+    for i, scan in enumerate(scans):
+        origin, returns = scan[0], scan[1]
+        misses = scan[2] if len(scan) > 2 and scan[2] is not None else np.zeros((0, 3))
+        origins[i] = np.asarray(origin, np.float32).reshape(3)
+        r = _f32_points(returns) if len(returns) else np.zeros((0, 3), np.float32)
+        m = _f32_points(misses) if len(misses) else np.zeros((0, 3), np.float32)
+        rets.append(r)
+        miss.append(m)
+        ro[i + 1] = ro[i] + len(r)
+        mo[i + 1] = mo[i] + len(m)
+    r = np.ascontiguousarray(np.concatenate(rets)) if rets else np.zeros((0, 3), np.float32)
+    m = np.ascontiguousarray(np.concatenate(miss)) if miss else np.zeros((0, 3), np.float32)
+    return origins, r, ro, m, mo
+
+
+class DeviceProbabilityGrid:
+    """A ProbabilityGrid that lives on the device (csm_probability_grid): built
+    there by the reference's range-data inserter bit for bit, grown and cropped
+    there, and read by both 2D matchers without a host copy."""
+
+    def __init__(self, resolution: float, max_x: float, max_y: float, num_x_cells: int,
+                 num_y_cells: int, cells: Optional[np.ndarray] = None,
+                 context: Optional[Context] = None):
+        self.context = context or default_context()
+        self._lib = self.context._lib
+        lim = MapLimits(resolution, max_x, max_y, num_x_cells, num_y_cells)
+        c = None
+        if cells is not None:
+            c = np.ascontiguousarray(cells, np.uint16)
+            if c.size != num_x_cells * num_y_cells:
+                raise ValueError("cells must hold num_x_cells * num_y_cells values")
+        h = C.c_void_p()
+        _check(self._lib.csm_probability_grid_create(
+            self.context.handle, C.byref(lim), _ptr(c, C.c_uint16) if c is not None else None,
+            C.byref(h)), "csm_probability_grid_create")
+        self.handle = h
+        self.min_correspondence_cost = K_MIN_CORRESPONDENCE_COST
+        self.max_correspondence_cost = K_MAX_CORRESPONDENCE_COST
+
+    @staticmethod
+    def from_host(grid: ProbabilityGrid, context: Optional[Context] = None):
+        return DeviceProbabilityGrid(grid.resolution, grid.max_x, grid.max_y, grid.num_x_cells,
+                                     grid.num_y_cells, grid.cells, context)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.csm_probability_grid_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def limits(self) -> MapLimits:
+        lim = MapLimits()
+        _check(self._lib.csm_probability_grid_limits(self.handle, C.byref(lim)),
+               "csm_probability_grid_limits")
+        return lim
+
+    def insert(self, origin, returns, misses=None, hit_probability: float = 0.55,
+               miss_probability: float = 0.49, insert_free_space: bool = True) -> None:
+        """ProbabilityGridRangeDataInserter2D::Insert of one scan (points in the
+        grid's frame)."""
+        origins, r, _, m, _ = _pack_scans([(origin, returns, misses)])
+        o = Inserter2DOptions(hit_probability, miss_probability, int(bool(insert_free_space)))
+        _check(self._lib.csm_probability_grid_insert(
+            self.handle, C.byref(o), _ptr(origins, C.c_float), _ptr(r, C.c_float), len(r),
+            _ptr(m, C.c_float), len(m)), "csm_probability_grid_insert")
+
+    @staticmethod
+    def insert_batch(grids: Sequence["DeviceProbabilityGrid"], grid_of_scan, scans,
+                     hit_probability: float = 0.55, miss_probability: float = 0.49,
+                     insert_free_space: bool = True) -> None:
+        """Many inserts in one call: scan i = (origin, returns[, misses]) goes into
+        grids[grid_of_scan[i]]; scans of one grid in list order, grids
+        concurrently. All grids share one context."""
+        if not grids:
+            return
+        ctx = grids[0].context
+        origins, r, ro, m, mo = _pack_scans(scans)
+        gos = np.ascontiguousarray(grid_of_scan, np.int32)
+        if len(gos) != len(scans):
+            raise ValueError("grid_of_scan and scans differ in length")
+        handles = (C.c_void_p * len(grids))(*[g.handle for g in grids])
+        o = Inserter2DOptions(hit_probability, miss_probability, int(bool(insert_free_space)))
+        _check(ctx._lib.csm_probability_grid_insert_batch(
+            ctx.handle, handles, len(grids), C.byref(o), len(scans), _ptr(gos, C.c_int32),
+            _ptr(origins, C.c_float), _ptr(r, C.c_float), _ptr(ro, C.c_int64),
+            _ptr(m, C.c_float), _ptr(mo, C.c_int64)), "csm_probability_grid_insert_batch")
+
+    def finish(self) -> None:
+        """Submap2D::Finish: crops in place; later inserts fail."""
+        _check(self._lib.csm_probability_grid_finish(self.handle), "csm_probability_grid_finish")
+
+    def to_host(self) -> ProbabilityGrid:
+        lim = self.limits()
+        cells = np.zeros((lim.num_y_cells, lim.num_x_cells), np.uint16)
+        _check(self._lib.csm_probability_grid_read(self.handle, _ptr(cells, C.c_uint16),
+                                                   cells.size), "csm_probability_grid_read")
+        return ProbabilityGrid(lim.resolution, lim.max_x, lim.max_y, cells)
+
+
+def inserter2d_lookup_table(probability: float) -> np.ndarray:
+    """ComputeLookupTableToApplyCorrespondenceCostOdds(Odds(probability))."""
+    out = np.zeros(32768, np.uint16)
+    _check(load_library().csm_inserter2d_lookup_table(probability, _ptr(out, C.c_uint16)),
+           "csm_inserter2d_lookup_table")
+    return out
+
+
+def ray_to_pixel_mask(rays, subpixel_scale: int, context: Optional[Context] = None):
+    """RayToPixelMask for (n, 4) rays (begin x, y, end x, y): a list of (k, 2)
+    int32 arrays of cells, in the reference's order (visible for testing)."""
+    ctx = context or default_context()
+    r = np.ascontiguousarray(np.asarray(rays, np.int32).reshape(-1, 4))
+    off = np.zeros(len(r) + 1, np.int64)
+    _check(ctx._lib.csm_ray_to_pixel_mask(ctx.handle, _ptr(r, C.c_int32), len(r), subpixel_scale,
+                                          None, 0, _ptr(off, C.c_int64)), "csm_ray_to_pixel_mask")
+    out = np.zeros((max(int(off[-1]), 1), 2), np.int32)
+    _check(ctx._lib.csm_ray_to_pixel_mask(ctx.handle, _ptr(r, C.c_int32), len(r), subpixel_scale,
+                                          _ptr(out, C.c_int32), len(out), _ptr(off, C.c_int64)),
+           "csm_ray_to_pixel_mask")
+    return [out[off[i]:off[i + 1]] for i in range(len(r))]
+
+
 @dataclass
 class FastCorrelativeScanMatcherOptions2D:
     """proto::FastCorrelativeScanMatcherOptions2D; defaults from
@@ -709,10 +871,16 @@ class FastCorrelativeScanMatcher2D:
         self._lib = self.context._lib
         self.grid_limits = grid.limits()
         self.options = options
-        cells = np.ascontiguousarray(grid.cells, dtype=np.uint16)
         opts = Fast2DOptions(options.linear_search_window, options.angular_search_window,
                              options.branch_and_bound_depth, options.search_depth)
         h = C.c_void_p()
+        if isinstance(grid, DeviceProbabilityGrid):
+            _check(self._lib.csm_fast2d_create_from_grid(self.context.handle, grid.handle,
+                                                         C.byref(opts), C.byref(h)),
+                   "csm_fast2d_create_from_grid")
+            self.handle = h
+            return
+        cells = np.ascontiguousarray(grid.cells, dtype=np.uint16)
         _check(self._lib.csm_fast2d_create(self.context.handle, C.byref(self.grid_limits),
                                            _ptr(cells, C.c_uint16),
                                            grid.min_correspondence_cost,
@@ -788,6 +956,12 @@ class RealTimeCorrelativeScanMatcher2D:
         init = Pose2D(*initial_pose_estimate)
         score = C.c_double(0.0)
         pose = Pose2D()
+        if isinstance(grid, DeviceProbabilityGrid):
+            _check(self._lib.csm_rt2d_match_grid(
+                self.context.handle, C.byref(opts), grid.handle, C.byref(init),
+                _ptr(pts, C.c_float), len(pts), C.byref(score), C.byref(pose)),
+                "csm_rt2d_match_grid")
+            return float(score.value), pose.as_tuple()
         if isinstance(grid, TSDF2D):
             tsd = np.ascontiguousarray(grid.tsd_cells, dtype=np.uint16)
             wgt = np.ascontiguousarray(grid.weight_cells, dtype=np.uint16)
@@ -1354,3 +1528,7 @@ class Comm:
 def synchronize(context: "Context"):
     if _hip().hipStreamSynchronize(C.c_void_p(context.stream)) != 0:
         raise CsmError("hipStreamSynchronize failed")
+
+
+from .submap_2d import (ActiveSubmaps2D, ProbabilityGridRangeDataInserter2D,  # noqa: E402,F401
+                        ProbabilityGridRangeDataInserterOptions2D, RangeData, Submap2D)

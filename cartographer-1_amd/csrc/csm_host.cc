@@ -1181,10 +1181,14 @@ int32_t csm_context_level_stats(csm_context* ctx, double* candidates, double* ba
   return n;
 }
 
-int csm_fast2d_create(csm_context* ctx, const csm_map_limits* limits,
-                      const uint16_t* cells, float min_cc, float max_cc,
-                      const csm_fast2d_options* options, csm_fast2d** out) {
-  if (!ctx || !limits || !cells || !options || !out) return CSM_EINVAL;
+}  // extern "C"
+
+namespace csm {
+
+int Fast2dCreate(csm_context* ctx, const csm_map_limits* limits, const uint16_t* host_cells,
+                 const uint16_t* dev_cells, float min_cc, float max_cc,
+                 const csm_fast2d_options* options, csm_fast2d** out) {
+  if (!ctx || !limits || (!host_cells && !dev_cells) || !options || !out) return CSM_EINVAL;
   if (options->branch_and_bound_depth < 1 || limits->num_x_cells < 1 ||
       limits->num_y_cells < 1 || !(limits->resolution > 0.) || !(min_cc < max_cc))
     return CSM_EINVAL;
@@ -1326,12 +1330,16 @@ int csm_fast2d_create(csm_context* ctx, const csm_map_limits* limits,
     d.quad_off[l] = static_cast<int32_t>(qoffs[l]);
   }
 
-  DevBuf& dcells = ctx->f2_cells;
   const DevBuf& dq = ctx->f2_qtab;
-  if ((rc = dcells.Reserve(sizeof(uint16_t) * nx * ny))) return rc;
-  CSM_HIP(hipMemcpyAsync(dcells.ptr, cells, sizeof(uint16_t) * nx * ny, hipMemcpyHostToDevice, st));
+  const uint16_t* dcells = dev_cells;
+  if (!dev_cells) {
+    if ((rc = ctx->f2_cells.Reserve(sizeof(uint16_t) * nx * ny))) return rc;
+    CSM_HIP(hipMemcpyAsync(ctx->f2_cells.ptr, host_cells, sizeof(uint16_t) * nx * ny,
+                           hipMemcpyHostToDevice, st));
+    dcells = ctx->f2_cells.as<uint16_t>();
+  }
   const int n0 = nx * ny;
-  CSM_HIP(LaunchPyramidLevel0(dcells.as<uint16_t>(), dq.as<uint8_t>(),
+  CSM_HIP(LaunchPyramidLevel0(dcells, dq.as<uint8_t>(),
                               const_cast<uint8_t*>(d.level[0]), n0, st));
   for (int l = 1; l < depth; ++l) {
     CSM_HIP(LaunchPyramidDouble(d.level[l - 1], d.wide_nx[l - 1], d.wide_ny[l - 1],
@@ -1354,13 +1362,53 @@ int csm_fast2d_create(csm_context* ctx, const csm_map_limits* limits,
   // Correspondence costs (Grid2D::GetCorrespondenceCost, grid_2d.cc) for the
   // CeresScanMatcher2D refinement: the value table with unknown -> max_cc.
   if ((rc = ctx->pool.Take(sizeof(float) * n0, &m->cost))) return rc;
-  CSM_HIP(LaunchCellsToProbability(dcells.as<uint16_t>(), ctx->f2_ctab.as<float>(),
+  CSM_HIP(LaunchCellsToProbability(dcells, ctx->f2_ctab.as<float>(),
                                    m->cost.as<float>(), n0, st));
   // The cells are read from the caller's memory and the context's scratch
   // is reused by the next create: finish before returning.
   CSM_HIP(hipStreamSynchronize(st));
   *out = m.release();
   return CSM_OK;
+}
+
+}  // namespace csm
+
+extern "C" {
+
+int csm_fast2d_create(csm_context* ctx, const csm_map_limits* limits,
+                      const uint16_t* cells, float min_cc, float max_cc,
+                      const csm_fast2d_options* options, csm_fast2d** out) {
+  if (!cells) return CSM_EINVAL;
+  return csm::Fast2dCreate(ctx, limits, cells, nullptr, min_cc, max_cc, options, out);
+}
+
+// The pyramid of a device-resident grid: no host copy of the cells.
+int csm_fast2d_create_from_grid(csm_context* ctx, const csm_probability_grid* grid,
+                                const csm_fast2d_options* options, csm_fast2d** out) {
+  if (!ctx || !grid || !options || !out) return CSM_EINVAL;
+  if (grid->ctx->device != ctx->device) return CSM_EINVAL;
+  csm_map_limits limits;
+  const uint16_t* cells;
+  {
+    // The grid's stream work is ordered before this context's by an event
+    // when the two differ; limits and cells are read under the grid's lock.
+    // An insert into the grid during the create is the caller's error.
+    std::lock_guard<std::mutex> lock(grid->ctx->mu);
+    limits = grid->limits;
+    cells = grid->cells.as<uint16_t>();
+    if (grid->ctx != ctx) {
+      if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+      hipEvent_t ev;
+      CSM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      const bool ok = hipEventRecord(ev, grid->ctx->stream) == hipSuccess &&
+                      hipStreamWaitEvent(ctx->stream, ev, 0) == hipSuccess;
+      (void)hipEventDestroy(ev);
+      if (!ok) return CSM_EHIP;
+    }
+  }
+  // ProbabilityGrid's bounds are the library constants (probability_values.h).
+  const float min_cc = 1.f - (1.f - 0.1f), max_cc = 1.f - 0.1f;
+  return csm::Fast2dCreate(ctx, &limits, nullptr, cells, min_cc, max_cc, options, out);
 }
 
 void csm_fast2d_destroy(csm_fast2d* m) {

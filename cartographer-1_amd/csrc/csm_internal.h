@@ -171,6 +171,9 @@ struct Rt2dCache {
   float truncation = 0.f, max_weight = 0.f;
   float ttab_key[2] = {0.f, 0.f};
   std::vector<uint16_t> cells, wcells;
+  // A device-resident grid (csm_rt2d_match_grid) is keyed by its handle's id
+  // and generation instead of the host cells (grid_id 0: host cells).
+  uint64_t grid_id = 0, grid_gen = 0;
   DevBuf grid, dcells, ptab, ttab, bases, best, dstage, sink;
   PinnedBuf stage, stage_cells, host_key, wg_keys;  // wg_keys: per-workgroup keys (zero-copy path)
 };
@@ -299,6 +302,13 @@ struct csm_context {
   float f2_tab_key[2] = {-1.f, -1.f};
   csm::DevBuf f3_ptab, f3_qtab, f3_grid_cells, f3_grid_batch;
   bool f3_tables = false;
+  // Range-data insertion (insert2d.hip): the hit and miss tables of the last
+  // (hit, miss) probability pair (marker removed, hit first), the batch's
+  // points and scan descriptors with their pinned staging, the crop box.
+  csm::DevBuf ins_tabs, ins_dev, ins_box, ins_rays, ins_count, ins_mask;
+  float ins_tab_key[2] = {-1.f, -1.f};
+  csm::StageRing ins_stage;
+  csm::PinnedBuf ins_box_host;
   ~csm_context() {
     for (csm_context* c : call_all) csm_context_destroy(c);
   }
@@ -315,7 +325,30 @@ struct csm_fast2d {
   csm::DevBuf cost;  // float correspondence costs, x fastest (CeresScanMatcher2D refinement)
 };
 
+// A ProbabilityGrid on the device (insert2d.hip builds and updates it).
+// `limits` and `generation` are host state, current as of the last enqueued
+// call; the cells are current once the context's stream reaches that call.
+struct csm_probability_grid {
+  csm_context* ctx = nullptr;
+  csm_map_limits limits{};
+  csm::DevBuf cells;  // uint16, x fastest
+  csm::DevBuf marks;  // 2 bits per cell, 16 cells per word, rows of mark_words(nx) words; zero between calls
+  uint64_t id = 0;          // process-unique, never 0
+  uint64_t generation = 0;  // bumped by every insert, grow and finish
+  bool finished = false;
+};
+
 namespace csm {
+// csm_fast2d_create's body: cells from host memory (host_cells) or already on
+// the device and ordered on ctx->stream (dev_cells). Caller holds no lock.
+int Fast2dCreate(csm_context* ctx, const csm_map_limits* limits, const uint16_t* host_cells,
+                 const uint16_t* dev_cells, float min_cc, float max_cc,
+                 const csm_fast2d_options* options, csm_fast2d** out);
+// csm_rt2d_match on a device grid (rt2d.hip).
+int Rt2dMatchGrid(csm_context* ctx, const csm_rt_options* o, const csm_probability_grid* grid,
+                  const csm_pose2d* initial, const float* xyz, int32_t n, double* score,
+                  csm_pose2d* pose);
+
 // Call contexts (csm_context::call_free): taken for one single Match call,
 // returned with its timing added to the owner's.
 csm_context* AcquireCallContext(csm_context* owner);

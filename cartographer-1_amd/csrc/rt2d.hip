@@ -12,7 +12,10 @@
 // still reads the outside value: no bounds test in the inner loop. The
 // converted grid is cached on the device and re-made only when the cells
 // (compared with the host copy of the last call) or the padding change — in
-// local SLAM the same submap is matched by consecutive scans.
+// local SLAM the same submap is matched by consecutive scans. A
+// device-resident grid (csm_rt2d_match_grid, insert2d.hip) is converted
+// straight from its device cells and compared by (grid id, generation), which
+// every insert, growth and finish bumps: no host copy and no memcmp.
 //
 // Kernels.
 //   rt2d_convert     cells -> padded float / float2 grid (32768-entry tables,
@@ -304,11 +307,16 @@ struct GridArgs {
   const uint16_t* cells;
   const uint16_t* wcells;  // TSDF weights (nullptr: ProbabilityGrid)
   float truncation, max_weight;
+  // A device-resident ProbabilityGrid (cells == nullptr) and the generation
+  // `limits` was read at.
+  const csm_probability_grid* dev = nullptr;
+  uint64_t dev_generation = 0;
 };
 
 bool ValidGrid(const GridArgs& g) {
   const csm_map_limits* l = g.limits;
-  if (!l || !g.cells || l->num_x_cells < 1 || l->num_y_cells < 1 || !(l->resolution > 0.))
+  if (!l || (!g.cells && !g.dev) || l->num_x_cells < 1 || l->num_y_cells < 1 ||
+      !(l->resolution > 0.))
     return false;
   if (g.wcells && !(g.truncation > 0.f && g.max_weight > 0.f)) return false;
   return static_cast<int64_t>(l->num_x_cells) * l->num_y_cells <= (1ll << 28);
@@ -323,10 +331,19 @@ int EnsureGrid(csm_context* ctx, const GridArgs& g, int P, Rt2dGridDev* out) {
   const size_t ncell = static_cast<size_t>(nx) * ny;
   const bool tsdf = g.wcells != nullptr;
   const int W = nx + 2 * P, H = ny + 2 * P;
-  const bool same = c.valid && c.nx == nx && c.ny == ny && c.P == P && c.tsdf == tsdf &&
-                    (!tsdf || (c.truncation == g.truncation && c.max_weight == g.max_weight)) &&
-                    std::memcmp(c.cells.data(), g.cells, ncell * sizeof(uint16_t)) == 0 &&
-                    (!tsdf || std::memcmp(c.wcells.data(), g.wcells, ncell * sizeof(uint16_t)) == 0);
+  // A device grid changed between the caller's read of its limits and this
+  // lock: the caller's error (the limits no longer describe the cells).
+  if (g.dev && (g.dev->generation != g.dev_generation || g.dev->limits.num_x_cells != nx ||
+                g.dev->limits.num_y_cells != ny))
+    return CSM_EINVAL;
+  const bool same =
+      c.valid && c.nx == nx && c.ny == ny && c.P == P && c.tsdf == tsdf &&
+      (g.dev ? c.grid_id == g.dev->id && c.grid_gen == g.dev_generation
+             : c.grid_id == 0 &&
+                   (!tsdf || (c.truncation == g.truncation && c.max_weight == g.max_weight)) &&
+                   std::memcmp(c.cells.data(), g.cells, ncell * sizeof(uint16_t)) == 0 &&
+                   (!tsdf ||
+                    std::memcmp(c.wcells.data(), g.wcells, ncell * sizeof(uint16_t)) == 0));
   out->W = W;
   out->prob = tsdf ? nullptr : c.grid.as<float>();
   out->tsdf = tsdf ? c.grid.as<float2>() : nullptr;
@@ -356,26 +373,34 @@ int EnsureGrid(csm_context* ctx, const GridArgs& g, int P, Rt2dGridDev* out) {
     c.ttab_ok = true;
   }
   const size_t cell_bytes = ncell * sizeof(uint16_t) * (tsdf ? 2 : 1);
-  if ((rc = c.stage_cells.Reserve(cell_bytes))) return rc;
-  if ((rc = c.dcells.Reserve(cell_bytes))) return rc;
+  if (!g.dev) {
+    if ((rc = c.stage_cells.Reserve(cell_bytes))) return rc;
+    if ((rc = c.dcells.Reserve(cell_bytes))) return rc;
+  }
   if ((rc = c.grid.Reserve(static_cast<size_t>(W) * H * (tsdf ? sizeof(float2) : sizeof(float)))))
     return rc;
   out->prob = tsdf ? nullptr : c.grid.as<float>();
   out->tsdf = tsdf ? c.grid.as<float2>() : nullptr;
-  uint16_t* stage = c.stage_cells.as<uint16_t>();
-  std::memcpy(stage, g.cells, ncell * sizeof(uint16_t));
-  if (tsdf) std::memcpy(stage + ncell, g.wcells, ncell * sizeof(uint16_t));
-  CSM_HIP(hipMemcpyAsync(c.dcells.ptr, stage, cell_bytes, hipMemcpyHostToDevice, st));
-  const uint16_t* dc = c.dcells.as<uint16_t>();
+  // Device grid: its cells are current on this stream (same context).
+  const uint16_t* dc = g.dev ? g.dev->cells.as<uint16_t>() : c.dcells.as<uint16_t>();
+  if (!g.dev) {
+    uint16_t* stage = c.stage_cells.as<uint16_t>();
+    std::memcpy(stage, g.cells, ncell * sizeof(uint16_t));
+    if (tsdf) std::memcpy(stage + ncell, g.wcells, ncell * sizeof(uint16_t));
+    CSM_HIP(hipMemcpyAsync(c.dcells.ptr, stage, cell_bytes, hipMemcpyHostToDevice, st));
+  }
   const int total = W * H;
   hipLaunchKernelGGL(rt2d_convert, dim3((total + 255) / 256), dim3(256), 0, st, dc,
                      tsdf ? dc + ncell : nullptr, tsdf ? c.ttab.as<float>() : c.ptab.as<float>(),
                      tsdf ? c.ttab.as<float>() + 32768 : nullptr, g.truncation, nx, ny, P,
                      tsdf ? nullptr : c.grid.as<float>(), tsdf ? c.grid.as<float2>() : nullptr);
   CSM_HIP(hipGetLastError());
-  c.cells.assign(g.cells, g.cells + ncell);
+  if (g.dev) c.cells.clear();
+  else c.cells.assign(g.cells, g.cells + ncell);
   if (tsdf) c.wcells.assign(g.wcells, g.wcells + ncell);
   else c.wcells.clear();
+  c.grid_id = g.dev ? g.dev->id : 0;
+  c.grid_gen = g.dev_generation;
   c.nx = nx;
   c.ny = ny;
   c.P = P;
@@ -611,6 +636,21 @@ int Rt2dScoreCandidates(csm_context* ctx, const csm_rt_options* o, const GridArg
 }
 
 }  // namespace
+
+int Rt2dMatchGrid(csm_context* ctx, const csm_rt_options* o, const csm_probability_grid* grid,
+                  const csm_pose2d* initial, const float* xyz, int32_t n, double* score,
+                  csm_pose2d* pose) {
+  if (!ctx || !grid || grid->ctx != ctx) return CSM_EINVAL;
+  csm_map_limits limits;
+  GridArgs g{&limits, nullptr, nullptr, 0.f, 0.f, grid, 0};
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    limits = grid->limits;
+    g.dev_generation = grid->generation;
+  }
+  return Rt2dMatch(ctx, o, g, initial, xyz, n, score, pose);
+}
+
 }  // namespace csm
 
 extern "C" {

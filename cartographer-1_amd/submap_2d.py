@@ -1,0 +1,122 @@
+"""Submap2D, ActiveSubmaps2D and ProbabilityGridRangeDataInserter2D on
+device-resident grids (reference mapping/2d/submap_2d.{h,cc},
+probability_grid_range_data_inserter_2d.{h,cc}): the Python mirror of
+include/cartographer_amd/submap_2d.h."""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import numpy as np
+
+from . import Context, DeviceProbabilityGrid, default_context
+
+
+@dataclass
+class RangeData:
+    """sensor::RangeData (sensor/range_data.h:31-35), in the grid's frame."""
+    origin: np.ndarray                       # (3,)
+    returns: np.ndarray                      # (n, 3)
+    misses: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
+
+
+@dataclass
+class ProbabilityGridRangeDataInserterOptions2D:
+    """proto::ProbabilityGridRangeDataInserterOptions2D; defaults from
+    configuration_files/trajectory_builder_2d.lua:81-87."""
+    hit_probability: float = 0.55
+    miss_probability: float = 0.49
+    insert_free_space: bool = True
+
+
+class ProbabilityGridRangeDataInserter2D:
+    """probability_grid_range_data_inserter_2d.h:37-56."""
+
+    def __init__(self, options: Optional[ProbabilityGridRangeDataInserterOptions2D] = None):
+        self.options = options or ProbabilityGridRangeDataInserterOptions2D()
+
+    def Insert(self, range_data: RangeData, grid: DeviceProbabilityGrid) -> None:
+        o = self.options
+        grid.insert(range_data.origin, range_data.returns, range_data.misses, o.hit_probability,
+                    o.miss_probability, o.insert_free_space)
+
+    def InsertBatch(self, range_data: RangeData, grids: List[DeviceProbabilityGrid]) -> None:
+        """The same scan into several grids in one call (ActiveSubmaps2D)."""
+        o = self.options
+        scan = (range_data.origin, range_data.returns, range_data.misses)
+        DeviceProbabilityGrid.insert_batch(grids, list(range(len(grids))), [scan] * len(grids),
+                                           o.hit_probability, o.miss_probability,
+                                           o.insert_free_space)
+
+
+class Submap2D:
+    """submap_2d.h:41-72 (the grid and the insertion counters; the local pose
+    is the origin the submap was created at)."""
+
+    def __init__(self, origin, grid: DeviceProbabilityGrid):
+        self.origin = np.asarray(origin, np.float32)[:2].copy()
+        self._grid = grid
+        self._num_range_data = 0
+        self._insertion_finished = False
+
+    def grid(self) -> DeviceProbabilityGrid:
+        return self._grid
+
+    def num_range_data(self) -> int:
+        return self._num_range_data
+
+    def insertion_finished(self) -> bool:
+        return self._insertion_finished
+
+    def InsertRangeData(self, range_data: RangeData,
+                        inserter: ProbabilityGridRangeDataInserter2D) -> None:
+        assert not self._insertion_finished  # submap_2d.cc:141
+        inserter.Insert(range_data, self._grid)
+        self._num_range_data += 1
+
+    def Finish(self) -> None:
+        assert not self._insertion_finished  # submap_2d.cc:148
+        self._grid.finish()
+        self._insertion_finished = True
+
+
+class ActiveSubmaps2D:
+    """submap_2d.h:86-115, .cc:153-232: at most two submaps; a new 100 x 100 one
+    centred on the scan origin when the newest holds num_range_data scans; every
+    scan goes into all of them (one insert_batch call); the oldest is finished
+    at 2 * num_range_data."""
+
+    kInitialSubmapSize = 100
+
+    def __init__(self, num_range_data: int, resolution: float = 0.05,
+                 inserter_options: Optional[ProbabilityGridRangeDataInserterOptions2D] = None,
+                 context: Optional[Context] = None):
+        self.num_range_data = int(num_range_data)
+        self.resolution = float(np.float32(resolution))  # `float resolution` (:199)
+        self.range_data_inserter = ProbabilityGridRangeDataInserter2D(inserter_options)
+        self.context = context or default_context()
+        self._submaps: List[Submap2D] = []
+
+    def submaps(self) -> List[Submap2D]:
+        return list(self._submaps)
+
+    def _add_submap(self, origin) -> None:
+        if len(self._submaps) >= 2:
+            assert self._submaps[0].insertion_finished()  # :224
+            self._submaps.pop(0)
+        o = np.asarray(origin, np.float32)
+        half = 0.5 * self.kInitialSubmapSize * self.resolution
+        grid = DeviceProbabilityGrid(self.resolution, float(o[0]) + half, float(o[1]) + half,
+                                     self.kInitialSubmapSize, self.kInitialSubmapSize,
+                                     context=self.context)
+        self._submaps.append(Submap2D(o, grid))
+
+    def InsertRangeData(self, range_data: RangeData) -> List[Submap2D]:
+        if not self._submaps or self._submaps[-1].num_range_data() == self.num_range_data:
+            self._add_submap(range_data.origin)
+        self.range_data_inserter.InsertBatch(range_data, [s.grid() for s in self._submaps])
+        for s in self._submaps:
+            s._num_range_data += 1
+        if self._submaps[0].num_range_data() == 2 * self.num_range_data:
+            self._submaps[0].Finish()
+        return self.submaps()

@@ -586,6 +586,99 @@ int csm_grid2d_cropped_limits(const csm_map_limits* limits, const uint16_t* cell
 int csm_grid2d_crop(const csm_map_limits* limits, const uint16_t* cells,
                     csm_map_limits* cropped, uint16_t* cropped_cells, int64_t capacity);
 
+/* ---- device-resident ProbabilityGrid: range-data insertion -----------------
+ * A ProbabilityGrid (mapping/2d/probability_grid.h:31-68, grid_2d.h:40-123)
+ * that lives on the device, is built there by
+ * ProbabilityGridRangeDataInserter2D::Insert
+ * (probability_grid_range_data_inserter_2d.cc:35-98, :124-136) bit for bit, and
+ * feeds both 2D matchers without a host copy. Every call is enqueued on the
+ * grid's context's stream under that context's lock; a later call on the same
+ * context sees it. Only csm_probability_grid_read and _finish wait for the
+ * device. Grids of up to 8192 cells per side (the csm_fast2d_create limit). */
+typedef struct csm_probability_grid csm_probability_grid;
+
+/* proto::ProbabilityGridRangeDataInserterOptions2D
+ * (mapping/proto/probability_grid_range_data_inserter_options_2d.proto:19-30). */
+typedef struct csm_inserter2d_options {
+  float hit_probability, miss_probability;
+  int32_t insert_free_space;
+} csm_inserter2d_options;
+
+/* ProbabilityGrid(const MapLimits&) (probability_grid.cc:26-30): all unknown
+ * when cells is NULL, else num_x_cells * num_y_cells values, x fastest. */
+int csm_probability_grid_create(csm_context* ctx, const csm_map_limits* limits,
+                                const uint16_t* cells_or_null, csm_probability_grid** out);
+void csm_probability_grid_destroy(csm_probability_grid* grid);
+/* Grid2D::limits() (grid_2d.h:51) as of the last enqueued call. */
+int csm_probability_grid_limits(const csm_probability_grid* grid, csm_map_limits* out);
+/* correspondence_cost_cells() (grid_2d.h:103-105): copies the cells to the
+ * host (capacity >= nx * ny values) after waiting for the stream. */
+int csm_probability_grid_read(const csm_probability_grid* grid, uint16_t* out, int64_t capacity);
+
+/* ProbabilityGridRangeDataInserter2D::Insert(range_data, grid)
+ * (probability_grid_range_data_inserter_2d.cc:124-136): GrowAsNeeded (:35-50,
+ * Grid2D::GrowLimits, grid_2d.cc:142-175), then CastRays (:52-98) with
+ * RayToPixelMask at kSubpixelScale 1000, then FinishUpdate. Points are in the
+ * grid's frame. Per cell the result is hit_table[old] where a return lands,
+ * else miss_table[old] where a ray's pixel mask passes (insert_free_space),
+ * else old: the update marker admits one update per cell and Insert, and hits
+ * come first. CSM_EINVAL: a non-finite coordinate, a probability outside
+ * (0, 1), a finished grid; CSM_ERANGE: growth past 8192 cells per side. Either
+ * leaves the grid as it was and enqueues nothing. */
+int csm_probability_grid_insert(csm_probability_grid* grid, const csm_inserter2d_options* options,
+                                const float origin_xyz[3], const float* returns_xyz,
+                                int32_t num_returns, const float* misses_xyz, int32_t num_misses);
+
+/* Many Inserts in one call, e.g. ActiveSubmaps2D::InsertRangeData's two
+ * submaps (submap_2d.cc:185-196) or a rebuild of many submaps. Scan s goes
+ * into grids[grid_of_scan[s]]: origin origins_xyz[3s..], returns
+ * [return_offsets[s], return_offsets[s+1]) of returns_xyz, misses likewise
+ * (both miss arguments NULL: none). Scans of one grid are applied in array
+ * order; scans of different grids run concurrently. All grids belong to ctx
+ * and are distinct. Errors as for csm_probability_grid_insert, for the whole
+ * call. */
+int csm_probability_grid_insert_batch(csm_context* ctx, csm_probability_grid* const* grids,
+                                      int32_t num_grids, const csm_inserter2d_options* options,
+                                      int32_t num_scans, const int32_t* grid_of_scan,
+                                      const float* origins_xyz, const float* returns_xyz,
+                                      const int64_t* return_offsets, const float* misses_xyz,
+                                      const int64_t* miss_offsets);
+
+/* Submap2D::Finish (submap_2d.cc:146-150): replaces the grid by
+ * ComputeCroppedGrid() (probability_grid.cc:91-106; the known-cells box is
+ * the bounding box of the nonzero cells, reduced on the device). An
+ * all-unknown grid crops to 1 x 1 at offset (0, 0). Later inserts return
+ * CSM_EINVAL. */
+int csm_probability_grid_finish(csm_probability_grid* grid);
+
+/* csm_fast2d_create for a device-resident grid: the pyramid is built from the
+ * device cells (no host copy), everything else is shared with
+ * csm_fast2d_create. The grid may be inserted into or destroyed afterwards. */
+int csm_fast2d_create_from_grid(csm_context* ctx, const csm_probability_grid* grid,
+                                const csm_fast2d_options* options, csm_fast2d** out);
+
+/* csm_rt2d_match for a device-resident grid of ctx. The converted grid is
+ * cached per (grid id, generation, padding): every insert, growth and finish
+ * bumps the generation. */
+int csm_rt2d_match_grid(csm_context* ctx, const csm_rt_options* options,
+                        const csm_probability_grid* grid, const csm_pose2d* initial,
+                        const float* points_xyz, int32_t n, double* score, csm_pose2d* pose);
+
+/* Test-visible, like csm_fast2d_read_level: RayToPixelMask
+ * (mapping/internal/2d/ray_to_pixel_mask.cc:29-159) for a batch of rays, the
+ * device function the inserter marks cells with. Ray r is (begin.x, begin.y,
+ * end.x, end.y) in subpixel units, all in [0, 2^30). ray_offsets (num_rays + 1)
+ * receives the cell offsets; cells_xy (may be NULL: offsets only; capacity in
+ * cells >= ray_offsets[num_rays]) receives each ray's cells (x, y) in the
+ * reference's order, begin and end swapped so that begin.x <= end.x. */
+int csm_ray_to_pixel_mask(csm_context* ctx, const int32_t* begin_end_xyxy, int32_t num_rays,
+                          int32_t subpixel_scale, int32_t* cells_xy, int64_t capacity,
+                          int64_t* ray_offsets);
+/* ComputeLookupTableToApplyCorrespondenceCostOdds(Odds(probability))
+ * (probability_values.cc:89-106): 32768 entries, update marker included.
+ * Host-only. */
+int csm_inserter2d_lookup_table(float probability, uint16_t* out /* [32768] */);
+
 /* ---- node clouds: voxel filters -------------------------------------------
  * sensor::VoxelFilter and sensor::AdaptiveVoxelFilter
  * (sensor/internal/voxel_filter.h, voxel_filter.cc:212-232 and :263-268), the
