@@ -662,6 +662,13 @@ __global__ void pyramid_hex(const uint8_t* __restrict__ mlev, int mw, int mh, in
 // sums meet through LDS atomics (C3 launch 571.4 -> 569.0 ms, profiles/r5ba).
 constexpr int kMaxRotChunk = kV4MaxRotChunk;
 constexpr int kLists = kMaxClusterShift + 1;
+#ifndef CSM_PART_SWIZZLE
+// The children sums' LDS layout (V4Shared::PartIndex): 1 rotates a node's
+// row so that the scoring lanes' atomics, consecutive nodes at one child
+// index, fall on 32 different banks; 0 is the plain [node][child] array,
+// whose rows of 16 dwords put them on 2 (EXPERIMENTS.md).
+#define CSM_PART_SWIZZLE 1
+#endif
 
 // kKids: children sums per node, 4 (quad batches only, v4) or 16 (v5: hex
 // batches, and the virtual roots' quad batches in the first 4 columns).
@@ -672,7 +679,16 @@ struct V4Shared {
   static constexpr int kStackLds = kKids == 16 ? kStack2 / 4 : kStack2;
   static constexpr int kStackCapacity = kStackLds + kSpill2;
   uint2 stack[kStackLds];  // w0: xo | yo << 16; w1: sum | rot << 22 | level << 27
-  int part[kBatchNodes][kKids];  // children sums, accumulated by the 4 waves (LDS atomics)
+  // Children sums, accumulated by the 4 waves (LDS atomics): child `kid` of
+  // batch node `node` at PartIndex(node, kid). A row is rotated by node /
+  // (32 / kKids): 32 consecutive nodes' dwords of one child index then lie on
+  // 32 different banks (plain rows: kKids dwords apart, 32 / kKids banks),
+  // and a row still holds its kKids children, so the combine pass's lanes
+  // (node, child) read whole rows.
+  int part[kBatchNodes * kKids];
+  static __device__ __forceinline__ int PartIndex(int node, int kid) {
+    return node * kKids + (CSM_PART_SWIZZLE ? (kid + node / (32 / kKids)) & (kKids - 1) : kid);
+  }
   int batch_hex;                 // the batch's nodes score 16 grandchildren (v5)
   int head;                      // FIFO: LDS ring position of the oldest entry
   int ovf;                       // FIFO: entries in the global overflow stack
@@ -700,6 +716,14 @@ struct V4Shared {
   unsigned long long kp_active[kMaxLevels], kp_oob[kMaxLevels];
 #endif
 };
+
+// Six workgroups per CU (CSM_V4_WAVES) must fit the CU's 160 KiB of LDS at
+// the 1080-beam scans' launch: 2 rotations of 1088 padded points and 832
+// cluster entries, 2 * (1088 * 4 + 832 * 5) B of dynamic LDS next to the
+// static part, each workgroup's sum rounded up to the 1280 B the hardware
+// allocates LDS in.
+static_assert(6 * ((sizeof(V4Shared<16>) + 2 * (1088 * 4 + 832 * 5) + 1279) / 1280 * 1280) <= 160 * 1024,
+              "V4Shared<16>: 6 workgroups per CU no longer fit the LDS");
 
 // The DFS stack: entries [0, kStackLds) in LDS, [kStackLds, kStackLds + kSpill2)
 // in the workgroup's spill region (global memory; the workgroup's own waves
@@ -833,10 +857,10 @@ __device__ __forceinline__ void V4Score(Shared& sh, const uint32_t* cells, const
     }
   }
   if (active && (a0 | a1 | a2 | a3) != 0u) {
-    atomicAdd(&sh.part[node][0], static_cast<int>(a0));  // (xo,     yo)
-    atomicAdd(&sh.part[node][1], static_cast<int>(a1));  // (xo,     yo + h)
-    atomicAdd(&sh.part[node][2], static_cast<int>(a2));  // (xo + h, yo)
-    atomicAdd(&sh.part[node][3], static_cast<int>(a3));  // (xo + h, yo + h)
+    atomicAdd(&sh.part[Shared::PartIndex(node, 0)], static_cast<int>(a0));  // (xo,     yo)
+    atomicAdd(&sh.part[Shared::PartIndex(node, 1)], static_cast<int>(a1));  // (xo,     yo + h)
+    atomicAdd(&sh.part[Shared::PartIndex(node, 2)], static_cast<int>(a2));  // (xo + h, yo)
+    atomicAdd(&sh.part[Shared::PartIndex(node, 3)], static_cast<int>(a3));  // (xo + h, yo + h)
   }
 }
 
@@ -925,7 +949,7 @@ __device__ __forceinline__ void V4ScoreHex(Shared& sh, const uint32_t* cells, co
   if (active) {
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      if (acc[j] != 0u) atomicAdd(&sh.part[node][j], static_cast<int>(acc[j]));
+      if (acc[j] != 0u) atomicAdd(&sh.part[Shared::PartIndex(node, j)], static_cast<int>(acc[j]));
   }
 }
 
@@ -1075,7 +1099,7 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
   uint8_t* cnts = reinterpret_cast<uint8_t*>(cells + rc * (npad + capc));
   const int raw_end = rc * npad;
   uint2* spill = spill_base + static_cast<size_t>(blockIdx.x) * kSpill2;
-  for (int k = tid; k < kBatchNodes * kKids; k += kSearchThreads) sh.part[k / kKids][k % kKids] = 0;
+  for (int k = tid; k < kBatchNodes * kKids; k += kSearchThreads) sh.part[k] = 0;
   if (tid == 0) sh.batch_hex = 0;
   if (tid == 0) sh.high_water = 0;
   unsigned long long local_cands = 0, local_lookups = 0;
@@ -1332,8 +1356,9 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
           if (nd < pn) {
             clvl = sh.node_level[nd] - (hexb ? 2 : 1);
             const int h = 1 << clvl;
-            sum = sh.part[nd][c];
-            sh.part[nd][c] = 0;
+            int& slot = sh.part[sh.PartIndex(nd, c)];
+            sum = slot;
+            slot = 0;
             r = sh.node_rot[nd];
             xo = sh.node_xo[nd] + (c >> (lk >> 1)) * h;
             yo = sh.node_yo[nd] + (c & ((1 << (lk >> 1)) - 1)) * h;
