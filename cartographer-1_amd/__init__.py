@@ -73,6 +73,12 @@ class Inserter2DOptions(C.Structure):
                 ("insert_free_space", C.c_int32)]
 
 
+class Inserter3DOptions(C.Structure):
+    """csm_inserter3d_options (RangeDataInserterOptions3D)."""
+    _fields_ = [("hit_probability", C.c_float), ("miss_probability", C.c_float),
+                ("num_free_space_voxels", C.c_int32)]
+
+
 class Pair2D(C.Structure):
     _fields_ = [("submap", C.c_int32), ("scan", C.c_int32), ("full_submap", C.c_int32),
                 ("min_score", C.c_float), ("initial", Pose2D)]
@@ -363,6 +369,21 @@ _SIGNATURES = {
     "csm_ray_to_pixel_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                         C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "csm_inserter2d_lookup_table": (C.c_int, [C.c_float, C.POINTER(C.c_uint16)]),
+    "csm_hybrid_grid_insert": (C.c_int, [C.c_void_p, C.POINTER(Inserter3DOptions),
+                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32]),
+    "csm_hybrid_grid_insert_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
+                                               C.POINTER(Inserter3DOptions), C.c_int32,
+                                               C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_int64), C.c_int32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_float), C.c_int32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "csm_hybrid_grid_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.c_int64]),
+    "csm_hybrid_grid_insert_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64)]),
+    "csm_inserter3d_lookup_table": (C.c_int, [C.c_float, C.POINTER(C.c_uint16)]),
+    "csm_rotate_histogram": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_float,
+                                       C.POINTER(C.c_float)]),
     "csm_pbstream_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "csm_pbstream_close": (None, [C.c_void_p]),
     "csm_pbstream_format_version": (C.c_uint32, [C.c_void_p]),
@@ -1314,7 +1335,7 @@ class SyntheticWorld2D:
 from .matching3d import (FastCorrelativeScanMatcher3D, FastCorrelativeScanMatcherOptions3D,  # noqa: E402,F401
                          HybridGrid, NodeData3D, NodeSet3D, PAIR3_DTYPE, RESULT3_DTYPE,
                          RealTimeCorrelativeScanMatcher3D, SyntheticWorld3D, ceres_refine_batch_3d,
-                         make_pairs_3d, match_batch_3d)
+                         inserter3d_lookup_table, make_pairs_3d, match_batch_3d, rotate_histogram)
 
 
 # --------------------------------------------------------------------------
@@ -1532,3 +1553,5 @@ def synchronize(context: "Context"):
 
 from .submap_2d import (ActiveSubmaps2D, ProbabilityGridRangeDataInserter2D,  # noqa: E402,F401
                         ProbabilityGridRangeDataInserterOptions2D, RangeData, Submap2D)
+from .submap_3d import (ActiveSubmaps3D, RangeDataInserter3D,  # noqa: E402,F401
+                        RangeDataInserterOptions3D, Submap3D, SubmapsOptions3D)

@@ -309,6 +309,12 @@ struct csm_context {
   float ins_tab_key[2] = {-1.f, -1.f};
   csm::StageRing ins_stage;
   csm::PinnedBuf ins_box_host;
+  // 3D range-data insertion (insert3d.hip): the hit and miss tables of the
+  // last (hit, miss) pair, the value-to-probability table, a batch's job
+  // descriptors and returns with their pinned staging.
+  csm::DevBuf ins3_tabs, ins3_ptab, ins3_dev;
+  float ins3_tab_key[2] = {-1.f, -1.f};
+  csm::StageRing ins3_stage;
   ~csm_context() {
     for (csm_context* c : call_all) csm_context_destroy(c);
   }
@@ -367,7 +373,9 @@ class CallContext {
 };
 }  // namespace csm
 
-// A HybridGrid on the device (host3d.cc builds it).
+// A HybridGrid on the device (host3d.cc builds it, insert3d.hip updates it).
+// `brick`, `grid_size` and `generation` are host state, current as of the last
+// enqueued call; the bricks are current once the context's stream reaches it.
 struct csm_hybrid_grid {
   csm_context* ctx = nullptr;
   // Recorded on ctx->stream after the build's kernels (creates return
@@ -384,6 +392,13 @@ struct csm_hybrid_grid {
   int prob_wide_pad = 0;
   csm::DevBuf prob_col;   // padded by prob_col_pad cells, z fastest (rt3d_score5)
   int prob_col_pad = 0;
+  // Bumped by every insert that touches a cell; the padded copies above are
+  // those of the generation recorded next to them and are re-made when it
+  // differs (RunRt3d).
+  uint64_t generation = 0;
+  uint64_t prob_pad_gen = 0, prob_wide_gen = 0, prob_col_gen = 0;
+  // csm_hybrid_grid_insert_stats' two counters, made by the first insert.
+  csm::DevBuf insert_stats;
 };
 
 namespace csm {

@@ -402,6 +402,7 @@ void csm_hybrid_grid_destroy(csm_hybrid_grid* g) {
   (void)hipSetDevice(g->ctx->device);
   g->ctx->pool.Give(&g->values);  // reused by the next create
   g->ctx->pool.Give(&g->prob);
+  g->ctx->pool.Give(&g->insert_stats);
   if (g->ready) (void)hipEventDestroy(g->ready);
   delete g;
 }
@@ -511,12 +512,13 @@ int RunRt3d(csm_context* ctx, const csm_rt_options* o, const csm_hybrid_grid* gr
                   static_cast<int64_t>(gb.nx + 2) * (gb.ny + 2) * (gb.nz + 2) < (int64_t{1} << 29) &&
                   static_cast<int64_t>(gb.ny + 2) * (gb.nz + 2) < (int64_t{1} << 24);
   if (dscores && !v2) return CSM_ERANGE;
-  if (v2 && !grid->prob_pad_ready) {
+  if (v2 && (!grid->prob_pad_ready || grid->prob_pad_gen != grid->generation)) {
     csm_hybrid_grid* g = const_cast<csm_hybrid_grid*>(grid);
     if ((rc = g->prob_pad.Reserve(sizeof(float) * (gb.nx + 2) * (gb.ny + 2) * (gb.nz + 2))))
       return rc;
     CSM_HIP(LaunchPadProbBrick(grid->prob.as<float>(), gb, g->prob_pad.as<float>(), st));
     g->prob_pad_ready = true;
+    g->prob_pad_gen = grid->generation;
   }
   // v4 (rotation lanes) over a brick padded by P cells, P = the translation
   // lattice's reach in cells + 2, when its byte offsets are exact in float.
@@ -548,12 +550,13 @@ int RunRt3d(csm_context* ctx, const csm_rt_options* o, const csm_hybrid_grid* gr
   }
   if (v4) {
     csm_hybrid_grid* g = const_cast<csm_hybrid_grid*>(grid);
-    if (g->prob_wide_pad != P) {
+    if (g->prob_wide_pad != P || g->prob_wide_gen != g->generation) {
       if ((rc = g->prob_wide.Reserve(sizeof(float) * (gb.nx + 2 * P) * (gb.ny + 2 * P) *
                                      (gb.nz + 2 * P))))
         return rc;
       CSM_HIP(LaunchPadProbBrickP(grid->prob.as<float>(), gb, P, g->prob_wide.as<float>(), st));
       g->prob_wide_pad = P;
+      g->prob_wide_gen = g->generation;
     }
     // Rotations in 4 x 4 x 4 blocks of the (rx, ry, rz) lattice (one block
     // per 64 lanes; holes past the lattice edge carry index -1), or in the
@@ -616,12 +619,13 @@ int RunRt3d(csm_context* ctx, const csm_rt_options* o, const csm_hybrid_grid* gr
     const bool v5 = !std::getenv("CSM_RT3D_V4") && nl >= 3 && nl <= 15 && (nl & 1);
     if (v5) {
       csm_hybrid_grid* g = const_cast<csm_hybrid_grid*>(grid);
-      if (g->prob_col_pad != P) {
+      if (g->prob_col_pad != P || g->prob_col_gen != g->generation) {
         if ((rc = g->prob_col.Reserve(sizeof(float) * (gb.nx + 2 * P) * (gb.ny + 2 * P) *
                                       (gb.nz + 2 * P))))
           return rc;
         CSM_HIP(LaunchPadProbBrickZ(grid->prob.as<float>(), gb, P, g->prob_col.as<float>(), st));
         g->prob_col_pad = P;
+        g->prob_col_gen = g->generation;
       }
       // Per column: step 0's scaled translation and the per-axis thresholds
       // half - drift - allowance (drift: the largest |t'(k) - t'(0) - k e_z|;
@@ -1067,7 +1071,7 @@ int64_t csm_fast3d_device_bytes(const csm_fast3d* m) {
 
 int64_t csm_hybrid_grid_device_bytes(const csm_hybrid_grid* g) {
   return g ? static_cast<int64_t>(g->values.bytes + g->prob.bytes + g->prob_pad.bytes +
-                                  g->prob_wide.bytes + g->prob_col.bytes)
+                                  g->prob_wide.bytes + g->prob_col.bytes + g->insert_stats.bytes)
            : 0;
 }
 

@@ -1,0 +1,786 @@
+// RangeDataInserter3D::Insert on the device brick of a csm_hybrid_grid, on
+// gfx950 (range_data_inserter_3d.cc:44-74, :109-137; hybrid_grid.h
+// ApplyLookupTable / FinishUpdate :497-521, DynamicGrid::Grow :384-399;
+// submap_3d.cc:91-99; probability_values.cc:76-87), and the host pieces of
+// Submap3D next to it (rotational_scan_matcher.cc:138-158).
+//
+// Why the result does not depend on thread order. Within one Insert the
+// update marker admits one table lookup per cell and every hit is applied
+// before any miss, so a cell ends as hit_table[old] if a return lands in it,
+// else miss_table[old] if it lies on a ray's miss span, else old. The device
+// keeps the reference's own marker: bit 15 of the cell's value. A thread that
+// wants to update a cell sets the bit with an atomicOr on the 32-bit word that
+// holds the cell and its neighbour; exactly one thread sees the bit clear in
+// the value the atomic returns, and that thread alone replaces the low 15
+// bits (an atomicXor of old ^ table[old], which leaves the neighbour's half
+// as it is). Which thread wins does not matter: every contender would write
+// the same table[old]. Hits and misses are separate launches, so every hit
+// cell carries the marker before the first miss is tried. A third launch
+// walks the same points and spans, clears each marker with an atomicAnd (one
+// thread per cell sees it set in the returned value) and that thread writes
+// the cell's float probability. No side buffer exists, so nothing has to be
+// cleared between calls, and every pass costs returns x touched cells.
+//
+// Kernels. blockIdx.y is the job (one scan into one grid) of a round.
+//   insert3d_hits  one thread per return: transform, range filter, cell, hit.
+//   insert3d_rays  <false>: the miss span of every ray; a group of G lanes
+//                  (G a power of two near num_free_space_voxels, at most 64)
+//                  shares a ray. <true>: FinishUpdate over the hit cell and
+//                  the same span, with the probability brick's update.
+//   insert3d_grow  a grown grid's new bricks: the old cells at their offset,
+//                  unknown (0, kMinProbability) elsewhere.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+#include "csm_internal.h"
+
+namespace csm {
+namespace {
+
+constexpr uint32_t kMarker = 0x8000u;  // kUpdateMarker (probability_values.h:94)
+constexpr int kMaxSamples = 1 << 15;   // CHECK_LT(num_samples, 1 << 15), :58
+constexpr float kMaxCell = 1.0e9f;     // |coordinate / resolution| the index arithmetic takes
+
+// One (grid, scan) job of a round, as the kernels see it. The origin is
+// already in the grid's frame; the returns are transformed on the device.
+struct Job3 {
+  uint32_t* words;  // the value brick, two cells per word
+  float* prob;
+  unsigned long long* stats;  // [0] cells visited by the finish pass, [1] cells updated
+  Brick3 b;
+  float resolution;
+  float ox, oy, oz;     // origin (range_data.origin after the transform)
+  int cx, cy, cz;       // its cell
+  int has_transform;
+  float t[3], q[4];     // submap from local: translation, rotation (w, x, y, z)
+  float max_range;      // <= 0: none
+  int64_t begin;        // first return in the points array
+  int num_returns;
+};
+
+// Rigid3f * Vector3f (rigid_transform.h:191-196) with Eigen's
+// Quaternion::_transformVector: uv = 2 q.vec x v, v + w uv + q.vec x uv.
+__host__ __device__ inline void Apply3(const float* t, const float* q, float* p) {
+#ifdef __HIP_DEVICE_COMPILE__
+#define CSM_MUL(a, b) __fmul_rn(a, b)
+#define CSM_ADD(a, b) __fadd_rn(a, b)
+#define CSM_SUB(a, b) __fsub_rn(a, b)
+#else
+#define CSM_MUL(a, b) ((a) * (b))
+#define CSM_ADD(a, b) ((a) + (b))
+#define CSM_SUB(a, b) ((a) - (b))
+#endif
+  const float qw = q[0], qx = q[1], qy = q[2], qz = q[3];
+  const float vx = p[0], vy = p[1], vz = p[2];
+  float ux = CSM_SUB(CSM_MUL(qy, vz), CSM_MUL(qz, vy));
+  float uy = CSM_SUB(CSM_MUL(qz, vx), CSM_MUL(qx, vz));
+  float uz = CSM_SUB(CSM_MUL(qx, vy), CSM_MUL(qy, vx));
+  ux = CSM_ADD(ux, ux);
+  uy = CSM_ADD(uy, uy);
+  uz = CSM_ADD(uz, uz);
+  const float cx = CSM_SUB(CSM_MUL(qy, uz), CSM_MUL(qz, uy));
+  const float cy = CSM_SUB(CSM_MUL(qz, ux), CSM_MUL(qx, uz));
+  const float cz = CSM_SUB(CSM_MUL(qx, uy), CSM_MUL(qy, ux));
+  p[0] = CSM_ADD(CSM_ADD(CSM_ADD(vx, CSM_MUL(qw, ux)), cx), t[0]);
+  p[1] = CSM_ADD(CSM_ADD(CSM_ADD(vy, CSM_MUL(qw, uy)), cy), t[1]);
+  p[2] = CSM_ADD(CSM_ADD(CSM_ADD(vz, CSM_MUL(qw, uz)), cz), t[2]);
+}
+
+// (p - origin).norm() as Eigen sums three squares: x0 + (x1 + x2).
+__host__ __device__ inline float RangeOf(const float* p, float ox, float oy, float oz) {
+  const float dx = CSM_SUB(p[0], ox), dy = CSM_SUB(p[1], oy), dz = CSM_SUB(p[2], oz);
+  const float s = CSM_ADD(CSM_MUL(dx, dx), CSM_ADD(CSM_MUL(dy, dy), CSM_MUL(dz, dz)));
+#ifdef __HIP_DEVICE_COMPILE__
+  return __fsqrt_rn(s);
+#else
+  return std::sqrt(s);
+#endif
+}
+
+// HybridGrid::GetCellIndex (hybrid_grid.h:428-433): float division, lround.
+__device__ inline float CellF(float v, float resolution) {
+  return roundf(__fdiv_rn(v, resolution));
+}
+
+// The return's position in the grid's frame and whether the job keeps it
+// (FilterRangeDataByMaxRange, submap_3d.cc:91-99).
+__host__ __device__ inline bool JobPoint(const Job3& j, const float* src, float* p) {
+  p[0] = src[0];
+  p[1] = src[1];
+  p[2] = src[2];
+  if (j.has_transform) Apply3(j.t, j.q, p);
+  if (j.max_range > 0.f && !(RangeOf(p, j.ox, j.oy, j.oz) <= j.max_range)) return false;
+  return true;
+}
+
+// The miss span of a ray (InsertMissesIntoGrid, :44-74).
+struct Span3 {
+  int dx, dy, dz, num_samples, first;
+};
+__host__ __device__ inline Span3 MakeSpan(int cx, int cy, int cz, int hx, int hy, int hz,
+                                          int free_voxels) {
+  Span3 s;
+  s.dx = hx - cx;
+  s.dy = hy - cy;
+  s.dz = hz - cz;
+  const int ax = s.dx < 0 ? -s.dx : s.dx, ay = s.dy < 0 ? -s.dy : s.dy,
+            az = s.dz < 0 ? -s.dz : s.dz;
+  s.num_samples = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
+  s.first = s.num_samples > free_voxels ? s.num_samples - free_voxels : 0;
+  return s;
+}
+// origin_cell + delta * position / num_samples, C++ integer division;
+// num_samples > 0, |delta| and position < 2^15.
+__host__ __device__ inline void SpanCell(int cx, int cy, int cz, const Span3& s, int position,
+                                         int* x, int* y, int* z) {
+  *x = cx + s.dx * position / s.num_samples;
+  *y = cy + s.dy * position / s.num_samples;
+  *z = cz + s.dz * position / s.num_samples;
+}
+
+// The cell's index in the brick, -1 outside it.
+__device__ inline int64_t BrickIndex(const Brick3& b, int x, int y, int z) {
+  const unsigned ux = static_cast<unsigned>(x - b.ox), uy = static_cast<unsigned>(y - b.oy),
+                 uz = static_cast<unsigned>(z - b.oz);
+  if (ux >= static_cast<unsigned>(b.nx) || uy >= static_cast<unsigned>(b.ny) ||
+      uz >= static_cast<unsigned>(b.nz))
+    return -1;
+  return (static_cast<int64_t>(uz) * b.ny + uy) * b.nx + ux;
+}
+
+// ApplyLookupTable: table[old] for the one thread that sets the marker.
+__device__ inline void ApplyCell(const Job3& j, int x, int y, int z,
+                                 const uint16_t* __restrict__ table) {
+  const int64_t i = BrickIndex(j.b, x, y, z);
+  if (i < 0) return;
+  uint32_t* w = j.words + (i >> 1);
+  const int shift = (i & 1) * 16;
+  const uint32_t m = kMarker << shift;
+  // The marker only rises during these passes: a stale zero costs one
+  // redundant atomic, never a lost update. Rays of one scan share the cells
+  // near the origin and near each other's hits; this keeps them off the word.
+  if (__atomic_load_n(w, __ATOMIC_RELAXED) & m) return;
+  const uint32_t old = atomicOr(w, m);
+  if (old & m) return;
+  const uint32_t v = (old >> shift) & 0x7fffu;
+  atomicXor(w, (v ^ table[v]) << shift);
+}
+
+// FinishUpdate for one cell: the thread that clears the marker also writes
+// the probability. Returns 1 when this thread was the one.
+__device__ inline int FinishCell(const Job3& j, int x, int y, int z,
+                                 const float* __restrict__ ptab) {
+  const int64_t i = BrickIndex(j.b, x, y, z);
+  if (i < 0) return 0;
+  uint32_t* w = j.words + (i >> 1);
+  const int shift = (i & 1) * 16;
+  const uint32_t m = kMarker << shift;
+  if (!(__atomic_load_n(w, __ATOMIC_RELAXED) & m)) return 0;
+  const uint32_t old = atomicAnd(w, ~m);
+  if (!(old & m)) return 0;
+  j.prob[i] = ptab[(old >> shift) & 0x7fffu];
+  return 1;
+}
+
+__device__ inline bool HitCellOf(const Job3& j, const float* __restrict__ points, int i, int* hx,
+                                 int* hy, int* hz) {
+  float p[3];
+  if (!JobPoint(j, points + 3 * (j.begin + i), p)) return false;
+  *hx = static_cast<int>(CellF(p[0], j.resolution));
+  *hy = static_cast<int>(CellF(p[1], j.resolution));
+  *hz = static_cast<int>(CellF(p[2], j.resolution));
+  return true;
+}
+
+// tabs: hit table then miss table, 32768 entries each, update marker removed.
+__global__ void __launch_bounds__(256)
+insert3d_hits(const Job3* __restrict__ jobs, const float* __restrict__ points,
+              const uint16_t* __restrict__ tabs) {
+  const Job3 j = jobs[blockIdx.y];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < j.num_returns;
+       i += gridDim.x * blockDim.x) {
+    int hx, hy, hz;
+    if (HitCellOf(j, points, i, &hx, &hy, &hz)) ApplyCell(j, hx, hy, hz, tabs);
+  }
+}
+
+template <bool kFinish>
+__global__ void __launch_bounds__(256)
+insert3d_rays(const Job3* __restrict__ jobs, const float* __restrict__ points,
+              const uint16_t* __restrict__ tabs, const float* __restrict__ ptab, int free_voxels,
+              int group_bits) {
+  const Job3 j = jobs[blockIdx.y];
+  const int group = 1 << group_bits;
+  const int sub = threadIdx.x & (group - 1);
+  const int rays_per_block = blockDim.x >> group_bits;
+  int visited = 0, updated = 0;
+  for (int ray = blockIdx.x * rays_per_block + (threadIdx.x >> group_bits); ray < j.num_returns;
+       ray += gridDim.x * rays_per_block) {
+    int hx, hy, hz;
+    if (!HitCellOf(j, points, ray, &hx, &hy, &hz)) continue;
+    if (kFinish && sub == 0) {
+      ++visited;
+      updated += FinishCell(j, hx, hy, hz, ptab);
+    }
+    const Span3 s = MakeSpan(j.cx, j.cy, j.cz, hx, hy, hz, free_voxels);
+    if (s.num_samples >= kMaxSamples) continue;  // the host refuses these
+    for (int position = s.first + sub; position < s.num_samples; position += group) {
+      int x, y, z;
+      SpanCell(j.cx, j.cy, j.cz, s, position, &x, &y, &z);
+      if (kFinish) {
+        ++visited;
+        updated += FinishCell(j, x, y, z, ptab);
+      } else {
+        ApplyCell(j, x, y, z, tabs + 32768);
+      }
+    }
+  }
+  if (kFinish) {
+    // One atomic pair per wave.
+    for (int o = 32; o > 0; o >>= 1) {
+      visited += __shfl_xor(visited, o);
+      updated += __shfl_xor(updated, o);
+    }
+    if ((threadIdx.x & 63) == 0 && visited) {
+      atomicAdd(j.stats, static_cast<unsigned long long>(visited));
+      if (updated) atomicAdd(j.stats + 1, static_cast<unsigned long long>(updated));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256)
+insert3d_grow(const uint16_t* __restrict__ old_values, const float* __restrict__ old_prob,
+              Brick3 ob, uint16_t* __restrict__ values, float* __restrict__ prob, Brick3 nb,
+              float unknown) {
+  const int64_t total = static_cast<int64_t>(nb.nx) * nb.ny * nb.nz;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int x = static_cast<int>(i % nb.nx) + nb.ox;
+    const int y = static_cast<int>(i / nb.nx % nb.ny) + nb.oy;
+    const int z = static_cast<int>(i / nb.nx / nb.ny) + nb.oz;
+    const int64_t k = BrickIndex(ob, x, y, z);
+    values[i] = k < 0 ? uint16_t{0} : old_values[k];
+    prob[i] = k < 0 ? unknown : old_prob[k];
+  }
+}
+
+// ---------------------------------------------------------------- host -----
+
+void MoveBuf(DevBuf* from, DevBuf* to) {
+  to->ptr = from->ptr;
+  to->bytes = from->bytes;
+  from->ptr = nullptr;
+  from->bytes = 0;
+}
+
+// probability_values.h:32-45, :37-43 and common/math.h Clamp, in float.
+constexpr float kMinP = 0.1f, kMaxP = 1.f - kMinP;
+uint16_t ProbabilityToValue(float p) {
+  const float c = p > kMaxP ? kMaxP : (p < kMinP ? kMinP : p);
+  return static_cast<uint16_t>(
+      static_cast<int>(std::lround((c - kMinP) * (32766.f / (kMaxP - kMinP)))) + 1);
+}
+float Odds(float p) { return p / (1.f - p); }
+float ProbabilityFromOdds(float odds) { return odds / (odds + 1.f); }
+
+// kValueToProbability (probability_values.cc:26-66), the table
+// csm_hybrid_grid_create fills the probability brick from.
+void ProbabilityTable(float* out) {
+  const float scale = (kMaxP - kMinP) / (32768 - 2.f);
+  for (int v = 0; v < 32768; ++v) out[v] = v == 0 ? kMinP : v * scale + (kMinP - scale);
+}
+
+// ComputeLookupTableToApplyOdds (probability_values.cc:76-87).
+void LookupTable3(float odds, uint16_t* out) {
+  std::vector<float> ptab(32768);
+  ProbabilityTable(ptab.data());
+  constexpr uint16_t kUpdateMarker = 1u << 15;
+  out[0] = ProbabilityToValue(ProbabilityFromOdds(odds)) + kUpdateMarker;
+  for (int cell = 1; cell < 32768; ++cell)
+    out[cell] = ProbabilityToValue(ProbabilityFromOdds(odds * Odds(ptab[cell]))) + kUpdateMarker;
+}
+
+int EnsureTables3(csm_context* ctx, const csm_inserter3d_options* o) {
+  int rc;
+  if (!ctx->ins3_ptab.ptr) {
+    std::vector<float> ptab(32768);
+    ProbabilityTable(ptab.data());
+    if ((rc = ctx->ins3_ptab.Reserve(sizeof(float) * 32768))) return rc;
+    CSM_HIP(hipMemcpy(ctx->ins3_ptab.ptr, ptab.data(), sizeof(float) * 32768,
+                      hipMemcpyHostToDevice));
+  }
+  if (ctx->ins3_tab_key[0] == o->hit_probability && ctx->ins3_tab_key[1] == o->miss_probability)
+    return CSM_OK;
+  std::vector<uint16_t> tabs(2 * 32768);
+  LookupTable3(Odds(o->hit_probability), tabs.data());
+  LookupTable3(Odds(o->miss_probability), tabs.data() + 32768);
+  for (uint16_t& v : tabs) v &= 0x7fff;  // the kernels keep the marker themselves
+  // Earlier inserts on the stream may still read the previous tables.
+  CSM_HIP(hipStreamSynchronize(ctx->stream));
+  if ((rc = ctx->ins3_tabs.Reserve(tabs.size() * sizeof(uint16_t)))) return rc;
+  CSM_HIP(hipMemcpy(ctx->ins3_tabs.ptr, tabs.data(), tabs.size() * sizeof(uint16_t),
+                    hipMemcpyHostToDevice));
+  ctx->ins3_tab_key[0] = o->hit_probability;
+  ctx->ins3_tab_key[1] = o->miss_probability;
+  return CSM_OK;
+}
+
+unsigned Blocks(int64_t items, int per_block, int cap) {
+  const int64_t b = (items + per_block - 1) / per_block;
+  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(b, cap)));
+}
+
+bool Finite3(const float* p) {
+  return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+}
+
+// Bytes of a value brick of n cells: the kernels address it in 32-bit words.
+size_t ValueBytes(int64_t n) {
+  return static_cast<size_t>((n + 1) & ~int64_t{1}) * sizeof(uint16_t);
+}
+
+struct Box3 {
+  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+  bool empty() const { return hi[0] < lo[0]; }
+  void Add(int x, int y, int z) {
+    const int c[3] = {x, y, z};
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = std::min(lo[a], c[a]);
+      hi[a] = std::max(hi[a], c[a]);
+    }
+  }
+};
+
+// GetCellIndex on the host without a libm call per axis: truncate, then step
+// away from zero when the remainder reaches a half (the subtraction is exact).
+// False when the quotient is past kMaxCell.
+bool HostCell(float v, float resolution, int* out) {
+  const float q = v / resolution;
+  if (!(std::fabs(q) < kMaxCell)) return false;
+  int t = static_cast<int>(q);
+  const float d = q - static_cast<float>(t);
+  if (d >= 0.5f) ++t;
+  else if (d <= -0.5f) --t;
+  *out = t;
+  return true;
+}
+
+// A chunk of one job's returns for the planning pass.
+constexpr int kPlanChunk = 8192;
+constexpr int64_t kPlanThreaded = 32768;  // returns per call from which threads pay off
+constexpr size_t kPlanThreads = 8;
+struct PlanTask {
+  int job, i0, i1;
+  Box3 box;
+  int rc;
+};
+
+// The box of the cells returns [i0, i1) of job j touch: per ray the hit cell
+// and the first miss cell. CSM_ERANGE for a ray the reference would
+// CHECK-fail on or a coordinate past the index arithmetic.
+int PlanReturns(const Job3& j, const float* returns, int i0, int i1, int free_voxels, Box3* box) {
+  for (int i = i0; i < i1; ++i) {
+    float p[3];
+    if (!JobPoint(j, returns + 3 * (j.begin + i), p)) continue;
+    int hx, hy, hz;
+    if (!HostCell(p[0], j.resolution, &hx) || !HostCell(p[1], j.resolution, &hy) ||
+        !HostCell(p[2], j.resolution, &hz))
+      return CSM_ERANGE;
+    const Span3 sp = MakeSpan(j.cx, j.cy, j.cz, hx, hy, hz, free_voxels);
+    if (sp.num_samples >= kMaxSamples) return CSM_ERANGE;
+    box->Add(hx, hy, hz);
+    if (sp.first < sp.num_samples) {
+      int x, y, z;
+      SpanCell(j.cx, j.cy, j.cz, sp, sp.first, &x, &y, &z);
+      box->Add(x, y, z);
+    }
+  }
+  return CSM_OK;
+}
+
+struct GridPlan3 {
+  Box3 box;          // the cells this call touches
+  Brick3 after{};    // the brick once the call is done
+  int grid_size = 0;
+  bool touched = false, grew = false;
+  DevBuf values, prob, stats;  // a grown grid's new bricks; the first insert's counters
+  int rounds = 0;
+};
+
+int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_grids,
+                 const csm_inserter3d_options* o, int32_t num_scans, const float* origins,
+                 const float* returns, const int64_t* ret_off, int32_t num_jobs,
+                 const int32_t* grid_of_job, const int32_t* scan_of_job, const float* transforms,
+                 int32_t num_transforms, const int32_t* transform_of_job,
+                 const float* max_ranges, bool ctx_of_grid) {
+  if ((!ctx && !ctx_of_grid) || !grids || !o || num_grids < 1 || num_scans < 0 || num_jobs < 0 ||
+      num_transforms < 0)
+    return CSM_EINVAL;
+  if (num_scans > 0 && (!origins || !ret_off)) return CSM_EINVAL;
+  if (num_jobs > 0 && (!grid_of_job || !scan_of_job)) return CSM_EINVAL;
+  if (num_transforms > 0 && !transforms) return CSM_EINVAL;
+  if (!(o->hit_probability > 0.f && o->hit_probability < 1.f && o->miss_probability > 0.f &&
+        o->miss_probability < 1.f) ||
+      o->num_free_space_voxels < 0)
+    return CSM_EINVAL;
+  for (int g = 0; g < num_grids; ++g)
+    if (!grids[g]) return CSM_EINVAL;
+  if (num_jobs == 0) return CSM_OK;
+  if (num_scans == 0) return CSM_EINVAL;
+  if (ret_off[0] != 0) return CSM_EINVAL;
+  for (int s = 0; s < num_scans; ++s) {
+    if (ret_off[s + 1] < ret_off[s] || ret_off[s + 1] - ret_off[s] > (1 << 24)) return CSM_EINVAL;
+    if (!Finite3(origins + 3 * s)) return CSM_EINVAL;
+  }
+  const int64_t total_ret = ret_off[num_scans];
+  if (total_ret > 0 && !returns) return CSM_EINVAL;
+  for (int64_t i = 0; i < total_ret; ++i)
+    if (!Finite3(returns + 3 * i)) return CSM_EINVAL;
+  for (int64_t i = 0; i < int64_t{7} * num_transforms; ++i)
+    if (!std::isfinite(transforms[i])) return CSM_EINVAL;
+  for (int k = 0; k < num_jobs; ++k) {
+    if (grid_of_job[k] < 0 || grid_of_job[k] >= num_grids || scan_of_job[k] < 0 ||
+        scan_of_job[k] >= num_scans)
+      return CSM_EINVAL;
+    if (transform_of_job && transform_of_job[k] >= num_transforms) return CSM_EINVAL;
+    if (max_ranges && std::isnan(max_ranges[k])) return CSM_EINVAL;
+  }
+  // The points are checked before any handle is read.
+  if (ctx_of_grid) ctx = grids[0]->ctx;
+  if (!ctx) return CSM_EINVAL;
+  for (int g = 0; g < num_grids; ++g) {
+    if (grids[g]->ctx != ctx) return CSM_EINVAL;
+    for (int h = 0; h < g; ++h)
+      if (grids[h] == grids[g]) return CSM_EINVAL;
+  }
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+
+  // Plan on the host, before any launch: every job's origin cell and the box
+  // of the cells it touches. Per ray the first miss cell and the hit cell
+  // bound the span (each axis is monotone in `position`), and every touched
+  // cell ends nonzero (table[0] is nonzero), so the known-cell box afterwards
+  // is the old box united with the touched one.
+  const int free_voxels = o->num_free_space_voxels;
+  std::vector<Job3> jobs(num_jobs);
+  std::vector<GridPlan3> plan(num_grids);
+  std::vector<int> round_of(num_jobs);
+  std::vector<PlanTask> tasks;
+  int64_t planned = 0;
+  int num_rounds = 0;
+  for (int k = 0; k < num_jobs; ++k) {
+    Job3& j = jobs[k];
+    csm_hybrid_grid* g = grids[grid_of_job[k]];
+    GridPlan3& gp = plan[grid_of_job[k]];
+    round_of[k] = gp.rounds++;
+    num_rounds = std::max(num_rounds, gp.rounds);
+    const int s = scan_of_job[k];
+    j.resolution = g->resolution;
+    j.has_transform = transform_of_job && transform_of_job[k] >= 0;
+    float org[3] = {origins[3 * s], origins[3 * s + 1], origins[3 * s + 2]};
+    if (j.has_transform) {
+      const float* tf = transforms + 7 * transform_of_job[k];
+      for (int a = 0; a < 3; ++a) j.t[a] = tf[a];
+      for (int a = 0; a < 4; ++a) j.q[a] = tf[3 + a];
+      Apply3(j.t, j.q, org);
+    } else {
+      j.t[0] = j.t[1] = j.t[2] = 0.f;
+      j.q[0] = 1.f;
+      j.q[1] = j.q[2] = j.q[3] = 0.f;
+    }
+    j.ox = org[0];
+    j.oy = org[1];
+    j.oz = org[2];
+    j.max_range = max_ranges ? max_ranges[k] : 0.f;
+    j.begin = ret_off[s];
+    j.num_returns = static_cast<int>(ret_off[s + 1] - ret_off[s]);
+    if (!HostCell(org[0], j.resolution, &j.cx) || !HostCell(org[1], j.resolution, &j.cy) ||
+        !HostCell(org[2], j.resolution, &j.cz))
+      return CSM_ERANGE;
+    for (int i0 = 0; i0 < j.num_returns; i0 += kPlanChunk)
+      tasks.push_back(PlanTask{k, i0, std::min(j.num_returns, i0 + kPlanChunk), Box3{}, CSM_OK});
+    planned += j.num_returns;
+  }
+  {
+    // Large scans are planned on a few threads, a chunk of returns at a time.
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+      for (size_t t; (t = next.fetch_add(1)) < tasks.size();) {
+        PlanTask& task = tasks[t];
+        task.rc = PlanReturns(jobs[task.job], returns, task.i0, task.i1, free_voxels, &task.box);
+      }
+    };
+    const size_t hw = std::max(1u, std::thread::hardware_concurrency());
+    const size_t nthreads =
+        planned >= kPlanThreaded ? std::min<size_t>({tasks.size(), hw, kPlanThreads}) : 1;
+    std::vector<std::thread> pool;
+    try {
+      for (size_t t = 1; t < nthreads; ++t) pool.emplace_back(work);
+    } catch (...) {  // no more threads: the ones there are share the chunks
+    }
+    work();
+    for (std::thread& t : pool) t.join();
+    for (const PlanTask& task : tasks) {
+      if (task.rc != CSM_OK) return task.rc;
+      if (!task.box.empty()) {
+        Box3& box = plan[grid_of_job[task.job]].box;
+        box.Add(task.box.lo[0], task.box.lo[1], task.box.lo[2]);
+        box.Add(task.box.hi[0], task.box.hi[1], task.box.hi[2]);
+      }
+    }
+  }
+  for (int gi = 0; gi < num_grids; ++gi) {
+    GridPlan3& gp = plan[gi];
+    const csm_hybrid_grid* g = grids[gi];
+    gp.after = g->brick;
+    gp.grid_size = g->grid_size;
+    gp.touched = !gp.box.empty();
+    if (!gp.touched) continue;
+    const Brick3& b = g->brick;
+    const bool had = b.nx > 0;
+    const int olo[3] = {b.ox, b.oy, b.oz};
+    const int ohi[3] = {b.ox + b.nx - 1, b.oy + b.ny - 1, b.oz + b.nz - 1};
+    int lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = had ? std::min(olo[a], gp.box.lo[a]) : gp.box.lo[a];
+      hi[a] = had ? std::max(ohi[a], gp.box.hi[a]) : gp.box.hi[a];
+      // DynamicGrid::Grow (hybrid_grid.h:283-296, :384-399).
+      while (gp.box.lo[a] < -(gp.grid_size / 2) || gp.box.hi[a] >= gp.grid_size / 2)
+        gp.grid_size *= 2;
+    }
+    gp.after = Brick3{lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1,
+                      hi[2] - lo[2] + 1, 0};
+    const int64_t n = static_cast<int64_t>(gp.after.nx) * gp.after.ny * gp.after.nz;
+    if (n > (int64_t{1} << 31)) return CSM_ERANGE;
+    // A brick csm_hybrid_grid_create sized to an odd cell count is moved once
+    // so that its last cell has a whole word.
+    gp.grew = !had || gp.after.nx != b.nx || gp.after.ny != b.ny || gp.after.nz != b.nz ||
+              g->values.bytes < ValueBytes(n);
+  }
+
+  // Allocate before anything is enqueued: a failure leaves the grids as they
+  // were.
+  int rc = EnsureTables3(ctx, o);
+  auto give_back = [&] {
+    for (GridPlan3& gp : plan) {
+      if (gp.values.ptr) ctx->pool.Give(&gp.values);
+      if (gp.prob.ptr) ctx->pool.Give(&gp.prob);
+      if (gp.stats.ptr) ctx->pool.Give(&gp.stats);
+    }
+  };
+  for (int gi = 0; gi < num_grids && rc == CSM_OK; ++gi) {
+    GridPlan3& gp = plan[gi];
+    if (!gp.touched) continue;
+    if (!grids[gi]->insert_stats.ptr)
+      rc = ctx->pool.Take(2 * sizeof(unsigned long long), &gp.stats);
+    if (rc != CSM_OK || !gp.grew) continue;
+    const int64_t n = static_cast<int64_t>(gp.after.nx) * gp.after.ny * gp.after.nz;
+    if ((rc = ctx->pool.Take(ValueBytes(n), &gp.values)) == CSM_OK)
+      rc = ctx->pool.Take(sizeof(float) * n, &gp.prob);
+  }
+  // Jobs in round order (stable), then one upload: descriptors and returns.
+  std::vector<int> order;
+  for (int k = 0; k < num_jobs; ++k)
+    if (jobs[k].num_returns > 0) order.push_back(k);
+  std::stable_sort(order.begin(), order.end(),
+                   [&](int a, int b) { return round_of[a] < round_of[b]; });
+  const int live = static_cast<int>(order.size());
+  const size_t desc_bytes = (sizeof(Job3) * std::max(live, 1) + 255) & ~size_t(255);
+  const size_t bytes = desc_bytes + sizeof(float) * 3 * total_ret;
+  StageRing::Slot* slot = nullptr;
+  if (rc == CSM_OK && live > 0) rc = ctx->ins3_stage.Take(bytes, &slot);
+  if (rc == CSM_OK && live > 0 && ctx->ins3_dev.bytes < bytes) {
+    // The buffer is replaced: earlier inserts on the stream may still read it.
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CSM_EHIP;
+    else rc = ctx->ins3_dev.Reserve(bytes + bytes / 2);
+  }
+  for (int gi = 0; gi < num_grids && rc == CSM_OK; ++gi) {
+    csm_hybrid_grid* g = grids[gi];
+    if (plan[gi].touched && !g->ready &&
+        hipEventCreateWithFlags(&g->ready, hipEventDisableTiming) != hipSuccess)
+      rc = CSM_EHIP;
+  }
+  if (rc != CSM_OK) {
+    give_back();
+    return rc;
+  }
+  hipStream_t st = ctx->stream;
+  // From here on a failure is a HIP error: the stream's state is unknown.
+  std::deque<DevBuf> retired;
+  for (int gi = 0; gi < num_grids; ++gi) {
+    GridPlan3& gp = plan[gi];
+    csm_hybrid_grid* g = grids[gi];
+    if (!gp.touched) continue;
+    if (gp.stats.ptr) {
+      CSM_HIP(hipMemsetAsync(gp.stats.ptr, 0, 2 * sizeof(unsigned long long), st));
+      MoveBuf(&gp.stats, &g->insert_stats);
+    }
+    if (gp.grew) {
+      const int64_t n = static_cast<int64_t>(gp.after.nx) * gp.after.ny * gp.after.nz;
+      hipLaunchKernelGGL(insert3d_grow, dim3(Blocks(n, 1024, 8192)), dim3(256), 0, st,
+                         g->values.as<uint16_t>(), g->prob.as<float>(), g->brick,
+                         gp.values.as<uint16_t>(), gp.prob.as<float>(), gp.after, kMinP);
+      CSM_HIP(hipGetLastError());
+      retired.emplace_back();
+      MoveBuf(&g->values, &retired.back());
+      retired.emplace_back();
+      MoveBuf(&g->prob, &retired.back());
+      MoveBuf(&gp.values, &g->values);
+      MoveBuf(&gp.prob, &g->prob);
+    }
+    g->brick = gp.after;
+    g->grid_size = gp.grid_size;
+    ++g->generation;
+  }
+  if (live > 0) {
+    Job3* hd = slot->buf.as<Job3>();
+    for (int i = 0; i < live; ++i) {
+      Job3& j = jobs[order[i]];
+      csm_hybrid_grid* g = grids[grid_of_job[order[i]]];
+      j.words = g->values.as<uint32_t>();
+      j.prob = g->prob.as<float>();
+      j.stats = g->insert_stats.as<unsigned long long>();
+      j.b = g->brick;
+      hd[i] = j;
+    }
+    if (total_ret)
+      std::memcpy(slot->buf.as<char>() + desc_bytes, returns, sizeof(float) * 3 * total_ret);
+    CSM_HIP(hipMemcpyAsync(ctx->ins3_dev.ptr, slot->buf.ptr, bytes, hipMemcpyHostToDevice, st));
+    CSM_HIP(hipEventRecord(slot->copied, st));
+    const Job3* dd = ctx->ins3_dev.as<Job3>();
+    const float* dpts = reinterpret_cast<const float*>(ctx->ins3_dev.as<char>() + desc_bytes);
+    const uint16_t* tabs = ctx->ins3_tabs.as<uint16_t>();
+    const float* ptab = ctx->ins3_ptab.as<float>();
+    // Lanes per ray: the power of two at or above the span length, at most a
+    // wave.
+    int group_bits = 0;
+    while (group_bits < 6 && (1 << group_bits) < free_voxels) ++group_bits;
+    const int rays_per_block = 256 >> group_bits;
+    int i0 = 0;
+    for (int r = 0; r < num_rounds && i0 < live; ++r) {
+      int i1 = i0;
+      int64_t max_returns = 1;
+      for (; i1 < live && round_of[order[i1]] == r; ++i1)
+        max_returns = std::max<int64_t>(max_returns, jobs[order[i1]].num_returns);
+      const unsigned ny = static_cast<unsigned>(i1 - i0);
+      for (unsigned y0 = 0; y0 < ny; y0 += 65535) {  // gridDim.y
+        const unsigned nyy = std::min(65535u, ny - y0);
+        const dim3 ray_blocks(Blocks(max_returns, rays_per_block, 4096), nyy);
+        hipLaunchKernelGGL(insert3d_hits, dim3(Blocks(max_returns, 256, 1024), nyy), dim3(256), 0,
+                           st, dd + i0 + y0, dpts, tabs);
+        CSM_HIP(hipGetLastError());
+        if (free_voxels > 0) {
+          hipLaunchKernelGGL(insert3d_rays<false>, ray_blocks, dim3(256), 0, st, dd + i0 + y0,
+                             dpts, tabs, ptab, free_voxels, group_bits);
+          CSM_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(insert3d_rays<true>, ray_blocks, dim3(256), 0, st, dd + i0 + y0, dpts,
+                           tabs, ptab, free_voxels, group_bits);
+        CSM_HIP(hipGetLastError());
+      }
+      i0 = i1;
+    }
+  }
+  // Consumers on other streams wait for the last insert.
+  for (int gi = 0; gi < num_grids; ++gi)
+    if (plan[gi].touched) CSM_HIP(hipEventRecord(grids[gi]->ready, st));
+  // The old bricks of grown grids: reused by later takes on this stream.
+  for (DevBuf& b : retired)
+    if (b.ptr) ctx->pool.Give(&b);
+  return CSM_OK;
+}
+
+}  // namespace
+}  // namespace csm
+
+using namespace csm;
+
+extern "C" {
+
+int csm_inserter3d_lookup_table(float probability, uint16_t* out) {
+  if (!out || !(probability > 0.f && probability < 1.f)) return CSM_EINVAL;
+  LookupTable3(Odds(probability), out);
+  return CSM_OK;
+}
+
+int csm_rotate_histogram(const float* histogram, int32_t size, float angle, float* out) {
+  if (size < 0 || (size > 0 && (!histogram || !out)) || !std::isfinite(angle)) return CSM_EINVAL;
+  if (size == 0) return CSM_OK;
+  const float rotate_by_buckets =
+      static_cast<float>(static_cast<double>(-angle * static_cast<float>(size)) / M_PI);
+  if (!(std::fabs(rotate_by_buckets) < 1.0e9f)) return CSM_ERANGE;
+  int full_buckets = static_cast<int>(std::lround(rotate_by_buckets - 0.5f));
+  const float fraction = rotate_by_buckets - static_cast<float>(full_buckets);
+  full_buckets %= size;  // `while (full_buckets < 0) full_buckets += size`, then % size below
+  if (full_buckets < 0) full_buckets += size;
+  std::vector<float> in(histogram, histogram + size);  // out may alias histogram
+  for (int i = 0; i != size; ++i) {
+    const float r0 = in[(i + full_buckets) % size];
+    const float r1 = in[(i + 1 + full_buckets) % size];
+    out[i] = fraction * r1 + (1.f - fraction) * r0;
+  }
+  return CSM_OK;
+}
+
+int csm_hybrid_grid_insert_batch(csm_context* ctx, csm_hybrid_grid* const* grids,
+                                 int32_t num_grids, const csm_inserter3d_options* options,
+                                 int32_t num_scans, const float* origins_xyz,
+                                 const float* returns_xyz, const int64_t* return_offsets,
+                                 int32_t num_jobs, const int32_t* grid_of_job,
+                                 const int32_t* scan_of_job, const float* transforms,
+                                 int32_t num_transforms, const int32_t* transform_of_job,
+                                 const float* max_ranges) {
+  return InsertBatch3(ctx, grids, num_grids, options, num_scans, origins_xyz, returns_xyz,
+                      return_offsets, num_jobs, grid_of_job, scan_of_job, transforms,
+                      num_transforms, transform_of_job, max_ranges, false);
+}
+
+int csm_hybrid_grid_insert(csm_hybrid_grid* g, const csm_inserter3d_options* options,
+                           const float* origin, const float* returns, int32_t n) {
+  if (!g || !options || !origin || n < 0 || (n > 0 && !returns)) return CSM_EINVAL;
+  const int32_t zero = 0;
+  const int64_t off[2] = {0, n};
+  csm_hybrid_grid* const grids[1] = {g};
+  return InsertBatch3(nullptr, grids, 1, options, 1, origin, returns, off, 1, &zero, &zero,
+                      nullptr, 0, nullptr, nullptr, true);
+}
+
+int csm_hybrid_grid_read(const csm_hybrid_grid* g, uint16_t* out, int64_t capacity) {
+  if (!g || capacity < 0) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(g->ctx->mu);
+  const int64_t n = static_cast<int64_t>(g->brick.nx) * g->brick.ny * g->brick.nz;
+  if (capacity < n || (n > 0 && !out)) return CSM_EINVAL;
+  if (hipSetDevice(g->ctx->device) != hipSuccess) return CSM_EHIP;
+  if (n > 0)
+    CSM_HIP(hipMemcpyAsync(out, g->values.ptr, n * sizeof(uint16_t), hipMemcpyDeviceToHost,
+                           g->ctx->stream));
+  CSM_HIP(hipStreamSynchronize(g->ctx->stream));
+  return CSM_OK;
+}
+
+int csm_hybrid_grid_insert_stats(const csm_hybrid_grid* g, int64_t* cells_visited,
+                                 int64_t* cells_updated) {
+  if (!g) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(g->ctx->mu);
+  unsigned long long s[2] = {0, 0};
+  if (g->insert_stats.ptr) {
+    if (hipSetDevice(g->ctx->device) != hipSuccess) return CSM_EHIP;
+    CSM_HIP(hipMemcpyAsync(s, g->insert_stats.ptr, sizeof(s), hipMemcpyDeviceToHost,
+                           g->ctx->stream));
+    CSM_HIP(hipStreamSynchronize(g->ctx->stream));
+  }
+  if (cells_visited) *cells_visited = static_cast<int64_t>(s[0]);
+  if (cells_updated) *cells_updated = static_cast<int64_t>(s[1]);
+  return CSM_OK;
+}
+
+}  // extern "C"

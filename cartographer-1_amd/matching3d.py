@@ -21,8 +21,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import (CSM_OK, Context, Fast3DOptions, Node3D, Pair3D, Pose3D, Result3D, RtOptions,
-               _check, _f32_points, _ptr, default_context)
+from . import (CSM_OK, Context, Fast3DOptions, Inserter3DOptions, Node3D, Pair3D, Pose3D, Result3D,
+               RtOptions, _check, _f32_points, _ptr, default_context, load_library)
 
 
 class HybridGrid:
@@ -101,6 +101,83 @@ class HybridGrid:
                "csm_hybrid_grid_interpolate")
         return out
 
+    def insert(self, origin, returns, hit_probability: float = 0.55,
+               miss_probability: float = 0.49, num_free_space_voxels: int = 2) -> None:
+        """RangeDataInserter3D::Insert on the device (csm_hybrid_grid_insert);
+        origin and returns in the grid's frame."""
+        o = Inserter3DOptions(hit_probability, miss_probability, int(num_free_space_voxels))
+        org = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+        r = np.ascontiguousarray(np.asarray(returns, np.float32).reshape(-1, 3))
+        _check(self._lib.csm_hybrid_grid_insert(self.handle, C.byref(o), _ptr(org, C.c_float),
+                                                _ptr(r, C.c_float), len(r)),
+               "csm_hybrid_grid_insert")
+
+    @staticmethod
+    def insert_batch(grids: Sequence["HybridGrid"], scans, jobs, hit_probability: float = 0.55,
+                     miss_probability: float = 0.49, num_free_space_voxels: int = 2) -> None:
+        """Many inserts in one call (csm_hybrid_grid_insert_batch). ``scans``:
+        (origin, returns) pairs in the local frame, uploaded once. ``jobs``:
+        (grid index, scan index[, transform[, max_range]]) tuples; transform is
+        None or ((tx, ty, tz), (qw, qx, qy, qz)), submap from local; max_range
+        None or <= 0 keeps every return. Jobs on one grid apply in order."""
+        ctx = grids[0].context
+        o = Inserter3DOptions(hit_probability, miss_probability, int(num_free_space_voxels))
+        origins = np.zeros((max(len(scans), 1), 3), np.float32)
+        off = np.zeros(len(scans) + 1, np.int64)
+        rets = []
+        for s, (org, ret) in enumerate(scans):
+            origins[s] = np.asarray(org, np.float32).reshape(3)
+            rets.append(np.asarray(ret, np.float32).reshape(-1, 3))
+            off[s + 1] = off[s] + len(rets[-1])
+        r = np.ascontiguousarray(np.concatenate(rets) if rets else np.zeros((0, 3), np.float32))
+        n = len(jobs)
+        gj = np.zeros(max(n, 1), np.int32)
+        sj = np.zeros(max(n, 1), np.int32)
+        tj = np.full(max(n, 1), -1, np.int32)
+        mr = np.zeros(max(n, 1), np.float32)
+        tfs = []
+        for k, job in enumerate(jobs):
+            gj[k], sj[k] = int(job[0]), int(job[1])
+            if len(job) > 2 and job[2] is not None:
+                t, q = job[2]
+                tj[k] = len(tfs)
+                tfs.append([float(v) for v in t] + [float(v) for v in q])
+            if len(job) > 3 and job[3] is not None:
+                mr[k] = job[3]
+        tf = np.ascontiguousarray(np.asarray(tfs, np.float32).reshape(-1, 7))
+        handles = (C.c_void_p * len(grids))(*[g.handle for g in grids])
+        _check(ctx._lib.csm_hybrid_grid_insert_batch(
+            ctx.handle, handles, len(grids), C.byref(o), len(scans), _ptr(origins, C.c_float),
+            _ptr(r, C.c_float), _ptr(off, C.c_int64), n, _ptr(gj, C.c_int32), _ptr(sj, C.c_int32),
+            _ptr(tf, C.c_float) if len(tf) else None, len(tf), _ptr(tj, C.c_int32),
+            _ptr(mr, C.c_float)), "csm_hybrid_grid_insert_batch")
+
+    def values(self) -> np.ndarray:
+        """The uint16 brick, indexed [z, y, x], over the box :meth:`info`
+        reports (csm_hybrid_grid_read); waits for the device."""
+        _, d, _ = self.info()
+        out = np.zeros((d[2], d[1], d[0]), np.uint16)
+        _check(self._lib.csm_hybrid_grid_read(self.handle, _ptr(out, C.c_uint16), out.size),
+               "csm_hybrid_grid_read")
+        return out
+
+    def cells(self):
+        """(indices (n, 3), values (n,)) of the known cells, as the reference's
+        iterator yields them up to order: what the constructor takes."""
+        o, _, _ = self.info()
+        v = self.values()
+        z, y, x = np.nonzero(v)
+        idx = np.stack([x + o[0], y + o[1], z + o[2]], 1).astype(np.int32)
+        return idx, v[z, y, x]
+
+    def insert_stats(self):
+        """(cells visited, cells updated) by the FinishUpdate pass over all
+        inserts so far (csm_hybrid_grid_insert_stats, test-visible)."""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self._lib.csm_hybrid_grid_insert_stats(self.handle, C.byref(a), C.byref(b)),
+               "csm_hybrid_grid_insert_stats")
+        return a.value, b.value
+
     def close(self):
         if getattr(self, "handle", None):
             self._lib.csm_hybrid_grid_destroy(self.handle)
@@ -111,6 +188,23 @@ class HybridGrid:
             self.close()
         except Exception:
             pass
+
+
+def inserter3d_lookup_table(probability: float) -> np.ndarray:
+    """ComputeLookupTableToApplyOdds(Odds(probability)), marker included."""
+    out = np.zeros(32768, np.uint16)
+    _check(load_library().csm_inserter3d_lookup_table(probability, _ptr(out, C.c_uint16)),
+           "csm_inserter3d_lookup_table")
+    return out
+
+
+def rotate_histogram(histogram, angle: float) -> np.ndarray:
+    """RotationalScanMatcher::RotateHistogram (rotational_scan_matcher.cc:138-158)."""
+    h = np.ascontiguousarray(np.asarray(histogram, np.float32).reshape(-1))
+    out = np.zeros_like(h)
+    _check(load_library().csm_rotate_histogram(_ptr(h, C.c_float), len(h), float(np.float32(angle)),
+                                               _ptr(out, C.c_float)), "csm_rotate_histogram")
+    return out
 
 
 def _pose(p) -> Pose3D:

@@ -1,0 +1,191 @@
+"""Submap3D, ActiveSubmaps3D and RangeDataInserter3D on device-resident
+HybridGrids (reference mapping/3d/submap_3d.{h,cc},
+range_data_inserter_3d.{h,cc}): the Python mirror of
+include/cartographer_amd/submap_3d.h. The intensity grid
+(IntensityHybridGrid, range_data_inserter_3d.cc:76-89) is not kept: no matcher
+here reads it."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import Context, default_context
+from .matching3d import HybridGrid, rotate_histogram
+from .submap_2d import RangeData
+
+
+@dataclass
+class RangeDataInserterOptions3D:
+    """proto::RangeDataInserterOptions3D; defaults from
+    configuration_files/trajectory_builder_3d.lua:97-104."""
+    hit_probability: float = 0.55
+    miss_probability: float = 0.49
+    num_free_space_voxels: int = 2
+
+
+@dataclass
+class SubmapsOptions3D:
+    """proto::SubmapsOptions3D; defaults from trajectory_builder_3d.lua:92-104."""
+    high_resolution: float = 0.10
+    high_resolution_max_range: float = 20.0
+    low_resolution: float = 0.45
+    num_range_data: int = 160
+    range_data_inserter_options: Optional[RangeDataInserterOptions3D] = None
+
+
+# Rigid3d pieces in double, with Eigen's operation order.
+def _rotate(q, v):
+    """Quaternion::_transformVector: uv = 2 q.vec x v; v + w uv + q.vec x uv."""
+    w, x, y, z = q
+    ux = 2.0 * (y * v[2] - z * v[1])
+    uy = 2.0 * (z * v[0] - x * v[2])
+    uz = 2.0 * (x * v[1] - y * v[0])
+    return (v[0] + w * ux + (y * uz - z * uy),
+            v[1] + w * uy + (z * ux - x * uz),
+            v[2] + w * uz + (x * uy - y * ux))
+
+
+def _quat_mul(a, b):
+    return (a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
+            a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+            a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3],
+            a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1])
+
+
+def _inverse(t, q):
+    """Rigid3d::inverse (rigid_transform.h:159-163)."""
+    c = (q[0], -q[1], -q[2], -q[3])
+    r = _rotate(c, t)
+    return (-r[0], -r[1], -r[2]), c
+
+
+class RangeDataInserter3D:
+    """range_data_inserter_3d.h:35-51, on device grids."""
+
+    def __init__(self, options: Optional[RangeDataInserterOptions3D] = None):
+        self.options = options or RangeDataInserterOptions3D()
+
+    def _args(self):
+        o = self.options
+        return o.hit_probability, o.miss_probability, o.num_free_space_voxels
+
+    def Insert(self, range_data: RangeData, grid: HybridGrid) -> None:
+        grid.insert(range_data.origin, range_data.returns, *self._args())
+
+    def InsertBatch(self, grids: Sequence[HybridGrid], scans, jobs) -> None:
+        """HybridGrid.insert_batch with this inserter's options."""
+        HybridGrid.insert_batch(grids, scans, jobs, *self._args())
+
+
+class Submap3D:
+    """submap_3d.h:43-104: the high and low resolution grids, the local pose
+    and the accumulated rotational scan matcher histogram."""
+
+    def __init__(self, high_resolution: float, low_resolution: float, local_pose,
+                 histogram_size: int, context: Optional[Context] = None):
+        t, q = local_pose
+        self._local_pose = (tuple(float(v) for v in t), tuple(float(v) for v in q))
+        ctx = context or default_context()
+        empty = np.zeros((0, 3), np.int32), np.zeros(0, np.uint16)
+        self._high = HybridGrid(high_resolution, *empty, context=ctx)
+        self._low = HybridGrid(low_resolution, *empty, context=ctx)
+        self._histogram = np.zeros(histogram_size, np.float32)
+        self._num_range_data = 0
+        self._insertion_finished = False
+
+    def local_pose(self):
+        return self._local_pose
+
+    def high_resolution_hybrid_grid(self) -> HybridGrid:
+        return self._high
+
+    def low_resolution_hybrid_grid(self) -> HybridGrid:
+        return self._low
+
+    def rotational_scan_matcher_histogram(self) -> np.ndarray:
+        return self._histogram
+
+    def num_range_data(self) -> int:
+        return self._num_range_data
+
+    def insertion_finished(self) -> bool:
+        return self._insertion_finished
+
+    def _submap_from_local(self):
+        """local_pose().inverse().cast<float>() (submap_3d.cc:330-331)."""
+        t, q = _inverse(*self._local_pose)
+        return ([float(np.float32(v)) for v in t], [float(np.float32(v)) for v in q])
+
+    def _jobs(self, first_grid: int, scan: int, high_resolution_max_range: float):
+        """The two batch jobs of InsertData (submap_3d.cc:329-339)."""
+        tf = self._submap_from_local()
+        return [(first_grid, scan, tf, high_resolution_max_range), (first_grid + 1, scan, tf, None)]
+
+    def _after_insert(self, local_from_gravity_aligned, scan_histogram_in_gravity) -> None:
+        """submap_3d.cc:340-346."""
+        self._num_range_data += 1
+        c = _inverse(*self._local_pose)[1]
+        d = _rotate(_quat_mul(c, tuple(float(v) for v in local_from_gravity_aligned)),
+                    (1.0, 0.0, 0.0))
+        yaw = float(np.float32(math.atan2(d[1], d[0])))
+        self._histogram = self._histogram + rotate_histogram(scan_histogram_in_gravity, yaw)
+
+    def InsertData(self, range_data_in_local: RangeData, inserter: RangeDataInserter3D,
+                   high_resolution_max_range: float, local_from_gravity_aligned,
+                   scan_histogram_in_gravity) -> None:
+        assert not self._insertion_finished  # submap_3d.cc:328
+        inserter.InsertBatch([self._high, self._low],
+                             [(range_data_in_local.origin, range_data_in_local.returns)],
+                             self._jobs(0, 0, high_resolution_max_range))
+        self._after_insert(local_from_gravity_aligned, scan_histogram_in_gravity)
+
+    def Finish(self) -> None:
+        assert not self._insertion_finished  # submap_3d.cc:350
+        self._insertion_finished = True
+
+
+class ActiveSubmaps3D:
+    """submap_3d.h:119-152, .cc:354-416: at most two submaps; a new one at the
+    scan's origin, rotated by local_from_gravity_aligned, when the newest holds
+    num_range_data scans; every scan goes into all active grids in one batch
+    call; the oldest is finished at 2 * num_range_data."""
+
+    def __init__(self, options: Optional[SubmapsOptions3D] = None,
+                 context: Optional[Context] = None):
+        self.options = options or SubmapsOptions3D()
+        self.range_data_inserter = RangeDataInserter3D(self.options.range_data_inserter_options)
+        self.context = context or default_context()
+        self._submaps: List[Submap3D] = []
+
+    def submaps(self) -> List[Submap3D]:
+        return list(self._submaps)
+
+    def AddSubmap(self, local_submap_pose, histogram_size: int) -> None:
+        if len(self._submaps) >= 2:
+            assert self._submaps[0].insertion_finished()  # :397
+            self._submaps.pop(0)
+        o = self.options
+        self._submaps.append(Submap3D(o.high_resolution, o.low_resolution, local_submap_pose,
+                                      histogram_size, self.context))
+
+    def InsertData(self, range_data: RangeData, local_from_gravity_aligned,
+                   rotational_scan_matcher_histogram_in_gravity) -> List[Submap3D]:
+        o = self.options
+        hist = np.asarray(rotational_scan_matcher_histogram_in_gravity, np.float32)
+        if not self._submaps or self._submaps[-1].num_range_data() == o.num_range_data:
+            origin = np.asarray(range_data.origin, np.float32)
+            self.AddSubmap(([float(v) for v in origin], local_from_gravity_aligned), len(hist))
+        grids, jobs = [], []
+        for s in self._submaps:
+            assert not s.insertion_finished()
+            jobs += s._jobs(len(grids), 0, o.high_resolution_max_range)
+            grids += [s.high_resolution_hybrid_grid(), s.low_resolution_hybrid_grid()]
+        self.range_data_inserter.InsertBatch(grids, [(range_data.origin, range_data.returns)], jobs)
+        for s in self._submaps:
+            s._after_insert(local_from_gravity_aligned, hist)
+        if self._submaps[0].num_range_data() == 2 * o.num_range_data:
+            self._submaps[0].Finish()
+        return self.submaps()

@@ -679,6 +679,100 @@ int csm_ray_to_pixel_mask(csm_context* ctx, const int32_t* begin_end_xyxy, int32
  * Host-only. */
 int csm_inserter2d_lookup_table(float probability, uint16_t* out /* [32768] */);
 
+/* ---- device-resident HybridGrid: 3D range-data insertion --------------------
+ * RangeDataInserter3D::Insert (mapping/3d/range_data_inserter_3d.cc:44-74,
+ * :109-137) on the device brick of a csm_hybrid_grid, bit for bit: a grid
+ * made by csm_hybrid_grid_create (an empty one, count 0, included) is updated
+ * where it lives, and csm_rt3d_match, csm_hybrid_grid_get_probability,
+ * csm_hybrid_grid_interpolate, csm_ceres3d_refine_batch and later
+ * csm_fast3d_create calls see the new values without a host copy. Every call
+ * is enqueued on the grid's context's stream under that context's lock and
+ * re-records the grid's ready event; only csm_hybrid_grid_read and
+ * csm_hybrid_grid_insert_stats wait for the device.
+ *
+ * After every insert csm_hybrid_grid_info reports exactly the bounding box of
+ * the known cells and DynamicGrid's size (hybrid_grid.h:283-296, :384-399):
+ * what csm_hybrid_grid_create would derive from the reference grid's iterator
+ * list. A grid whose box grows is moved into a new brick on the device.
+ *
+ * One limit, as in the reference, where matchers are built from finished
+ * submaps only (constraint_builder_3d.cc:170-198): inserting into a grid that
+ * a live csm_fast3d was built from, or holds as its low-resolution grid, is
+ * not supported. Calls that read a grid from another context's stream must
+ * not overlap an insert into it. The intensity grid (IntensityHybridGrid,
+ * range_data_inserter_3d.cc:76-89) is not kept: no matcher here reads it. */
+
+/* proto::RangeDataInserterOptions3D
+ * (mapping/proto/range_data_inserter_options_3d.proto), without the intensity
+ * threshold. */
+typedef struct csm_inserter3d_options {
+  float hit_probability, miss_probability;
+  int32_t num_free_space_voxels;
+} csm_inserter3d_options;
+
+/* RangeDataInserter3D::Insert(range_data, hybrid_grid)
+ * (range_data_inserter_3d.cc:109-137): every return's cell (GetCellIndex,
+ * hybrid_grid.h:428-433) takes hit_table[old]; then, per ray, the last
+ * num_free_space_voxels cells origin_cell + delta * position / num_samples
+ * before the hit (InsertMissesIntoGrid, :44-74) take miss_table[old] unless
+ * already updated in this call (ApplyLookupTable's update marker,
+ * hybrid_grid.h:497-513); FinishUpdate (:515-521). Points are in the grid's
+ * frame. CSM_EINVAL: a non-finite coordinate, a probability outside (0, 1), a
+ * negative num_free_space_voxels. CSM_ERANGE: a ray of 2^15 cells or more
+ * (the reference's CHECK_LT, :58) or a brick past 2^31 cells. Either leaves
+ * the grid as it was and enqueues nothing. */
+int csm_hybrid_grid_insert(csm_hybrid_grid* grid, const csm_inserter3d_options* options,
+                           const float origin_xyz[3], const float* returns_xyz,
+                           int32_t num_returns);
+
+/* Many Inserts in one call: Submap3D::InsertData (submap_3d.cc:323-347) for
+ * the two active submaps, four grids, is one call. The scans go up once, in
+ * the local frame: scan s has origin origins_xyz[3s..] and returns
+ * [return_offsets[s], return_offsets[s+1]) of returns_xyz. Job k inserts scan
+ * scan_of_job[k] into grids[grid_of_job[k]], after
+ *  - transform_of_job[k] >= 0: sensor::TransformRangeData by the Rigid3f
+ *    transforms[7 t..] (translation, then rotation w, x, y, z; submap from
+ *    local), applied to the origin and every return as Rigid3f * Vector3f
+ *    (rigid_transform.h:191-196). transform_of_job NULL: no job has one.
+ *  - max_ranges[k] > 0: FilterRangeDataByMaxRange (submap_3d.cc:91-99), which
+ *    keeps a return when (p - origin).norm() <= max_range in float, after the
+ *    transform. max_ranges NULL: no job filters.
+ * Jobs on one grid are applied in array order; jobs on different grids run
+ * concurrently. All grids belong to ctx and are distinct. Errors as for
+ * csm_hybrid_grid_insert, for the whole call. */
+int csm_hybrid_grid_insert_batch(csm_context* ctx, csm_hybrid_grid* const* grids,
+                                 int32_t num_grids, const csm_inserter3d_options* options,
+                                 int32_t num_scans, const float* origins_xyz,
+                                 const float* returns_xyz, const int64_t* return_offsets,
+                                 int32_t num_jobs, const int32_t* grid_of_job,
+                                 const int32_t* scan_of_job, const float* transforms,
+                                 int32_t num_transforms, const int32_t* transform_of_job,
+                                 const float* max_ranges);
+
+/* The uint16 values of the device brick (x fastest) over the box
+ * csm_hybrid_grid_info reports, capacity >= nx * ny * nz values: with the box
+ * origin, what HybridGrid's iterator / ToProto yields (hybrid_grid.h:530-541;
+ * unknown cells are 0). Waits for the stream. */
+int csm_hybrid_grid_read(const csm_hybrid_grid* grid, uint16_t* values_out, int64_t capacity);
+
+/* Test-visible, like csm_fast3d_read_level: totals over the grid's inserts of
+ * the cells the FinishUpdate pass looked at (one per return and per miss
+ * position, duplicates included) and of the cells it updated. The pass walks
+ * the returns again, never the brick. Waits for the stream. */
+int csm_hybrid_grid_insert_stats(const csm_hybrid_grid* grid, int64_t* cells_visited,
+                                 int64_t* cells_updated);
+
+/* ComputeLookupTableToApplyOdds(Odds(probability))
+ * (probability_values.cc:76-87): 32768 entries, update marker included.
+ * Host-only. */
+int csm_inserter3d_lookup_table(float probability, uint16_t* out /* [32768] */);
+
+/* RotationalScanMatcher::RotateHistogram(histogram, angle)
+ * (rotational_scan_matcher.cc:138-158), which Submap3D::InsertData adds to
+ * the submap's histogram (submap_3d.cc:341-346). out may be histogram.
+ * Host-only. */
+int csm_rotate_histogram(const float* histogram, int32_t size, float angle, float* out);
+
 /* ---- node clouds: voxel filters -------------------------------------------
  * sensor::VoxelFilter and sensor::AdaptiveVoxelFilter
  * (sensor/internal/voxel_filter.h, voxel_filter.cc:212-232 and :263-268), the
