@@ -73,6 +73,30 @@ class Inserter2DOptions(C.Structure):
                 ("insert_free_space", C.c_int32)]
 
 
+class TSDFInserterOptions(C.Structure):
+    """csm_tsdf_inserter_options (TSDFRangeDataInserterOptions2D, proto order)."""
+    _fields_ = [("truncation_distance", C.c_double), ("maximum_weight", C.c_double),
+                ("update_free_space", C.c_int32), ("num_normal_samples", C.c_int32),
+                ("sample_radius", C.c_double),
+                ("project_sdf_distance_to_scan_normal", C.c_int32),
+                ("update_weight_range_exponent", C.c_int32),
+                ("update_weight_angle_scan_normal_to_ray_kernel_bandwidth", C.c_double),
+                ("update_weight_distance_cell_to_hit_kernel_bandwidth", C.c_double)]
+
+    @staticmethod
+    def make(options=None) -> "TSDFInserterOptions":
+        """From a TSDFInserterOptions, a 9-sequence in proto order, or None for
+        the reference's test defaults (0.3, 10, no free space, 4 samples of
+        radius 0.5, projection, exponent 0, both bandwidths 0.5)."""
+        if isinstance(options, TSDFInserterOptions):
+            return options
+        v = (0.3, 10.0, 0, 4, 0.5, 1, 0, 0.5, 0.5) if options is None else tuple(options)
+        if len(v) != 9:
+            raise ValueError("TSDF inserter options: 9 values in proto order")
+        return TSDFInserterOptions(float(v[0]), float(v[1]), int(v[2]), int(v[3]), float(v[4]),
+                                   int(v[5]), int(v[6]), float(v[7]), float(v[8]))
+
+
 class Inserter3DOptions(C.Structure):
     """csm_inserter3d_options (RangeDataInserterOptions3D)."""
     _fields_ = [("hit_probability", C.c_float), ("miss_probability", C.c_float),
@@ -369,6 +393,29 @@ _SIGNATURES = {
     "csm_ray_to_pixel_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                         C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "csm_inserter2d_lookup_table": (C.c_int, [C.c_float, C.POINTER(C.c_uint16)]),
+    "csm_tsdf_grid_create": (C.c_int, [C.c_void_p, C.POINTER(MapLimits), C.c_float, C.c_float,
+                                       C.POINTER(C.c_uint16), C.POINTER(C.c_uint16),
+                                       C.POINTER(C.c_void_p)]),
+    "csm_tsdf_grid_destroy": (None, [C.c_void_p]),
+    "csm_tsdf_grid_limits": (C.c_int, [C.c_void_p, C.POINTER(MapLimits)]),
+    "csm_tsdf_grid_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16),
+                                     C.c_int64]),
+    "csm_tsdf_grid_insert": (C.c_int, [C.c_void_p, C.POINTER(TSDFInserterOptions),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32]),
+    "csm_tsdf_grid_insert_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
+                                             C.POINTER(TSDFInserterOptions), C.c_int32,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "csm_tsdf_grid_finish": (C.c_int, [C.c_void_p]),
+    "csm_rt2d_match_tsdf_grid": (C.c_int, [C.c_void_p, C.POINTER(RtOptions), C.c_void_p,
+                                           C.POINTER(Pose2D), C.POINTER(C.c_float), C.c_int32,
+                                           C.POINTER(C.c_double), C.POINTER(Pose2D)]),
+    "csm_tsdf_plan_scan": (C.c_int, [C.POINTER(TSDFInserterOptions), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_uint8)]),
+    "csm_tsdf_round_trip_tables": (C.c_int, [C.c_float, C.c_float, C.POINTER(C.c_uint16),
+                                             C.POINTER(C.c_uint16)]),
     "csm_hybrid_grid_insert": (C.c_int, [C.c_void_p, C.POINTER(Inserter3DOptions),
                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32]),
     "csm_hybrid_grid_insert_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
@@ -840,6 +887,129 @@ class DeviceProbabilityGrid:
         return ProbabilityGrid(lim.resolution, lim.max_x, lim.max_y, cells)
 
 
+class DeviceTSDF2D:
+    """A TSDF2D that lives on the device (csm_tsdf_grid): built there by the
+    reference's TSDFRangeDataInserter2D bit for bit, grown and cropped there,
+    and read by the real-time matcher without a host copy."""
+
+    def __init__(self, resolution: float, max_x: float, max_y: float, num_x_cells: int,
+                 num_y_cells: int, truncation_distance: float, max_weight: float,
+                 tsd_cells: Optional[np.ndarray] = None,
+                 weight_cells: Optional[np.ndarray] = None, context: Optional[Context] = None):
+        self.context = context or default_context()
+        self._lib = self.context._lib
+        lim = MapLimits(resolution, max_x, max_y, num_x_cells, num_y_cells)
+        if (tsd_cells is None) != (weight_cells is None):
+            raise ValueError("tsd_cells and weight_cells: both or neither")
+        t = w = None
+        if tsd_cells is not None:
+            t = np.ascontiguousarray(tsd_cells, np.uint16)
+            w = np.ascontiguousarray(weight_cells, np.uint16)
+            if t.size != num_x_cells * num_y_cells or w.size != t.size:
+                raise ValueError("cells must hold num_x_cells * num_y_cells values")
+        h = C.c_void_p()
+        _check(self._lib.csm_tsdf_grid_create(
+            self.context.handle, C.byref(lim), truncation_distance, max_weight,
+            _ptr(t, C.c_uint16) if t is not None else None,
+            _ptr(w, C.c_uint16) if w is not None else None, C.byref(h)), "csm_tsdf_grid_create")
+        self.handle = h
+        self.truncation_distance = float(np.float32(truncation_distance))
+        self.max_weight = float(np.float32(max_weight))
+
+    @staticmethod
+    def from_host(grid: TSDF2D, context: Optional[Context] = None):
+        return DeviceTSDF2D(grid.resolution, grid.max_x, grid.max_y, grid.num_x_cells,
+                            grid.num_y_cells, grid.truncation_distance, grid.max_weight,
+                            grid.tsd_cells, grid.weight_cells, context)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.csm_tsdf_grid_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def limits(self) -> MapLimits:
+        lim = MapLimits()
+        _check(self._lib.csm_tsdf_grid_limits(self.handle, C.byref(lim)), "csm_tsdf_grid_limits")
+        return lim
+
+    def insert(self, origin, returns, options=None) -> None:
+        """TSDFRangeDataInserter2D::Insert of one scan (points in the grid's
+        frame; the reference ignores misses). ``options``: see
+        TSDFInserterOptions.make."""
+        origins, r, _, _, _ = _pack_scans([(origin, returns)])
+        o = TSDFInserterOptions.make(options)
+        _check(self._lib.csm_tsdf_grid_insert(
+            self.handle, C.byref(o), _ptr(origins, C.c_float), _ptr(r, C.c_float), len(r)),
+            "csm_tsdf_grid_insert")
+
+    @staticmethod
+    def insert_batch(grids: Sequence["DeviceTSDF2D"], grid_of_scan, scans, options=None) -> None:
+        """Many inserts in one call: scan i = (origin, returns) goes into
+        grids[grid_of_scan[i]]; scans of one grid in list order, grids
+        concurrently. All grids share one context."""
+        if not grids:
+            return
+        ctx = grids[0].context
+        origins, r, ro, _, _ = _pack_scans([(s[0], s[1]) for s in scans])
+        gos = np.ascontiguousarray(grid_of_scan, np.int32)
+        if len(gos) != len(scans):
+            raise ValueError("grid_of_scan and scans differ in length")
+        handles = (C.c_void_p * len(grids))(*[g.handle for g in grids])
+        o = TSDFInserterOptions.make(options)
+        _check(ctx._lib.csm_tsdf_grid_insert_batch(
+            ctx.handle, handles, len(grids), C.byref(o), len(scans), _ptr(gos, C.c_int32),
+            _ptr(origins, C.c_float), _ptr(r, C.c_float), _ptr(ro, C.c_int64)),
+            "csm_tsdf_grid_insert_batch")
+
+    def finish(self) -> None:
+        """Submap2D::Finish: crops in place; later inserts fail."""
+        _check(self._lib.csm_tsdf_grid_finish(self.handle), "csm_tsdf_grid_finish")
+
+    def to_host(self) -> TSDF2D:
+        lim = self.limits()
+        tsd = np.zeros((lim.num_y_cells, lim.num_x_cells), np.uint16)
+        wgt = np.zeros_like(tsd)
+        _check(self._lib.csm_tsdf_grid_read(self.handle, _ptr(tsd, C.c_uint16),
+                                            _ptr(wgt, C.c_uint16), tsd.size), "csm_tsdf_grid_read")
+        return TSDF2D(lim.resolution, lim.max_x, lim.max_y, tsd, wgt, self.truncation_distance,
+                      self.max_weight)
+
+
+def tsdf_plan_scan(origin, returns, options=None):
+    """csm_tsdf_plan_scan (visible for testing): (order int32, normals float32,
+    ray_weight float32, cast bool) of one Insert's rays, in cast order."""
+    o = TSDFInserterOptions.make(options)
+    org = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+    r = _f32_points(returns) if len(returns) else np.zeros((0, 3), np.float32)
+    n = len(r)
+    order = np.zeros(max(n, 1), np.int32)
+    normals = np.zeros(max(n, 1), np.float32)
+    weight = np.zeros(max(n, 1), np.float32)
+    cast = np.zeros(max(n, 1), np.uint8)
+    _check(load_library().csm_tsdf_plan_scan(
+        C.byref(o), _ptr(org, C.c_float), _ptr(r, C.c_float), n, _ptr(order, C.c_int32),
+        _ptr(normals, C.c_float), _ptr(weight, C.c_float), _ptr(cast, C.c_uint8)),
+        "csm_tsdf_plan_scan")
+    return order[:n], normals[:n], weight[:n], cast[:n].astype(bool)
+
+
+def tsdf_round_trip_tables(truncation_distance: float, max_weight: float):
+    """(TSDToValue(ValueToTSD(v)), WeightToValue(ValueToWeight(v))) for v in
+    0..32767: the tables DeviceTSDF2D.finish copies through."""
+    t = np.zeros(32768, np.uint16)
+    w = np.zeros(32768, np.uint16)
+    _check(load_library().csm_tsdf_round_trip_tables(
+        truncation_distance, max_weight, _ptr(t, C.c_uint16), _ptr(w, C.c_uint16)),
+        "csm_tsdf_round_trip_tables")
+    return t, w
+
+
 def inserter2d_lookup_table(probability: float) -> np.ndarray:
     """ComputeLookupTableToApplyCorrespondenceCostOdds(Odds(probability))."""
     out = np.zeros(32768, np.uint16)
@@ -982,6 +1152,12 @@ class RealTimeCorrelativeScanMatcher2D:
                 self.context.handle, C.byref(opts), grid.handle, C.byref(init),
                 _ptr(pts, C.c_float), len(pts), C.byref(score), C.byref(pose)),
                 "csm_rt2d_match_grid")
+            return float(score.value), pose.as_tuple()
+        if isinstance(grid, DeviceTSDF2D):
+            _check(self._lib.csm_rt2d_match_tsdf_grid(
+                self.context.handle, C.byref(opts), grid.handle, C.byref(init),
+                _ptr(pts, C.c_float), len(pts), C.byref(score), C.byref(pose)),
+                "csm_rt2d_match_tsdf_grid")
             return float(score.value), pose.as_tuple()
         if isinstance(grid, TSDF2D):
             tsd = np.ascontiguousarray(grid.tsd_cells, dtype=np.uint16)
@@ -1552,6 +1728,7 @@ def synchronize(context: "Context"):
 
 
 from .submap_2d import (ActiveSubmaps2D, ProbabilityGridRangeDataInserter2D,  # noqa: E402,F401
-                        ProbabilityGridRangeDataInserterOptions2D, RangeData, Submap2D)
+                        ProbabilityGridRangeDataInserterOptions2D, RangeData, Submap2D,
+                        TSDFRangeDataInserter2D, TSDFRangeDataInserterOptions2D)
 from .submap_3d import (ActiveSubmaps3D, RangeDataInserter3D,  # noqa: E402,F401
                         RangeDataInserterOptions3D, Submap3D, SubmapsOptions3D)

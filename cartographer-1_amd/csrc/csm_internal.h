@@ -178,6 +178,14 @@ struct Rt2dCache {
   PinnedBuf stage, stage_cells, host_key, wg_keys;  // wg_keys: per-workgroup keys (zero-copy path)
 };
 
+// TSDValueConverter (tsd_value_converter.{h,cc}) of one (truncation, max
+// weight) pair on the device: value -> TSD and value -> weight (32768 floats
+// each, TSD first), and the round trips TSDToValue(ValueToTSD(v)) and
+// WeightToValue(ValueToWeight(v)) Finish copies through (32768 uint16 each).
+struct TsdfTables {
+  DevBuf to_float, round_trip;
+};
+
 }  // namespace csm
 
 struct csm_scan_set {
@@ -315,6 +323,12 @@ struct csm_context {
   csm::DevBuf ins3_tabs, ins3_ptab, ins3_dev;
   float ins3_tab_key[2] = {-1.f, -1.f};
   csm::StageRing ins3_stage;
+  // TSDF range-data insertion (insert_tsdf2d.hip): per (truncation, max
+  // weight) the converter's tables on the device, a batch's scan descriptors
+  // and ray plans with their pinned staging.
+  std::map<std::pair<float, float>, csm::TsdfTables> tsdf_tabs;
+  csm::DevBuf tsdf_dev;
+  csm::StageRing tsdf_stage;
   ~csm_context() {
     for (csm_context* c : call_all) csm_context_destroy(c);
   }
@@ -344,7 +358,25 @@ struct csm_probability_grid {
   bool finished = false;
 };
 
+// A TSDF2D on the device (insert_tsdf2d.hip builds and updates it): the TSD
+// and weight planes and the rank plane of the first-writer rule. Host state
+// as for csm_probability_grid.
+struct csm_tsdf_grid {
+  csm_context* ctx = nullptr;
+  csm_map_limits limits{};
+  float truncation = 0.f, max_weight = 0.f;
+  csm::DevBuf tsd, weight;  // uint16, x fastest
+  csm::DevBuf rank;         // uint32 per cell, all ones between calls
+  uint64_t id = 0;          // process-unique, never 0 (shared counter with csm_probability_grid)
+  uint64_t generation = 0;  // bumped by every insert, grow and finish
+  bool finished = false;
+};
+
 namespace csm {
+// csm_rt2d_match_tsdf on a device grid (rt2d.hip).
+int Rt2dMatchTsdfGrid(csm_context* ctx, const csm_rt_options* o, const csm_tsdf_grid* grid,
+                      const csm_pose2d* initial, const float* xyz, int32_t n, double* score,
+                      csm_pose2d* pose);
 // csm_fast2d_create's body: cells from host memory (host_cells) or already on
 // the device and ordered on ctx->stream (dev_cells). Caller holds no lock.
 int Fast2dCreate(csm_context* ctx, const csm_map_limits* limits, const uint16_t* host_cells,

@@ -311,14 +311,18 @@ struct GridArgs {
   // `limits` was read at.
   const csm_probability_grid* dev = nullptr;
   uint64_t dev_generation = 0;
+  // A device-resident TSDF2D (cells == wcells == nullptr), likewise.
+  const csm_tsdf_grid* tdev = nullptr;
+  bool tsdf() const { return wcells != nullptr || tdev != nullptr; }
+  bool on_device() const { return dev != nullptr || tdev != nullptr; }
 };
 
 bool ValidGrid(const GridArgs& g) {
   const csm_map_limits* l = g.limits;
-  if (!l || (!g.cells && !g.dev) || l->num_x_cells < 1 || l->num_y_cells < 1 ||
+  if (!l || (!g.cells && !g.on_device()) || l->num_x_cells < 1 || l->num_y_cells < 1 ||
       !(l->resolution > 0.))
     return false;
-  if (g.wcells && !(g.truncation > 0.f && g.max_weight > 0.f)) return false;
+  if (g.tsdf() && !(g.truncation > 0.f && g.max_weight > 0.f)) return false;
   return static_cast<int64_t>(l->num_x_cells) * l->num_y_cells <= (1ll << 28);
 }
 
@@ -329,16 +333,20 @@ int EnsureGrid(csm_context* ctx, const GridArgs& g, int P, Rt2dGridDev* out) {
   csm::Rt2dCache& c = ctx->rt2d;
   const int nx = g.limits->num_x_cells, ny = g.limits->num_y_cells;
   const size_t ncell = static_cast<size_t>(nx) * ny;
-  const bool tsdf = g.wcells != nullptr;
+  const bool tsdf = g.tsdf();
+  const bool on_dev = g.on_device();
   const int W = nx + 2 * P, H = ny + 2 * P;
+  const uint64_t dev_id = g.dev ? g.dev->id : (g.tdev ? g.tdev->id : 0);
+  const uint64_t dev_gen = g.dev ? g.dev->generation : (g.tdev ? g.tdev->generation : 0);
+  const csm_map_limits* dev_limits = g.dev ? &g.dev->limits : (g.tdev ? &g.tdev->limits : nullptr);
   // A device grid changed between the caller's read of its limits and this
   // lock: the caller's error (the limits no longer describe the cells).
-  if (g.dev && (g.dev->generation != g.dev_generation || g.dev->limits.num_x_cells != nx ||
-                g.dev->limits.num_y_cells != ny))
+  if (on_dev && (dev_gen != g.dev_generation || dev_limits->num_x_cells != nx ||
+                 dev_limits->num_y_cells != ny))
     return CSM_EINVAL;
   const bool same =
       c.valid && c.nx == nx && c.ny == ny && c.P == P && c.tsdf == tsdf &&
-      (g.dev ? c.grid_id == g.dev->id && c.grid_gen == g.dev_generation
+      (on_dev ? c.grid_id == dev_id && c.grid_gen == g.dev_generation
              : c.grid_id == 0 &&
                    (!tsdf || (c.truncation == g.truncation && c.max_weight == g.max_weight)) &&
                    std::memcmp(c.cells.data(), g.cells, ncell * sizeof(uint16_t)) == 0 &&
@@ -373,7 +381,7 @@ int EnsureGrid(csm_context* ctx, const GridArgs& g, int P, Rt2dGridDev* out) {
     c.ttab_ok = true;
   }
   const size_t cell_bytes = ncell * sizeof(uint16_t) * (tsdf ? 2 : 1);
-  if (!g.dev) {
+  if (!on_dev) {
     if ((rc = c.stage_cells.Reserve(cell_bytes))) return rc;
     if ((rc = c.dcells.Reserve(cell_bytes))) return rc;
   }
@@ -382,8 +390,11 @@ int EnsureGrid(csm_context* ctx, const GridArgs& g, int P, Rt2dGridDev* out) {
   out->prob = tsdf ? nullptr : c.grid.as<float>();
   out->tsdf = tsdf ? c.grid.as<float2>() : nullptr;
   // Device grid: its cells are current on this stream (same context).
-  const uint16_t* dc = g.dev ? g.dev->cells.as<uint16_t>() : c.dcells.as<uint16_t>();
-  if (!g.dev) {
+  const uint16_t* dc = g.dev    ? g.dev->cells.as<uint16_t>()
+                       : g.tdev ? g.tdev->tsd.as<uint16_t>()
+                                : c.dcells.as<uint16_t>();
+  const uint16_t* dw = g.tdev ? g.tdev->weight.as<uint16_t>() : dc + ncell;
+  if (!on_dev) {
     uint16_t* stage = c.stage_cells.as<uint16_t>();
     std::memcpy(stage, g.cells, ncell * sizeof(uint16_t));
     if (tsdf) std::memcpy(stage + ncell, g.wcells, ncell * sizeof(uint16_t));
@@ -391,15 +402,15 @@ int EnsureGrid(csm_context* ctx, const GridArgs& g, int P, Rt2dGridDev* out) {
   }
   const int total = W * H;
   hipLaunchKernelGGL(rt2d_convert, dim3((total + 255) / 256), dim3(256), 0, st, dc,
-                     tsdf ? dc + ncell : nullptr, tsdf ? c.ttab.as<float>() : c.ptab.as<float>(),
+                     tsdf ? dw : nullptr, tsdf ? c.ttab.as<float>() : c.ptab.as<float>(),
                      tsdf ? c.ttab.as<float>() + 32768 : nullptr, g.truncation, nx, ny, P,
                      tsdf ? nullptr : c.grid.as<float>(), tsdf ? c.grid.as<float2>() : nullptr);
   CSM_HIP(hipGetLastError());
-  if (g.dev) c.cells.clear();
+  if (on_dev) c.cells.clear();
   else c.cells.assign(g.cells, g.cells + ncell);
-  if (tsdf) c.wcells.assign(g.wcells, g.wcells + ncell);
+  if (tsdf && !on_dev) c.wcells.assign(g.wcells, g.wcells + ncell);
   else c.wcells.clear();
-  c.grid_id = g.dev ? g.dev->id : 0;
+  c.grid_id = dev_id;
   c.grid_gen = g.dev_generation;
   c.nx = nx;
   c.ny = ny;
@@ -505,7 +516,7 @@ int Rt2dMatch(csm_context* ctx, const csm_rt_options* o, const GridArgs& g,
   const float2* drot = reinterpret_cast<const float2*>(c.dstage.as<char>() + rot_off);
   const int grid_bytes = static_cast<int>(
       (static_cast<int64_t>(l->num_x_cells) + 2 * P) * (l->num_y_cells + 2 * P) *
-      (g.wcells ? sizeof(float2) : sizeof(float)));
+      (g.tsdf() ? sizeof(float2) : sizeof(float)));
   if ((rc = c.sink.Reserve(sizeof(uint32_t)))) return rc;
   unsigned long long* hk = c.host_key.as<unsigned long long>();
   const auto t_prep = Rt2dClock::now();
@@ -539,7 +550,7 @@ int Rt2dMatch(csm_context* ctx, const csm_rt_options* o, const GridArgs& g,
     else if (depth == 32) CSM_RT2D_LAUNCH(TSDF, 32); \
     else CSM_RT2D_LAUNCH(TSDF, 16);           \
   } while (0)
-  if (g.wcells) CSM_RT2D_DEPTHS(true);
+  if (g.tsdf()) CSM_RT2D_DEPTHS(true);
   else CSM_RT2D_DEPTHS(false);
 #undef CSM_RT2D_DEPTHS
 #undef CSM_RT2D_LAUNCH
@@ -643,6 +654,20 @@ int Rt2dMatchGrid(csm_context* ctx, const csm_rt_options* o, const csm_probabili
   if (!ctx || !grid || grid->ctx != ctx) return CSM_EINVAL;
   csm_map_limits limits;
   GridArgs g{&limits, nullptr, nullptr, 0.f, 0.f, grid, 0};
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    limits = grid->limits;
+    g.dev_generation = grid->generation;
+  }
+  return Rt2dMatch(ctx, o, g, initial, xyz, n, score, pose);
+}
+
+int Rt2dMatchTsdfGrid(csm_context* ctx, const csm_rt_options* o, const csm_tsdf_grid* grid,
+                      const csm_pose2d* initial, const float* xyz, int32_t n, double* score,
+                      csm_pose2d* pose) {
+  if (!ctx || !grid || grid->ctx != ctx) return CSM_EINVAL;
+  csm_map_limits limits;
+  GridArgs g{&limits, nullptr, nullptr, grid->truncation, grid->max_weight, nullptr, 0, grid};
   {
     std::lock_guard<std::mutex> lock(ctx->mu);
     limits = grid->limits;

@@ -144,6 +144,8 @@ class FastCorrelativeScanMatcher2D {
   csm_fast2d* handle_ = nullptr;
 };
 
+class TSDF2D;  // the device-resident TSDF (submap_2d.h)
+
 // real_time_correlative_scan_matcher_2d.h:53-85
 class RealTimeCorrelativeScanMatcher2D {
  public:
@@ -175,6 +177,11 @@ class RealTimeCorrelativeScanMatcher2D {
     *pose_estimate = Rigid2d{out.x, out.y, out.theta};
     return score;
   }
+
+  // The same on a device-resident TSDF2D, without a host copy (defined in
+  // submap_2d.h, which has the type).
+  double Match(const Rigid2d& initial_pose_estimate, const PointCloud& point_cloud,
+               const TSDF2D& grid, Rigid2d* pose_estimate) const;
 
  private:
   csm_rt_options options_;

@@ -4,6 +4,8 @@
 //   submap_2d.h:86-115    ActiveSubmaps2D::InsertRangeData (.cc:153-232)
 //   probability_grid_range_data_inserter_2d.h:37-56  Insert(range_data, grid)
 //   probability_grid.h:31-68  ProbabilityGrid (limits, cells, ComputeCroppedGrid)
+//   tsdf_2d.h:34-78           TSDF2D (limits, both planes, ComputeCroppedGrid)
+//   tsdf_range_data_inserter_2d.h:33-55  Insert(range_data, grid)
 //
 // The grid lives on the device: Insert grows and updates it there with the
 // reference's values bit for bit, Finish crops it there, and both 2D matchers
@@ -108,6 +110,129 @@ inline double MatchRealTime(const RealTimeCorrelativeScanMatcherOptions& o,
   return score;
 }
 
+// proto::TSDFRangeDataInserterOptions2D (trajectory_builder_2d.lua:100-112
+// defaults), in the proto's types.
+struct TSDFRangeDataInserterOptions2D {
+  double truncation_distance = 0.3;
+  double maximum_weight = 10.;
+  bool update_free_space = false;
+  int num_normal_samples = 4;
+  double sample_radius = 0.5;
+  bool project_sdf_distance_to_scan_normal = true;
+  int update_weight_range_exponent = 0;
+  double update_weight_angle_scan_normal_to_ray_kernel_bandwidth = 0.5;
+  double update_weight_distance_cell_to_hit_kernel_bandwidth = 0.5;
+};
+
+// tsdf_2d.h:34-78: RAII holder of the device TSDF.
+class TSDF2D {
+ public:
+  // TSDF2D(limits, truncation_distance, max_weight, tables): all cells unknown.
+  TSDF2D(double resolution, double max_x, double max_y, int num_x_cells, int num_y_cells,
+         float truncation_distance, float max_weight, csm_context* context = nullptr)
+      : context_(context ? context : ThreadContext()) {
+    const csm_map_limits l{resolution, max_x, max_y, num_x_cells, num_y_cells};
+    CheckOk(csm_tsdf_grid_create(context_, &l, truncation_distance, max_weight, nullptr, nullptr,
+                                 &handle_),
+            "TSDF2D");
+  }
+  ~TSDF2D() { csm_tsdf_grid_destroy(handle_); }
+  TSDF2D(const TSDF2D&) = delete;
+  TSDF2D& operator=(const TSDF2D&) = delete;
+
+  // Grid2D::limits().
+  csm_map_limits limits() const {
+    csm_map_limits l{};
+    CheckOk(csm_tsdf_grid_limits(handle_, &l), "TSDF2D::limits");
+    return l;
+  }
+  // correspondence_cost_cells() (the TSD values) and the weight cells, read
+  // back (waits for the device).
+  void cells(std::vector<uint16_t>* tsd, std::vector<uint16_t>* weight) const {
+    const csm_map_limits l = limits();
+    const size_t n = static_cast<size_t>(l.num_x_cells) * l.num_y_cells;
+    tsd->assign(n, 0);
+    weight->assign(n, 0);
+    CheckOk(csm_tsdf_grid_read(handle_, tsd->data(), weight->data(), static_cast<int64_t>(n)),
+            "TSDF2D::cells");
+  }
+  // tsdf_2d.cc:118-135, in place (Submap2D::Finish replaces the grid by its
+  // cropped copy; nothing else calls it).
+  void ComputeCroppedGrid() { CheckOk(csm_tsdf_grid_finish(handle_), "TSDF2D::ComputeCroppedGrid"); }
+
+  csm_tsdf_grid* handle() const { return handle_; }
+  csm_context* context() const { return context_; }
+
+ private:
+  csm_context* context_;
+  csm_tsdf_grid* handle_ = nullptr;
+};
+
+// RealTimeCorrelativeScanMatcher2D::Match on a device TSDF
+// (real_time_correlative_scan_matcher_2d.cc:38-59, :117-149); declared in
+// scan_matching.h.
+inline double RealTimeCorrelativeScanMatcher2D::Match(const Rigid2d& initial_pose_estimate,
+                                                      const PointCloud& point_cloud,
+                                                      const TSDF2D& grid,
+                                                      Rigid2d* pose_estimate) const {
+  const csm_pose2d init{initial_pose_estimate.x, initial_pose_estimate.y,
+                        initial_pose_estimate.theta};
+  csm_pose2d out{};
+  double score = 0.;
+  CheckOk(csm_rt2d_match_tsdf_grid(grid.context(), &options_, grid.handle(), &init,
+                                   point_cloud.xyz.data(),
+                                   static_cast<int32_t>(point_cloud.size()), &score, &out),
+          "RealTimeCorrelativeScanMatcher2D::Match");
+  *pose_estimate = Rigid2d{out.x, out.y, out.theta};
+  return score;
+}
+
+// tsdf_range_data_inserter_2d.h:33-55 (the reference ignores the misses).
+class TSDFRangeDataInserter2D {
+ public:
+  explicit TSDFRangeDataInserter2D(const TSDFRangeDataInserterOptions2D& o)
+      : options_{o.truncation_distance,
+                 o.maximum_weight,
+                 o.update_free_space ? 1 : 0,
+                 o.num_normal_samples,
+                 o.sample_radius,
+                 o.project_sdf_distance_to_scan_normal ? 1 : 0,
+                 o.update_weight_range_exponent,
+                 o.update_weight_angle_scan_normal_to_ray_kernel_bandwidth,
+                 o.update_weight_distance_cell_to_hit_kernel_bandwidth} {}
+
+  void Insert(const RangeData& range_data, TSDF2D* grid) const {
+    CheckOk(csm_tsdf_grid_insert(grid->handle(), &options_, range_data.origin,
+                                 range_data.returns.xyz.data(),
+                                 static_cast<int32_t>(range_data.returns.size())),
+            "TSDFRangeDataInserter2D::Insert");
+  }
+
+  // The same scan into several grids of one context in one call.
+  void Insert(const RangeData& range_data, const std::vector<TSDF2D*>& grids) const {
+    if (grids.empty()) return;
+    const int n = static_cast<int>(grids.size());
+    std::vector<csm_tsdf_grid*> handles;
+    std::vector<int32_t> grid_of_scan;
+    std::vector<float> origins, returns;
+    std::vector<int64_t> return_offsets{0};
+    for (int g = 0; g < n; ++g) {
+      handles.push_back(grids[g]->handle());
+      grid_of_scan.push_back(g);
+      origins.insert(origins.end(), range_data.origin, range_data.origin + 3);
+      returns.insert(returns.end(), range_data.returns.xyz.begin(), range_data.returns.xyz.end());
+      return_offsets.push_back(static_cast<int64_t>(returns.size() / 3));
+    }
+    CheckOk(csm_tsdf_grid_insert_batch(grids[0]->context(), handles.data(), n, &options_, n,
+                                       grid_of_scan.data(), origins.data(), returns.data(),
+                                       return_offsets.data()),
+            "TSDFRangeDataInserter2D::Insert");
+  }
+
+ private:
+  csm_tsdf_inserter_options options_;
+};
+
 // probability_grid_range_data_inserter_2d.h:37-56
 class ProbabilityGridRangeDataInserter2D {
  public:
@@ -152,14 +277,19 @@ class ProbabilityGridRangeDataInserter2D {
   csm_inserter2d_options options_;
 };
 
-// submap_2d.h:41-72
+// submap_2d.h:41-72. The grid is a ProbabilityGrid (grid()) or a TSDF2D
+// (tsdf()); the other accessor returns null.
 class Submap2D {
  public:
   Submap2D(float origin_x, float origin_y, std::unique_ptr<ProbabilityGrid> grid)
       : origin_x_(origin_x), origin_y_(origin_y), grid_(std::move(grid)) {}
+  Submap2D(float origin_x, float origin_y, std::unique_ptr<TSDF2D> tsdf)
+      : origin_x_(origin_x), origin_y_(origin_y), tsdf_(std::move(tsdf)) {}
 
   const ProbabilityGrid* grid() const { return grid_.get(); }
   ProbabilityGrid* mutable_grid() { return grid_.get(); }
+  const TSDF2D* tsdf() const { return tsdf_.get(); }
+  TSDF2D* mutable_tsdf() { return tsdf_.get(); }
   float origin_x() const { return origin_x_; }
   float origin_y() const { return origin_y_; }
   int num_range_data() const { return num_range_data_; }
@@ -169,13 +299,21 @@ class Submap2D {
   void InsertRangeData(const RangeData& range_data,
                        const ProbabilityGridRangeDataInserter2D* range_data_inserter) {
     CheckOk(insertion_finished_ ? CSM_EINVAL : CSM_OK, "Submap2D::InsertRangeData");
+    CheckOk(grid_ ? CSM_OK : CSM_EINVAL, "Submap2D::InsertRangeData");
     range_data_inserter->Insert(range_data, grid_.get());
+    ++num_range_data_;
+  }
+  void InsertRangeData(const RangeData& range_data,
+                       const TSDFRangeDataInserter2D* range_data_inserter) {
+    CheckOk(insertion_finished_ || !tsdf_ ? CSM_EINVAL : CSM_OK, "Submap2D::InsertRangeData");
+    range_data_inserter->Insert(range_data, tsdf_.get());
     ++num_range_data_;
   }
   // submap_2d.cc:146-151
   void Finish() {
     CheckOk(insertion_finished_ ? CSM_EINVAL : CSM_OK, "Submap2D::Finish");
-    grid_->ComputeCroppedGrid();
+    if (grid_) grid_->ComputeCroppedGrid();
+    else tsdf_->ComputeCroppedGrid();
     insertion_finished_ = true;
   }
 
@@ -183,6 +321,7 @@ class Submap2D {
   friend class ActiveSubmaps2D;
   float origin_x_, origin_y_;
   std::unique_ptr<ProbabilityGrid> grid_;
+  std::unique_ptr<TSDF2D> tsdf_;
   int num_range_data_ = 0;
   bool insertion_finished_ = false;
 };
@@ -192,7 +331,11 @@ class Submap2D {
 struct SubmapsOptions2D {
   int num_range_data = 90;
   float resolution = 0.05f;
+  // grid_options_2d.grid_type; it selects the inserter too
+  // (CreateGrid / CreateRangeDataInserter, submap_2d.cc:176-222).
+  Grid2DView::GridType grid_type = Grid2DView::GridType::PROBABILITY_GRID;
   ProbabilityGridRangeDataInserterOptions2D range_data_inserter_options;
+  TSDFRangeDataInserterOptions2D tsdf_range_data_inserter_options;
 };
 
 // submap_2d.h:86-115
@@ -201,7 +344,8 @@ class ActiveSubmaps2D {
   explicit ActiveSubmaps2D(const SubmapsOptions2D& options, csm_context* context = nullptr)
       : options_(options),
         context_(context ? context : ThreadContext()),
-        range_data_inserter_(options.range_data_inserter_options) {}
+        range_data_inserter_(options.range_data_inserter_options),
+        tsdf_range_data_inserter_(options.tsdf_range_data_inserter_options) {}
 
   std::vector<std::shared_ptr<const Submap2D>> submaps() const {
     return std::vector<std::shared_ptr<const Submap2D>>(submaps_.begin(), submaps_.end());
@@ -212,11 +356,14 @@ class ActiveSubmaps2D {
     if (submaps_.empty() || submaps_.back()->num_range_data() == options_.num_range_data)
       AddSubmap(range_data.origin[0], range_data.origin[1]);
     std::vector<ProbabilityGrid*> grids;
+    std::vector<TSDF2D*> tsdfs;
     for (auto& submap : submaps_) {
       CheckOk(submap->insertion_finished() ? CSM_EINVAL : CSM_OK, "ActiveSubmaps2D");
-      grids.push_back(submap->mutable_grid());
+      if (submap->mutable_grid()) grids.push_back(submap->mutable_grid());
+      else tsdfs.push_back(submap->mutable_tsdf());
     }
     range_data_inserter_.Insert(range_data, grids);
+    tsdf_range_data_inserter_.Insert(range_data, tsdfs);
     for (auto& submap : submaps_) ++submap->num_range_data_;
     if (submaps_.front()->num_range_data() == 2 * options_.num_range_data)
       submaps_.front()->Finish();
@@ -224,7 +371,8 @@ class ActiveSubmaps2D {
   }
 
  private:
-  // submap_2d.cc:196-232: a kInitialSubmapSize^2 grid centred on the origin.
+  // submap_2d.cc:192-232: a kInitialSubmapSize^2 grid of options_.grid_type
+  // centred on the origin.
   void AddSubmap(float origin_x, float origin_y) {
     if (submaps_.size() >= 2) {
       CheckOk(submaps_.front()->insertion_finished() ? CSM_OK : CSM_EINVAL, "AddSubmap");
@@ -233,6 +381,16 @@ class ActiveSubmaps2D {
     constexpr int kInitialSubmapSize = 100;
     const float resolution = options_.resolution;
     const double half = 0.5 * kInitialSubmapSize * resolution;
+    if (options_.grid_type == Grid2DView::GridType::TSDF) {
+      const TSDFRangeDataInserterOptions2D& t = options_.tsdf_range_data_inserter_options;
+      submaps_.push_back(std::make_shared<Submap2D>(
+          origin_x, origin_y,
+          std::make_unique<TSDF2D>(resolution, static_cast<double>(origin_x) + half,
+                                   static_cast<double>(origin_y) + half, kInitialSubmapSize,
+                                   kInitialSubmapSize, static_cast<float>(t.truncation_distance),
+                                   static_cast<float>(t.maximum_weight), context_)));
+      return;
+    }
     submaps_.push_back(std::make_shared<Submap2D>(
         origin_x, origin_y,
         std::make_unique<ProbabilityGrid>(resolution, static_cast<double>(origin_x) + half,
@@ -243,6 +401,7 @@ class ActiveSubmaps2D {
   SubmapsOptions2D options_;
   csm_context* context_;
   ProbabilityGridRangeDataInserter2D range_data_inserter_;
+  TSDFRangeDataInserter2D tsdf_range_data_inserter_;
   std::vector<std::shared_ptr<Submap2D>> submaps_;
 };
 

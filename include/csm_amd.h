@@ -679,6 +679,107 @@ int csm_ray_to_pixel_mask(csm_context* ctx, const int32_t* begin_end_xyxy, int32
  * Host-only. */
 int csm_inserter2d_lookup_table(float probability, uint16_t* out /* [32768] */);
 
+/* ---- device-resident TSDF2D: TSDF range-data insertion ----------------------
+ * A TSDF2D (mapping/internal/2d/tsdf_2d.h:34-78: a TSD plane and a weight
+ * plane of uint16 values over one MapLimits) that lives on the device, is
+ * built there by TSDFRangeDataInserter2D::Insert
+ * (tsdf_range_data_inserter_2d.cc:131-240) bit for bit, and feeds the
+ * real-time matcher without a host copy. Calls are enqueued on the grid's
+ * context's stream under that context's lock, as for csm_probability_grid;
+ * only csm_tsdf_grid_read and _finish wait for the device. Up to 8192 cells
+ * per side. */
+typedef struct csm_tsdf_grid csm_tsdf_grid;
+
+/* proto::TSDFRangeDataInserterOptions2D
+ * (mapping/proto/tsdf_range_data_inserter_options_2d.proto:19-55, with its
+ * NormalEstimationOptions2D), in the proto's types; the casts to float happen
+ * where the reference casts. */
+typedef struct csm_tsdf_inserter_options {
+  double truncation_distance;
+  double maximum_weight;
+  int32_t update_free_space;
+  int32_t num_normal_samples;
+  double sample_radius;
+  int32_t project_sdf_distance_to_scan_normal;
+  int32_t update_weight_range_exponent;
+  double update_weight_angle_scan_normal_to_ray_kernel_bandwidth;
+  double update_weight_distance_cell_to_hit_kernel_bandwidth;
+} csm_tsdf_inserter_options;
+
+/* TSDF2D(limits, truncation_distance, max_weight, tables) (tsdf_2d.cc:23-34):
+ * all unknown when both cell arrays are NULL, else both hold
+ * num_x_cells * num_y_cells values, x fastest (tsdf_2d.cc:36-48). One array
+ * alone, or a truncation distance or maximum weight <= 0: CSM_EINVAL. */
+int csm_tsdf_grid_create(csm_context* ctx, const csm_map_limits* limits,
+                         float truncation_distance, float max_weight,
+                         const uint16_t* tsd_cells_or_null, const uint16_t* weight_cells_or_null,
+                         csm_tsdf_grid** out);
+void csm_tsdf_grid_destroy(csm_tsdf_grid* grid);
+/* Grid2D::limits() (grid_2d.h:51) as of the last enqueued call. */
+int csm_tsdf_grid_limits(const csm_tsdf_grid* grid, csm_map_limits* out);
+/* correspondence_cost_cells() and the weight cells (tsdf_2d.h:76): copies both
+ * planes to the host (capacity >= nx * ny values each) after waiting for the
+ * stream. */
+int csm_tsdf_grid_read(const csm_tsdf_grid* grid, uint16_t* tsd_out, uint16_t* weight_out,
+                       int64_t capacity);
+
+/* TSDFRangeDataInserter2D::Insert(range_data, grid)
+ * (tsdf_range_data_inserter_2d.cc:131-165): GrowAsNeeded (:33-47), the
+ * RangeDataSorter (:69-88) and EstimateNormals (normal_estimation_2d.cc:74-109)
+ * when the options ask for normals, InsertHit per return in that order
+ * (:167-225) and FinishUpdate. Misses are ignored by the reference, so none
+ * are passed. A cell is written by the first ray, in the reference's order,
+ * whose pixel mask holds it with a non-zero update weight (TSDF2D::SetCell,
+ * tsdf_2d.cc:56-69; UpdateCell, :227-239). With zero returns the limits still
+ * grow around the origin. CSM_EINVAL: a non-finite coordinate, a truncation
+ * distance or maximum weight <= 0, a negative num_normal_samples, a finished
+ * grid; CSM_ERANGE: growth past 8192 cells per side. Either leaves the grid as
+ * it was and enqueues nothing. */
+int csm_tsdf_grid_insert(csm_tsdf_grid* grid, const csm_tsdf_inserter_options* options,
+                         const float origin_xyz[3], const float* returns_xyz,
+                         int32_t num_returns);
+
+/* Many Inserts in one call, e.g. ActiveSubmaps2D::InsertRangeData's two
+ * submaps (submap_2d.cc:171-182). Arguments as for
+ * csm_probability_grid_insert_batch without the misses: scans of one grid are
+ * applied in array order, scans of different grids run concurrently in
+ * rounds. */
+int csm_tsdf_grid_insert_batch(csm_context* ctx, csm_tsdf_grid* const* grids, int32_t num_grids,
+                               const csm_tsdf_inserter_options* options, int32_t num_scans,
+                               const int32_t* grid_of_scan, const float* origins_xyz,
+                               const float* returns_xyz, const int64_t* return_offsets);
+
+/* Submap2D::Finish (submap_2d.cc:146-150): replaces the grid by
+ * TSDF2D::ComputeCroppedGrid() (tsdf_2d.cc:118-135): the known-cells box is
+ * the bounding box of the cells whose TSD value is not 0, and every known
+ * cell goes through SetCell(GetTSD, GetWeight) once more. An all-unknown grid
+ * crops to 1 x 1 at offset (0, 0). Later inserts return CSM_EINVAL. */
+int csm_tsdf_grid_finish(csm_tsdf_grid* grid);
+
+/* csm_rt2d_match_tsdf for a device-resident TSDF2D of ctx
+ * (real_time_correlative_scan_matcher_2d.cc:38-59, :117-149). The converted
+ * (term, weight) grid is cached per (grid id, generation, padding). */
+int csm_rt2d_match_tsdf_grid(csm_context* ctx, const csm_rt_options* options,
+                             const csm_tsdf_grid* grid, const csm_pose2d* initial,
+                             const float* points_xyz, int32_t n, double* score, csm_pose2d* pose);
+
+/* Test-visible and host-only, like csm_inserter2d_lookup_table: the per-ray
+ * plan of one Insert that the device consumes. order[k] is the index of the
+ * return cast as ray k (std::sort with the RangeDataSorter's comparator,
+ * :69-88; the identity when the options need no normals), normals[k] its
+ * estimated normal (NaN without normals), ray_weight[k] the float product of
+ * the range and angle weight factors (:205-214, :81-87), cast[k] 0 where the
+ * range is below the truncation distance (:174), else 1. Each output holds n
+ * entries; any may be NULL. */
+int csm_tsdf_plan_scan(const csm_tsdf_inserter_options* options, const float origin_xyz[3],
+                       const float* returns_xyz, int32_t n, int32_t* order_out,
+                       float* normals_out, float* ray_weight_out, uint8_t* cast_out);
+/* Test-visible, host-only: the two round-trip tables Finish copies through,
+ * TSDToValue(ValueToTSD(v)) and WeightToValue(ValueToWeight(v))
+ * (tsd_value_converter.h:33-50), 32768 entries each. */
+int csm_tsdf_round_trip_tables(float truncation_distance, float max_weight,
+                               uint16_t* tsd_out /* [32768] */, uint16_t* weight_out /* [32768] */);
+
 /* ---- device-resident HybridGrid: 3D range-data insertion --------------------
  * RangeDataInserter3D::Insert (mapping/3d/range_data_inserter_3d.cc:44-74,
  * :109-137) on the device brick of a csm_hybrid_grid, bit for bit: a grid
