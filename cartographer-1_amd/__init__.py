@@ -410,6 +410,24 @@ _SIGNATURES = {
     "csm_rt2d_match_tsdf_grid": (C.c_int, [C.c_void_p, C.POINTER(RtOptions), C.c_void_p,
                                            C.POINTER(Pose2D), C.POINTER(C.c_float), C.c_int32,
                                            C.POINTER(C.c_double), C.POINTER(Pose2D)]),
+    "csm_fast2d_create_tsdf": (C.c_int, [C.c_void_p, C.POINTER(MapLimits), C.POINTER(C.c_uint16),
+                                         C.POINTER(C.c_uint16), C.c_float, C.c_float,
+                                         C.POINTER(Fast2DOptions), C.POINTER(C.c_void_p)]),
+    "csm_fast2d_create_from_tsdf_grid": (C.c_int, [C.c_void_p, C.c_void_p,
+                                                   C.POINTER(Fast2DOptions),
+                                                   C.POINTER(C.c_void_p)]),
+    "csm_ceres2d_match_grid": (C.c_int, [C.c_void_p, C.POINTER(CeresOptions2D), C.c_void_p,
+                                         C.POINTER(C.c_double), C.POINTER(Pose2D),
+                                         C.POINTER(C.c_float), C.c_int32, C.POINTER(Pose2D),
+                                         C.POINTER(C.c_int32)]),
+    "csm_ceres2d_match_tsdf_grid": (C.c_int, [C.c_void_p, C.POINTER(CeresOptions2D), C.c_void_p,
+                                              C.POINTER(C.c_double), C.POINTER(Pose2D),
+                                              C.POINTER(C.c_float), C.c_int32, C.POINTER(Pose2D),
+                                              C.POINTER(C.c_int32)]),
+    "csm_ceres2d_tsdf_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float),
+                                            C.c_int32, C.c_double, C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int32)]),
     "csm_tsdf_plan_scan": (C.c_int, [C.POINTER(TSDFInserterOptions), C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -890,7 +908,8 @@ class DeviceProbabilityGrid:
 class DeviceTSDF2D:
     """A TSDF2D that lives on the device (csm_tsdf_grid): built there by the
     reference's TSDFRangeDataInserter2D bit for bit, grown and cropped there,
-    and read by the real-time matcher without a host copy."""
+    and read without a host copy by the real-time matcher, the fast matcher's
+    constructor and CeresScanMatcher2D."""
 
     def __init__(self, resolution: float, max_x: float, max_y: float, num_x_cells: int,
                  num_y_cells: int, truncation_distance: float, max_weight: float,
@@ -1054,9 +1073,12 @@ class RealTimeCorrelativeScanMatcherOptions:
 
 
 class FastCorrelativeScanMatcher2D:
-    """Device pyramid of one submap grid; Match / MatchFullSubmap run on the GPU."""
+    """Device pyramid of one submap grid; Match / MatchFullSubmap run on the GPU.
+    The grid is a ProbabilityGrid, a TSDF2D or either one's device-resident
+    class; a matcher made from a TSDF also carries the weights, and
+    ceres_refine_batch refines it with the TSDF match cost."""
 
-    def __init__(self, grid: ProbabilityGrid, options: FastCorrelativeScanMatcherOptions2D,
+    def __init__(self, grid, options: FastCorrelativeScanMatcherOptions2D,
                  context: Optional[Context] = None):
         self.context = context or default_context()
         self._lib = self.context._lib
@@ -1065,10 +1087,29 @@ class FastCorrelativeScanMatcher2D:
         opts = Fast2DOptions(options.linear_search_window, options.angular_search_window,
                              options.branch_and_bound_depth, options.search_depth)
         h = C.c_void_p()
+        self.is_tsdf = False
         if isinstance(grid, DeviceProbabilityGrid):
             _check(self._lib.csm_fast2d_create_from_grid(self.context.handle, grid.handle,
                                                          C.byref(opts), C.byref(h)),
                    "csm_fast2d_create_from_grid")
+            self.handle = h
+            return
+        self.is_tsdf = isinstance(grid, (TSDF2D, DeviceTSDF2D))
+        if isinstance(grid, DeviceTSDF2D):
+            _check(self._lib.csm_fast2d_create_from_tsdf_grid(self.context.handle, grid.handle,
+                                                              C.byref(opts), C.byref(h)),
+                   "csm_fast2d_create_from_tsdf_grid")
+            self.handle = h
+            return
+        if isinstance(grid, TSDF2D):
+            tsd = np.ascontiguousarray(grid.tsd_cells, dtype=np.uint16)
+            wgt = np.ascontiguousarray(grid.weight_cells, dtype=np.uint16)
+            if tsd.shape != wgt.shape:
+                raise ValueError("TSDF2D tsd_cells and weight_cells differ in shape")
+            _check(self._lib.csm_fast2d_create_tsdf(
+                self.context.handle, C.byref(self.grid_limits), _ptr(tsd, C.c_uint16),
+                _ptr(wgt, C.c_uint16), grid.truncation_distance, grid.max_weight, C.byref(opts),
+                C.byref(h)), "csm_fast2d_create_tsdf")
             self.handle = h
             return
         cells = np.ascontiguousarray(grid.cells, dtype=np.uint16)
@@ -1446,6 +1487,61 @@ def ceres_refine_batch(matchers: Sequence[FastCorrelativeScanMatcher2D], scans: 
     return poses, iters[:n]
 
 
+class CeresScanMatcher2D:
+    """ceres_scan_matcher_2d.h: Match(target_translation, initial, cloud, grid)
+    -> (pose, iterations) on the device. A DeviceProbabilityGrid or DeviceTSDF2D
+    is read where it lives (csm_ceres2d_match_grid / _match_tsdf_grid); a host
+    ProbabilityGrid or TSDF2D goes through a one-level matcher handle."""
+
+    def __init__(self, options: Optional["CeresOptions2D"] = None,
+                 context: Optional[Context] = None):
+        self.options = options or CeresOptions2D.make()
+        self.context = context or default_context()
+
+    def Match(self, target_translation, initial_pose_estimate, point_cloud, grid):
+        ctx = self.context
+        pts = _f32_points(point_cloud)
+        if isinstance(grid, (DeviceProbabilityGrid, DeviceTSDF2D)):
+            tsdf = isinstance(grid, DeviceTSDF2D)
+            fn = ctx._lib.csm_ceres2d_match_tsdf_grid if tsdf else ctx._lib.csm_ceres2d_match_grid
+            target = (C.c_double * 2)(float(target_translation[0]), float(target_translation[1]))
+            init = Pose2D(*initial_pose_estimate)
+            pose, iters = Pose2D(), C.c_int32(0)
+            _check(fn(ctx.handle, C.byref(self.options), grid.handle, target, C.byref(init),
+                      _ptr(pts, C.c_float), len(pts), C.byref(pose), C.byref(iters)),
+                   "csm_ceres2d_match_tsdf_grid" if tsdf else "csm_ceres2d_match_grid")
+            return pose.as_tuple(), int(iters.value)
+        matcher = FastCorrelativeScanMatcher2D(
+            grid, FastCorrelativeScanMatcherOptions2D(0.1, 0.1, 1, 1), ctx)
+        scans = ScanSet([pts], ctx)
+        try:
+            poses, iters = ceres_refine_batch(
+                [matcher], scans, [0], [0], [tuple(initial_pose_estimate)],
+                [tuple(target_translation)[:2]], self.options, ctx)
+        finally:
+            scans.close()
+            matcher.close()
+        return tuple(float(v) for v in poses[0]), int(iters[0])
+
+
+def ceres_tsdf_evaluate(matcher: FastCorrelativeScanMatcher2D, point_cloud,
+                        scaling_factor: float, pose, context: Optional[Context] = None):
+    """csm_ceres2d_tsdf_evaluate (visible for testing): TSDFMatchCostFunction2D
+    alone on a TSDF matcher -> (valid, residuals (n,), jacobian (n, 3))."""
+    ctx = context or matcher.context
+    pts = _f32_points(point_cloud)
+    n = len(pts)
+    res = np.zeros(max(n, 1), np.float64)
+    jac = np.zeros((max(n, 1), 3), np.float64)
+    valid = C.c_int32(0)
+    p = (C.c_double * 3)(*[float(v) for v in pose])
+    _check(ctx._lib.csm_ceres2d_tsdf_evaluate(ctx.handle, matcher.handle, _ptr(pts, C.c_float), n,
+                                              float(scaling_factor), p, _ptr(res, C.c_double),
+                                              _ptr(jac, C.c_double), C.byref(valid)),
+           "csm_ceres2d_tsdf_evaluate")
+    return bool(valid.value), res[:n], jac[:n]
+
+
 # --------------------------------------------------------------------------
 # Synthetic world (bench / test inputs; not the matching path).
 
@@ -1727,7 +1823,7 @@ def synchronize(context: "Context"):
         raise CsmError("hipStreamSynchronize failed")
 
 
-from .submap_2d import (ActiveSubmaps2D, ProbabilityGridRangeDataInserter2D,  # noqa: E402,F401
+from .submap_2d import (ActiveSubmaps2D, FastMatcherFor, ProbabilityGridRangeDataInserter2D,  # noqa: E402,F401
                         ProbabilityGridRangeDataInserterOptions2D, RangeData, Submap2D,
                         TSDFRangeDataInserter2D, TSDFRangeDataInserterOptions2D)
 from .submap_3d import (ActiveSubmaps3D, RangeDataInserter3D,  # noqa: E402,F401

@@ -22,7 +22,10 @@ Instead of one ``common::Task`` per pair, the pending pairs are searched as one
 GPU batch (``match_batch``) when a node ends, or once ``flush_pairs`` pairs are
 pending. Accepted matches are then refined as one batch with the
 CeresScanMatcher2D restatement (:245-249; ``ceres_refine_batch``, parity with
-Ceres unpinned) unless ``refine_with_ceres`` is off.
+Ceres unpinned) unless ``refine_with_ceres`` is off. A submap whose grid is a
+``TSDF2D`` or ``DeviceTSDF2D`` gets a TSDF matcher, and its matches are refined
+with the TSDF match cost, as ceres_scan_matcher_2d.cc:74-91 switches on the
+grid type.
 """
 
 from __future__ import annotations
@@ -246,7 +249,7 @@ def _budget_parts(pending, key_of, cache: _MatcherCache, make, bytes_of):
 class Submap2D:
     """What the builder reads of a Submap2D: its grid and local pose
     (ComputeSubmapPose = Project2D(local_pose), constraint_builder_2d.cc:55-57)."""
-    grid: ProbabilityGrid
+    grid: ProbabilityGrid  # or a TSDF2D, or either one's device-resident class
     local_pose: Tuple[float, float, float] = (0.0, 0.0, 0.0)
 
 

@@ -16,6 +16,12 @@
 // 1e-10 / 1e-8, non-monotonic steps as pose_graph.lua:35 sets them). Ceres is
 // absent from this image: the solver follows oracle/ceres2d.cc's restatement,
 // which the reference's ceres_scan_matcher_2d_test.cc pins.
+//
+// csm_ceres2d_refine_batch sends each item to the kernel of its handle's kind:
+// this one for probability grids, ceres2d_tsdf.hip's for TSDF handles. The
+// single-call entry points csm_ceres2d_match_grid / _match_tsdf_grid run the
+// same kernels on a device-resident grid's uint16 cells (kU16), for
+// LocalTrajectoryBuilder2D::ScanMatch's call on the active submap.
 
 #include <hip/hip_runtime.h>
 
@@ -24,35 +30,24 @@
 #include <cmath>
 #include <vector>
 
+#include "ceres2d_common.h"
 #include "ceres_lm.h"
 #include "csm_internal.h"
 
 namespace csm {
 namespace {
 
-constexpr int kRefineThreads = 256;
 constexpr int kPadding = INT_MAX / 4;
 
-struct RefineDesc {
-  const float* cost;  // num_y_cells x num_x_cells correspondence costs
-  double max_x, max_y, resolution;
-  int32_t nx, ny;
-  double max_cost;
-  int64_t point_offset;
-  int32_t n;
-  double initial[3], target[2];
-};
-
-struct RefineOpts {
-  double occupied, wt, wr;
-  int max_iterations;
-  int nonmonotonic;  // ceres_solver_options.use_nonmonotonic_steps
-};
-
+// kU16: the cells of a device-resident grid through their value table
+// (oracle/ceres2d.cc:50) instead of a handle's float plane.
+template <bool kU16>
 __device__ __forceinline__ double CostAt(const RefineDesc& d, int row, int col) {
   if (row < kPadding || col < kPadding || row >= d.ny + kPadding || col >= d.nx + kPadding)
     return d.max_cost;
-  return static_cast<double>(d.cost[static_cast<int64_t>(row - kPadding) * d.nx + (col - kPadding)]);
+  const int64_t at = static_cast<int64_t>(row - kPadding) * d.nx + (col - kPadding);
+  if (kU16) return static_cast<double>(d.table[d.cells16[at] & 0x7fff]);
+  return static_cast<double>(d.cost[at]);
 }
 
 // ceres::CubicHermiteSpline.
@@ -67,6 +62,7 @@ __device__ __forceinline__ void Hermite(double p0, double p1, double p2, double 
 }
 
 // Residual row i (and its Jacobian row when J != nullptr) at pose x.
+template <bool kU16>
 __device__ void Row(const RefineDesc& d, const float* pts, double scale, const double* x, double s,
                     double c, int i, double* r, double* J) {
   const double px = static_cast<double>(pts[3 * i]), py = static_cast<double>(pts[3 * i + 1]);
@@ -79,7 +75,8 @@ __device__ void Row(const RefineDesc& d, const float* pts, double scale, const d
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int q = row - 1 + k;
-    Hermite(CostAt(d, q, col - 1), CostAt(d, q, col), CostAt(d, q, col + 1), CostAt(d, q, col + 2),
+    Hermite(CostAt<kU16>(d, q, col - 1), CostAt<kU16>(d, q, col), CostAt<kU16>(d, q, col + 1),
+            CostAt<kU16>(d, q, col + 2),
             cc - col, &fr[k], &dfr[k]);
   }
   double f, dfdr, dfdc;
@@ -94,57 +91,9 @@ __device__ void Row(const RefineDesc& d, const float* pts, double scale, const d
   }
 }
 
-__device__ __forceinline__ double WaveSumD(double v) {
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// Sums k doubles per thread over the workgroup; every thread gets the totals.
-template <int K>
-__device__ void BlockSum(double* v, double (*red)[K]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double t = WaveSumD(v[k]);
-    if (lane == 0) red[w][k] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double t = 0.;
-    for (int q = 0; q < kRefineThreads / 64; ++q) t += red[q][k];
-    v[k] = t;
-  }
-  __syncthreads();
-}
-
-__device__ bool Solve3(double M[3][4], double out[3]) {
-  for (int c = 0; c < 3; ++c) {
-    int piv = c;
-    for (int i = c + 1; i < 3; ++i)
-      if (fabs(M[i][c]) > fabs(M[piv][c])) piv = i;
-    if (M[piv][c] == 0.) return false;
-    for (int j = 0; j < 4; ++j) {
-      const double t = M[c][j];
-      M[c][j] = M[piv][j];
-      M[piv][j] = t;
-    }
-    for (int i = c + 1; i < 3; ++i) {
-      const double f = M[i][c] / M[c][c];
-      for (int j = c; j < 4; ++j) M[i][j] -= f * M[c][j];
-    }
-  }
-  for (int i = 2; i >= 0; --i) {
-    double v = M[i][3];
-    for (int j = i + 1; j < 3; ++j) v -= M[i][j] * out[j];
-    out[i] = v / M[i][i];
-  }
-  return true;
-}
-
 // Pass over the N occupied-space rows plus the 3 delta rows at pose x:
 // out[0] = sum r^2, and with jac, out[1..6] = Ju^T Ju (upper), out[7..9] = Ju^T r.
-template <bool kJac>
+template <bool kU16, bool kJac>
 __device__ void Pass(const RefineDesc& d, const float* pts, double scale, const RefineOpts& o,
                      const double* x, double* out, double (*red)[10]) {
   const double s = sin(x[2]), c = cos(x[2]);
@@ -152,7 +101,7 @@ __device__ void Pass(const RefineDesc& d, const float* pts, double scale, const 
   for (int i = threadIdx.x; i < d.n + 3; i += kRefineThreads) {
     double r, J[3] = {0., 0., 0.};
     if (i < d.n) {
-      Row(d, pts, scale, x, s, c, i, &r, kJac ? J : nullptr);
+      Row<kU16>(d, pts, scale, x, s, c, i, &r, kJac ? J : nullptr);
     } else if (i == d.n) {
       r = o.wt * (x[0] - d.target[0]);
       J[0] = o.wt;
@@ -186,16 +135,21 @@ __device__ void Pass(const RefineDesc& d, const float* pts, double scale, const 
 // candidate), acceptance by step quality > 1e-3; the lowest-cost accepted
 // point is returned. Every thread runs the (scalar) step logic on the same
 // block-reduced sums, so all of them hold the same state.
+// Workgroup b refines items[order[b]] (order == nullptr: items[b]) and writes
+// the result at that index.
+template <bool kU16>
 __global__ void __launch_bounds__(kRefineThreads)
-ceres2d_refine(const RefineDesc* __restrict__ items, const float* __restrict__ points,
-               RefineOpts o, double* __restrict__ out_pose, int32_t* __restrict__ out_iters) {
+ceres2d_refine(const RefineDesc* __restrict__ items, const int32_t* __restrict__ order,
+               const float* __restrict__ points, RefineOpts o, double* __restrict__ out_pose,
+               int32_t* __restrict__ out_iters) {
   __shared__ double red[kRefineThreads / 64][10];
-  const RefineDesc d = items[blockIdx.x];
+  const int item = order ? order[blockIdx.x] : static_cast<int>(blockIdx.x);
+  const RefineDesc d = items[item];
   const float* pts = points + 3 * d.point_offset;
   const double scale = o.occupied / sqrt(static_cast<double>(d.n));
   double x[3] = {d.initial[0], d.initial[1], d.initial[2]};
   double S[10];
-  Pass<true>(d, pts, scale, o, x, S, red);
+  Pass<kU16, true>(d, pts, scale, o, x, S, red);
   double cost = 0.5 * S[0];
   // Jacobi scaling from the initial Jacobian.
   const double js[3] = {1. / (1. + sqrt(S[1])), 1. / (1. + sqrt(S[4])), 1. / (1. + sqrt(S[6]))};
@@ -240,14 +194,14 @@ ceres2d_refine(const RefineDesc* __restrict__ items, const float* __restrict__ p
         x_norm += x[a] * x[a];
       }
       double T[10];
-      Pass<false>(d, pts, scale, o, xn, T, red);
+      Pass<kU16, false>(d, pts, scale, o, xn, T, red);
       const double new_cost = 0.5 * T[0];
       if (sqrt(step_norm) <= (sqrt(x_norm) + 1e-8) * 1e-8) break;  // parameter tolerance
       if (fabs(cost - new_cost) <= 1e-6 * cost) break;             // function tolerance
       const double quality = ev.Quality(new_cost, model);
       if (quality > 1e-3) {
         for (int a = 0; a < 3; ++a) x[a] = xn[a];
-        Pass<true>(d, pts, scale, o, x, S, red);
+        Pass<kU16, true>(d, pts, scale, o, x, S, red);
         cost = 0.5 * S[0];
         lm.Accepted(quality);
         ev.Accepted(new_cost, model);
@@ -262,11 +216,101 @@ ceres2d_refine(const RefineDesc* __restrict__ items, const float* __restrict__ p
     go = iter < o.max_iterations && lm.radius >= 1e-32 && !gradient_small();
   }
   if (threadIdx.x == 0) {
-    out_pose[3 * blockIdx.x + 0] = best[0];
-    out_pose[3 * blockIdx.x + 1] = best[1];
-    out_pose[3 * blockIdx.x + 2] = best[2];
-    if (out_iters) out_iters[blockIdx.x] = iter;
+    out_pose[3 * item + 0] = best[0];
+    out_pose[3 * item + 1] = best[1];
+    out_pose[3 * item + 2] = best[2];
+    if (out_iters) out_iters[item] = iter;
   }
+}
+
+// Uploads the items, runs each through its grid kind's kernel and reads the
+// results back in item order. u16: the items read device grids' uint16 cells.
+// The caller holds ctx->mu.
+int RunRefine2d(csm_context* ctx, const std::vector<RefineDesc>& desc,
+                const std::vector<uint8_t>& tsdf, bool u16, const float* dpoints,
+                const csm_ceres2d_options* options, csm_pose2d* out, int32_t* iterations) {
+  const size_t n = desc.size();
+  // Item indices by grid kind, probability items first. A batch of one kind
+  // needs no index list: workgroup b takes item b.
+  std::vector<int32_t> order;
+  order.reserve(n);
+  for (size_t i = 0; i < n; ++i)
+    if (!tsdf[i]) order.push_back(static_cast<int32_t>(i));
+  const int num_prob = static_cast<int>(order.size()), num_tsdf = static_cast<int>(n) - num_prob;
+  for (size_t i = 0; i < n; ++i)
+    if (tsdf[i]) order.push_back(static_cast<int32_t>(i));
+  const bool mixed = num_prob > 0 && num_tsdf > 0;
+  int rc;
+  const size_t desc_bytes = sizeof(RefineDesc) * n;
+  if ((rc = ctx->cr_items.Reserve(desc_bytes + (mixed ? sizeof(int32_t) * n : 0)))) return rc;
+  if ((rc = ctx->cr_out.Reserve(sizeof(double) * 3 * n + sizeof(int32_t) * n))) return rc;
+  hipStream_t st = ctx->stream;
+  CSM_HIP(hipMemcpyAsync(ctx->cr_items.ptr, desc.data(), desc_bytes, hipMemcpyHostToDevice, st));
+  const RefineDesc* ditems = ctx->cr_items.as<RefineDesc>();
+  const int32_t* dorder = nullptr;
+  if (mixed) {
+    dorder = reinterpret_cast<const int32_t*>(ctx->cr_items.as<char>() + desc_bytes);
+    CSM_HIP(hipMemcpyAsync(const_cast<int32_t*>(dorder), order.data(), sizeof(int32_t) * n,
+                           hipMemcpyHostToDevice, st));
+  }
+  const RefineOpts o{options->occupied_space_weight, options->translation_weight,
+                     options->rotation_weight, options->max_num_iterations,
+                     options->use_nonmonotonic_steps ? 1 : 0};
+  double* dpose = ctx->cr_out.as<double>();
+  int32_t* diters = reinterpret_cast<int32_t*>(dpose + 3 * n);
+  if (num_prob > 0) {
+    if (u16)
+      hipLaunchKernelGGL(ceres2d_refine<true>, dim3(static_cast<unsigned>(num_prob)),
+                         dim3(kRefineThreads), 0, st, ditems, dorder, dpoints, o, dpose, diters);
+    else
+      hipLaunchKernelGGL(ceres2d_refine<false>, dim3(static_cast<unsigned>(num_prob)),
+                         dim3(kRefineThreads), 0, st, ditems, dorder, dpoints, o, dpose, diters);
+    CSM_HIP(hipGetLastError());
+  }
+  if (num_tsdf > 0)
+    CSM_HIP(LaunchCeres2dTsdfRefine(ditems, mixed ? dorder + num_prob : nullptr, num_tsdf, u16,
+                                    dpoints, o, dpose, diters, st));
+  std::vector<double> pose(3 * n);
+  CSM_HIP(hipMemcpyAsync(pose.data(), dpose, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
+  if (iterations)
+    CSM_HIP(hipMemcpyAsync(iterations, diters, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < n; ++i) out[i] = csm_pose2d{pose[3 * i], pose[3 * i + 1], pose[3 * i + 2]};
+  return CSM_OK;
+}
+
+int CheckCeres2dOptions(const csm_ceres2d_options* options) {
+  if (!(options->occupied_space_weight > 0.) || !(options->translation_weight > 0.) ||
+      !(options->rotation_weight > 0.) || options->max_num_iterations < 0)
+    return CSM_EINVAL;  // the reference CHECKs the weights (ceres_scan_matcher_2d.cc:74-97)
+  return CSM_OK;
+}
+
+int UploadSingleCloud(csm_context* ctx, const float* points_xyz, int32_t n) {
+  if (!points_xyz || n < 1) return CSM_EINVAL;
+  for (int64_t i = 0; i < 3 * static_cast<int64_t>(n); ++i)
+    if (!std::isfinite(points_xyz[i])) return CSM_EINVAL;
+  int rc;
+  if ((rc = ctx->cr_points.Reserve(sizeof(float) * 3 * n))) return rc;
+  CSM_HIP(hipMemcpyAsync(ctx->cr_points.ptr, points_xyz, sizeof(float) * 3 * n,
+                         hipMemcpyHostToDevice, ctx->stream));
+  return CSM_OK;
+}
+
+void FillSingleItem(const csm_map_limits& limits, const double target_xy[2],
+                    const csm_pose2d* initial, int32_t n, RefineDesc* d) {
+  d->max_x = limits.max_x;
+  d->max_y = limits.max_y;
+  d->resolution = limits.resolution;
+  d->nx = limits.num_x_cells;
+  d->ny = limits.num_y_cells;
+  d->point_offset = 0;
+  d->n = n;
+  d->initial[0] = initial->x;
+  d->initial[1] = initial->y;
+  d->initial[2] = initial->theta;
+  d->target[0] = target_xy[0];
+  d->target[1] = target_xy[1];
 }
 
 }  // namespace
@@ -281,21 +325,23 @@ int csm_ceres2d_refine_batch(csm_context* ctx, csm_fast2d* const* submaps, int32
   using namespace csm;
   if (!ctx || !scans || !options || (n > 0 && (!items || !out || !submaps))) return CSM_EINVAL;
   if (n == 0) return CSM_OK;
-  if (!(options->occupied_space_weight > 0.) || !(options->translation_weight > 0.) ||
-      !(options->rotation_weight > 0.) || options->max_num_iterations < 0)
-    return CSM_EINVAL;  // the reference CHECKs the weights (ceres_scan_matcher_2d.cc:74-97)
+  if (CheckCeres2dOptions(options)) return CSM_EINVAL;
   if (n > 0x7fffffff) return CSM_ERANGE;
   const int64_t num_scans = static_cast<int64_t>(scans->offsets.size()) - 1;
   std::vector<RefineDesc> desc(static_cast<size_t>(n));
+  std::vector<uint8_t> tsdf(static_cast<size_t>(n));
   for (int64_t i = 0; i < n; ++i) {
     const csm_refine2d& it = items[i];
     if (it.submap < 0 || it.submap >= num_submaps || !submaps[it.submap] || it.scan < 0 ||
         it.scan >= num_scans)
       return CSM_EINVAL;
     const csm_fast2d* m = submaps[it.submap];
-    if (m->ctx != ctx || !m->cost.ptr) return CSM_EINVAL;
+    if (m->ctx != ctx || !m->cost.ptr || (m->tsdf && !m->weight.ptr)) return CSM_EINVAL;
     RefineDesc& d = desc[i];
+    d = RefineDesc{};
     d.cost = m->cost.as<float>();
+    d.weight = m->tsdf ? m->weight.as<float>() : nullptr;
+    tsdf[i] = m->tsdf ? 1 : 0;
     d.max_x = m->limits.max_x;
     d.max_y = m->limits.max_y;
     d.resolution = m->limits.resolution;
@@ -313,27 +359,59 @@ int csm_ceres2d_refine_batch(csm_context* ctx, csm_fast2d* const* submaps, int32
   }
   std::lock_guard<std::mutex> lock(ctx->mu);
   if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  return RunRefine2d(ctx, desc, tsdf, false, scans->points.as<float>(), options, out, iterations);
+}
+
+int csm_ceres2d_match_grid(csm_context* ctx, const csm_ceres2d_options* options,
+                           const csm_probability_grid* grid, const double target_xy[2],
+                           const csm_pose2d* initial, const float* points_xyz, int32_t n,
+                           csm_pose2d* pose_out, int32_t* iterations_out) {
+  using namespace csm;
+  if (!ctx || !options || !grid || !target_xy || !initial || !pose_out) return CSM_EINVAL;
+  if (grid->ctx != ctx || CheckCeres2dOptions(options)) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
   int rc;
-  if ((rc = ctx->cr_items.Reserve(sizeof(RefineDesc) * n))) return rc;
-  if ((rc = ctx->cr_out.Reserve(sizeof(double) * 3 * n + sizeof(int32_t) * n))) return rc;
-  hipStream_t st = ctx->stream;
-  CSM_HIP(hipMemcpyAsync(ctx->cr_items.ptr, desc.data(), sizeof(RefineDesc) * n,
-                         hipMemcpyHostToDevice, st));
-  const RefineOpts o{options->occupied_space_weight, options->translation_weight,
-                     options->rotation_weight, options->max_num_iterations,
-                     options->use_nonmonotonic_steps ? 1 : 0};
-  double* dpose = ctx->cr_out.as<double>();
-  int32_t* diters = reinterpret_cast<int32_t*>(dpose + 3 * n);
-  hipLaunchKernelGGL(ceres2d_refine, dim3(static_cast<unsigned>(n)), dim3(kRefineThreads), 0, st,
-                     ctx->cr_items.as<RefineDesc>(), scans->points.as<float>(), o, dpose, diters);
-  CSM_HIP(hipGetLastError());
-  std::vector<double> pose(3 * static_cast<size_t>(n));
-  CSM_HIP(hipMemcpyAsync(pose.data(), dpose, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
-  if (iterations)
-    CSM_HIP(hipMemcpyAsync(iterations, diters, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-  CSM_HIP(hipStreamSynchronize(st));
-  for (int64_t i = 0; i < n; ++i) out[i] = csm_pose2d{pose[3 * i], pose[3 * i + 1], pose[3 * i + 2]};
-  return CSM_OK;
+  if ((rc = UploadSingleCloud(ctx, points_xyz, n))) return rc;
+  // ProbabilityGrid's bounds are the library constants (probability_values.h).
+  const float min_cc = 1.f - (1.f - 0.1f), max_cc = 1.f - 0.1f;
+  const float* table;
+  if ((rc = EnsureValueTable(ctx, max_cc, min_cc, max_cc, &table))) return rc;
+  std::vector<RefineDesc> desc(1);
+  FillSingleItem(grid->limits, target_xy, initial, n, &desc[0]);
+  desc[0].max_cost = static_cast<double>(max_cc);
+  desc[0].cells16 = grid->cells.as<uint16_t>();
+  desc[0].table = table;
+  return RunRefine2d(ctx, desc, {0}, true, ctx->cr_points.as<float>(), options, pose_out,
+                     iterations_out);
+}
+
+int csm_ceres2d_match_tsdf_grid(csm_context* ctx, const csm_ceres2d_options* options,
+                                const csm_tsdf_grid* grid, const double target_xy[2],
+                                const csm_pose2d* initial, const float* points_xyz, int32_t n,
+                                csm_pose2d* pose_out, int32_t* iterations_out) {
+  using namespace csm;
+  if (!ctx || !options || !grid || !target_xy || !initial || !pose_out) return CSM_EINVAL;
+  if (grid->ctx != ctx || CheckCeres2dOptions(options)) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  int rc;
+  if ((rc = UploadSingleCloud(ctx, points_xyz, n))) return rc;
+  // Grid2D's table of a TSDF2D (tsdf_2d.cc:24-27, grid_2d.cc:69-71) and
+  // TSDValueConverter::ValueToWeight.
+  const float *table, *wtable;
+  if ((rc = EnsureValueTable(ctx, grid->truncation, -grid->truncation, grid->truncation, &table)) ||
+      (rc = EnsureValueTable(ctx, 0.f, 0.f, grid->max_weight, &wtable)))
+    return rc;
+  std::vector<RefineDesc> desc(1);
+  FillSingleItem(grid->limits, target_xy, initial, n, &desc[0]);
+  desc[0].max_cost = static_cast<double>(grid->truncation);
+  desc[0].cells16 = grid->tsd.as<uint16_t>();
+  desc[0].table = table;
+  desc[0].weight16 = grid->weight.as<uint16_t>();
+  desc[0].wtable = wtable;
+  return RunRefine2d(ctx, desc, {1}, true, ctx->cr_points.as<float>(), options, pose_out,
+                     iterations_out);
 }
 
 }  // extern "C"

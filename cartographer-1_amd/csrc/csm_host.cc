@@ -1185,10 +1185,30 @@ int32_t csm_context_level_stats(csm_context* ctx, double* candidates, double* ba
 
 namespace csm {
 
+int EnsureValueTable(csm_context* ctx, float unknown, float lower, float upper, const float** out) {
+  DevBuf& t = ctx->value_tabs[std::make_tuple(unknown, lower, upper)];
+  if (!t.ptr) {
+    std::vector<float> tab(32768);
+    ConversionTable(unknown, lower, upper, tab.data());
+    int rc;
+    if ((rc = t.Reserve(sizeof(float) * 32768))) return rc;
+    if (hipMemcpy(t.ptr, tab.data(), sizeof(float) * 32768, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(t.ptr);
+      t.ptr = nullptr;
+      t.bytes = 0;
+      return CSM_EHIP;
+    }
+  }
+  *out = t.as<float>();
+  return CSM_OK;
+}
+
 int Fast2dCreate(csm_context* ctx, const csm_map_limits* limits, const uint16_t* host_cells,
                  const uint16_t* dev_cells, float min_cc, float max_cc,
-                 const csm_fast2d_options* options, csm_fast2d** out) {
+                 const csm_fast2d_options* options, csm_fast2d** out, const TsdfWeights* tsdf) {
   if (!ctx || !limits || (!host_cells && !dev_cells) || !options || !out) return CSM_EINVAL;
+  if (tsdf && ((!tsdf->host_cells && !tsdf->dev_cells) || !(tsdf->max_weight > 0.f)))
+    return CSM_EINVAL;
   if (options->branch_and_bound_depth < 1 || limits->num_x_cells < 1 ||
       limits->num_y_cells < 1 || !(limits->resolution > 0.) || !(min_cc < max_cc))
     return CSM_EINVAL;
@@ -1364,6 +1384,22 @@ int Fast2dCreate(csm_context* ctx, const csm_map_limits* limits, const uint16_t*
   if ((rc = ctx->pool.Take(sizeof(float) * n0, &m->cost))) return rc;
   CSM_HIP(LaunchCellsToProbability(dcells, ctx->f2_ctab.as<float>(),
                                    m->cost.as<float>(), n0, st));
+  if (tsdf) {
+    // TSDF2D::GetWeight (tsdf_2d.cc:81-87) for the TSDF match cost. The cells'
+    // staging buffer is free again: the stream runs the copies in order.
+    m->tsdf = true;
+    m->max_weight = tsdf->max_weight;
+    const float* wtab;
+    if ((rc = EnsureValueTable(ctx, 0.f, 0.f, tsdf->max_weight, &wtab))) return rc;
+    const uint16_t* dweights = tsdf->dev_cells;
+    if (!dweights) {
+      CSM_HIP(hipMemcpyAsync(ctx->f2_cells.ptr, tsdf->host_cells, sizeof(uint16_t) * nx * ny,
+                             hipMemcpyHostToDevice, st));
+      dweights = ctx->f2_cells.as<uint16_t>();
+    }
+    if ((rc = ctx->pool.Take(sizeof(float) * n0, &m->weight))) return rc;
+    CSM_HIP(LaunchCellsToProbability(dweights, wtab, m->weight.as<float>(), n0, st));
+  }
   // The cells are read from the caller's memory and the context's scratch
   // is reused by the next create: finish before returning.
   CSM_HIP(hipStreamSynchronize(st));
@@ -1411,16 +1447,57 @@ int csm_fast2d_create_from_grid(csm_context* ctx, const csm_probability_grid* gr
   return csm::Fast2dCreate(ctx, &limits, nullptr, cells, min_cc, max_cc, options, out);
 }
 
+int csm_fast2d_create_tsdf(csm_context* ctx, const csm_map_limits* limits,
+                           const uint16_t* tsd_cells, const uint16_t* weight_cells,
+                           float truncation_distance, float max_weight,
+                           const csm_fast2d_options* options, csm_fast2d** out) {
+  if (!tsd_cells || !weight_cells) return CSM_EINVAL;
+  if (!(truncation_distance > 0.f) || !(max_weight > 0.f)) return CSM_EINVAL;
+  // TSDF2D's Grid2D bounds (tsdf_2d.cc:24-27).
+  const csm::TsdfWeights w{weight_cells, nullptr, max_weight};
+  return csm::Fast2dCreate(ctx, limits, tsd_cells, nullptr, -truncation_distance,
+                           truncation_distance, options, out, &w);
+}
+
+// The pyramid and cost planes of a device-resident TSDF2D: no host copy.
+int csm_fast2d_create_from_tsdf_grid(csm_context* ctx, const csm_tsdf_grid* grid,
+                                     const csm_fast2d_options* options, csm_fast2d** out) {
+  if (!ctx || !grid || !options || !out) return CSM_EINVAL;
+  if (grid->ctx->device != ctx->device) return CSM_EINVAL;
+  csm_map_limits limits;
+  csm::TsdfWeights w{nullptr, nullptr, grid->max_weight};
+  const uint16_t* cells;
+  {
+    // As csm_fast2d_create_from_grid: ordered after the grid's stream work.
+    std::lock_guard<std::mutex> lock(grid->ctx->mu);
+    limits = grid->limits;
+    cells = grid->tsd.as<uint16_t>();
+    w.dev_cells = grid->weight.as<uint16_t>();
+    if (grid->ctx != ctx) {
+      if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+      hipEvent_t ev;
+      CSM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      const bool ok = hipEventRecord(ev, grid->ctx->stream) == hipSuccess &&
+                      hipStreamWaitEvent(ctx->stream, ev, 0) == hipSuccess;
+      (void)hipEventDestroy(ev);
+      if (!ok) return CSM_EHIP;
+    }
+  }
+  return csm::Fast2dCreate(ctx, &limits, nullptr, cells, -grid->truncation, grid->truncation,
+                           options, out, &w);
+}
+
 void csm_fast2d_destroy(csm_fast2d* m) {
   if (!m) return;
   (void)hipSetDevice(m->ctx->device);
   m->ctx->pool.Give(&m->pyramid);  // reused by the next create
   m->ctx->pool.Give(&m->cost);
+  if (m->weight.ptr) m->ctx->pool.Give(&m->weight);
   delete m;
 }
 
 int64_t csm_fast2d_device_bytes(const csm_fast2d* m) {
-  return m ? static_cast<int64_t>(m->pyramid.bytes + m->cost.bytes) : 0;
+  return m ? static_cast<int64_t>(m->pyramid.bytes + m->cost.bytes + m->weight.bytes) : 0;
 }
 
 int csm_fast2d_read_level(const csm_fast2d* m, int32_t level, uint8_t* out,

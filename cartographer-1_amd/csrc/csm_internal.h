@@ -301,6 +301,12 @@ struct csm_context {
   csm::DevBuf vf_points, vf_offsets, vf_keep, vf_counts;
   // CeresScanMatcher2D refinement scratch (ceres2d.hip).
   csm::DevBuf cr_items, cr_out, cr3_items, cr3_points, cr3_out;
+  // The cloud of a single csm_ceres2d_match_*grid call, and the value tables
+  // (ConversionTable(unknown, lower, upper), 32768 floats) the refinement
+  // kernels read device grids' uint16 cells and the TSDF handles' weights
+  // through (csm::EnsureValueTable).
+  csm::DevBuf cr_points;
+  std::map<std::tuple<float, float, float>, csm::DevBuf> value_tabs;
   // Device buffers of destroyed matchers and grids kept for reuse (BufPool),
   // csm_fast2d_create's scratch and the quantization / cost tables of the
   // last (min_cc, max_cc); the 3D value tables and the pinned staging of
@@ -343,6 +349,12 @@ struct csm_fast2d {
   csm::SubmapDesc desc{};
   csm::DevBuf pyramid;
   csm::DevBuf cost;  // float correspondence costs, x fastest (CeresScanMatcher2D refinement)
+  // Made from a TSDF2D: min_cc / max_cc are -/+ truncation, `cost` holds the
+  // TSD values through Grid2D's table (unknown -> +truncation) and `weight`
+  // the weights through ValueToWeight (unknown -> 0), for the TSDF match cost.
+  bool tsdf = false;
+  float max_weight = 0.f;
+  csm::DevBuf weight;
 };
 
 // A ProbabilityGrid on the device (insert2d.hip builds and updates it).
@@ -379,9 +391,20 @@ int Rt2dMatchTsdfGrid(csm_context* ctx, const csm_rt_options* o, const csm_tsdf_
                       csm_pose2d* pose);
 // csm_fast2d_create's body: cells from host memory (host_cells) or already on
 // the device and ordered on ctx->stream (dev_cells). Caller holds no lock.
+// With `tsdf` the cells are a TSDF2D's TSD values and the handle also keeps
+// the weight plane (host or device array, as the cells).
+struct TsdfWeights {
+  const uint16_t* host_cells;
+  const uint16_t* dev_cells;
+  float max_weight;
+};
 int Fast2dCreate(csm_context* ctx, const csm_map_limits* limits, const uint16_t* host_cells,
                  const uint16_t* dev_cells, float min_cc, float max_cc,
-                 const csm_fast2d_options* options, csm_fast2d** out);
+                 const csm_fast2d_options* options, csm_fast2d** out,
+                 const TsdfWeights* tsdf = nullptr);
+// ValueConversionTables::GetConversionTable(unknown, lower, upper) on ctx's
+// device, made on first use and kept with the context (caller holds ctx->mu).
+int EnsureValueTable(csm_context* ctx, float unknown, float lower, float upper, const float** out);
 // csm_rt2d_match on a device grid (rt2d.hip).
 int Rt2dMatchGrid(csm_context* ctx, const csm_rt_options* o, const csm_probability_grid* grid,
                   const csm_pose2d* initial, const float* xyz, int32_t n, double* score,

@@ -10,11 +10,21 @@ from typing import List, Optional, Union
 
 import numpy as np
 
-from . import Context, DeviceProbabilityGrid, DeviceTSDF2D, TSDFInserterOptions, default_context
+from . import (Context, DeviceProbabilityGrid, DeviceTSDF2D, FastCorrelativeScanMatcher2D,
+               FastCorrelativeScanMatcherOptions2D, TSDFInserterOptions, default_context)
 
 # proto::GridOptions2D::GridType (grid_2d_options.proto:20-24).
 PROBABILITY_GRID = "PROBABILITY_GRID"
 TSDF = "TSDF"
+
+
+def FastMatcherFor(grid: Union[DeviceProbabilityGrid, DeviceTSDF2D],
+                   options: FastCorrelativeScanMatcherOptions2D) -> FastCorrelativeScanMatcher2D:
+    """FastCorrelativeScanMatcher2D(grid, options) for a device-resident grid,
+    on the grid's context and without a host copy (submap_2d.h's
+    FastMatcherFor): a DeviceTSDF2D gives a TSDF matcher, which
+    ceres_refine_batch refines with the TSDF match cost."""
+    return FastCorrelativeScanMatcher2D(grid, options, grid.context)
 
 
 @dataclass

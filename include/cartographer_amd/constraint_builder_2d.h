@@ -14,7 +14,10 @@
 // pending). Accepted matches are then refined as one batch by the
 // CeresScanMatcher2D restatement of ComputeConstraint (:245-249;
 // csm_ceres2d_refine_batch, parity with Ceres unpinned) unless
-// options.refine_with_ceres is off.
+// options.refine_with_ceres is off. The cost follows the submap's grid type as
+// ceres_scan_matcher_2d.cc:74-91 does: a TSDF view with its weights makes a
+// TSDF matcher, whose items are refined with TSDFMatchCostFunction2D; one
+// flush may mix TSDF and probability-grid submaps.
 //
 // Lifetimes: the Submap2DView and PointCloud passed to MaybeAdd* must stay
 // valid (and unchanged) until the flush that searches the pair — the next

@@ -105,9 +105,18 @@ class FastCorrelativeScanMatcher2D {
     const csm_fast2d_options o{options.linear_search_window, options.angular_search_window,
                                options.branch_and_bound_depth, 0};
     csm_fast2d* h = nullptr;
-    CheckOk(csm_fast2d_create(context ? context : ThreadContext(), &limits, grid.cells,
-                              grid.min_correspondence_cost, grid.max_correspondence_cost, &o, &h),
-            "FastCorrelativeScanMatcher2D");
+    // A TSDF view with its weights makes a TSDF handle: the same pyramid, plus
+    // the planes TSDFMatchCostFunction2D reads in the Ceres refinement
+    // (ceres_scan_matcher_2d.cc:74-91 switches on GetGridType()).
+    if (grid.grid_type == Grid2DView::GridType::TSDF && grid.weight_cells != nullptr)
+      CheckOk(csm_fast2d_create_tsdf(context ? context : ThreadContext(), &limits, grid.cells,
+                                     grid.weight_cells, grid.max_correspondence_cost,
+                                     grid.max_weight, &o, &h),
+              "FastCorrelativeScanMatcher2D");
+    else
+      CheckOk(csm_fast2d_create(context ? context : ThreadContext(), &limits, grid.cells,
+                                grid.min_correspondence_cost, grid.max_correspondence_cost, &o, &h),
+              "FastCorrelativeScanMatcher2D");
     handle_ = h;
   }
   ~FastCorrelativeScanMatcher2D() { csm_fast2d_destroy(handle_); }
@@ -144,7 +153,67 @@ class FastCorrelativeScanMatcher2D {
   csm_fast2d* handle_ = nullptr;
 };
 
-class TSDF2D;  // the device-resident TSDF (submap_2d.h)
+class ProbabilityGrid;  // the device-resident grids (submap_2d.h)
+class TSDF2D;
+
+// proto::CeresScanMatcherOptions2D (trajectory_builder_2d.lua:45-54 defaults).
+struct CeresScanMatcherOptions2D {
+  double occupied_space_weight = 1.;
+  double translation_weight = 10.;
+  double rotation_weight = 40.;
+  int max_num_iterations = 20;          // ceres_solver_options
+  bool use_nonmonotonic_steps = false;  // ceres_solver_options
+};
+
+// ceres_scan_matcher_2d.h:41-66. Match() fills *pose_estimate; the reference's
+// ceres::Solver::Summary is not reproduced (iterations, if asked for, are).
+class CeresScanMatcher2D {
+ public:
+  explicit CeresScanMatcher2D(const CeresScanMatcherOptions2D& o)
+      : options_{o.occupied_space_weight, o.translation_weight, o.rotation_weight,
+                 o.max_num_iterations, o.use_nonmonotonic_steps ? 1 : 0} {}
+
+  // On a host grid view: a one-level matcher handle carries the grid to the
+  // device (a TSDF view: with its weights), then one refinement item.
+  void Match(const double target_translation[2], const Rigid2d& initial_pose_estimate,
+             const PointCloud& point_cloud, const Grid2DView& grid, Rigid2d* pose_estimate,
+             int* iterations = nullptr) const {
+    csm_context* ctx = ThreadContext();
+    const FastCorrelativeScanMatcher2D matcher(
+        grid, FastCorrelativeScanMatcherOptions2D{0.1, 0.1, 1}, ctx);
+    const int64_t offsets[2] = {0, static_cast<int64_t>(point_cloud.size())};
+    csm_scan_set* scans = nullptr;
+    CheckOk(csm_scan_set_create(ctx, point_cloud.xyz.data(), offsets, 1, &scans),
+            "CeresScanMatcher2D::Match");
+    csm_fast2d* handle = matcher.handle();
+    const csm_refine2d item{0, 0,
+                            {initial_pose_estimate.x, initial_pose_estimate.y,
+                             initial_pose_estimate.theta},
+                            target_translation[0], target_translation[1]};
+    csm_pose2d out{};
+    int32_t iters = 0;
+    const int rc = csm_ceres2d_refine_batch(ctx, &handle, 1, scans, &item, 1, &options_, &out, &iters);
+    csm_scan_set_destroy(scans);
+    CheckOk(rc, "CeresScanMatcher2D::Match");
+    *pose_estimate = Rigid2d{out.x, out.y, out.theta};
+    if (iterations) *iterations = iters;
+  }
+
+  // On the device-resident grids, read where they live (defined in
+  // submap_2d.h, which has the types): what LocalTrajectoryBuilder2D::ScanMatch
+  // runs against the active submap after the real-time matcher.
+  void Match(const double target_translation[2], const Rigid2d& initial_pose_estimate,
+             const PointCloud& point_cloud, const ProbabilityGrid& grid, Rigid2d* pose_estimate,
+             int* iterations = nullptr) const;
+  void Match(const double target_translation[2], const Rigid2d& initial_pose_estimate,
+             const PointCloud& point_cloud, const TSDF2D& grid, Rigid2d* pose_estimate,
+             int* iterations = nullptr) const;
+
+  const csm_ceres2d_options& options() const { return options_; }
+
+ private:
+  csm_ceres2d_options options_;
+};
 
 // real_time_correlative_scan_matcher_2d.h:53-85
 class RealTimeCorrelativeScanMatcher2D {

@@ -187,6 +187,53 @@ inline double RealTimeCorrelativeScanMatcher2D::Match(const Rigid2d& initial_pos
   return score;
 }
 
+// FastCorrelativeScanMatcher2D(grid, options) for a device TSDF: a TSDF handle
+// (the pyramid from the TSD cells, the weights for the Ceres refinement),
+// without a host copy. Used and destroyed as the probability grid's.
+inline csm_fast2d* FastMatcherFor(const TSDF2D& grid,
+                                  const FastCorrelativeScanMatcherOptions2D& options) {
+  const csm_fast2d_options o{options.linear_search_window, options.angular_search_window,
+                             options.branch_and_bound_depth, 0};
+  csm_fast2d* h = nullptr;
+  CheckOk(csm_fast2d_create_from_tsdf_grid(grid.context(), grid.handle(), &o, &h),
+          "FastMatcherFor");
+  return h;
+}
+
+// CeresScanMatcher2D::Match on the device grids (ceres_scan_matcher_2d.cc:
+// 64-105); declared in scan_matching.h.
+inline void CeresScanMatcher2D::Match(const double target_translation[2],
+                                      const Rigid2d& initial_pose_estimate,
+                                      const PointCloud& point_cloud, const ProbabilityGrid& grid,
+                                      Rigid2d* pose_estimate, int* iterations) const {
+  const csm_pose2d init{initial_pose_estimate.x, initial_pose_estimate.y,
+                        initial_pose_estimate.theta};
+  csm_pose2d out{};
+  int32_t iters = 0;
+  CheckOk(csm_ceres2d_match_grid(grid.context(), &options_, grid.handle(), target_translation,
+                                 &init, point_cloud.xyz.data(),
+                                 static_cast<int32_t>(point_cloud.size()), &out, &iters),
+          "CeresScanMatcher2D::Match");
+  *pose_estimate = Rigid2d{out.x, out.y, out.theta};
+  if (iterations) *iterations = iters;
+}
+
+inline void CeresScanMatcher2D::Match(const double target_translation[2],
+                                      const Rigid2d& initial_pose_estimate,
+                                      const PointCloud& point_cloud, const TSDF2D& grid,
+                                      Rigid2d* pose_estimate, int* iterations) const {
+  const csm_pose2d init{initial_pose_estimate.x, initial_pose_estimate.y,
+                        initial_pose_estimate.theta};
+  csm_pose2d out{};
+  int32_t iters = 0;
+  CheckOk(csm_ceres2d_match_tsdf_grid(grid.context(), &options_, grid.handle(),
+                                      target_translation, &init, point_cloud.xyz.data(),
+                                      static_cast<int32_t>(point_cloud.size()), &out, &iters),
+          "CeresScanMatcher2D::Match");
+  *pose_estimate = Rigid2d{out.x, out.y, out.theta};
+  if (iterations) *iterations = iters;
+}
+
 // tsdf_range_data_inserter_2d.h:33-55 (the reference ignores the misses).
 class TSDFRangeDataInserter2D {
  public:

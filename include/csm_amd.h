@@ -539,6 +539,26 @@ int csm_ceres2d_refine_batch(csm_context* ctx, csm_fast2d* const* submaps, int32
                              const csm_ceres2d_options* options, csm_pose2d* out,
                              int32_t* iterations);
 
+/* The submaps may be TSDF handles (csm_fast2d_create_tsdf,
+ * csm_fast2d_create_from_tsdf_grid), and one call may mix both kinds: a TSDF
+ * item's first residual block is TSDFMatchCostFunction2D
+ * (tsdf_match_cost_function_2d.cc:39-66 over interpolated_tsdf_2d.h:41-121;
+ * ceres_scan_matcher_2d.cc:83-90) instead of the occupied-space cost. That
+ * functor fails to evaluate where no point reads a weighted cell: at the
+ * initial pose the item returns its initial pose and 0 iterations (Ceres ends
+ * with FAILURE and CeresScanMatcher2D::Match ignores the summary); at a
+ * candidate the step counts as one of infinite cost and is rejected. */
+
+/* Test-visible, like csm_fast2d_read_level: TSDFMatchCostFunction2D alone (no
+ * delta rows) on a TSDF handle of ctx, through the device functions the
+ * refinement uses. residuals[n] and the row-major n x 3 Jacobian by
+ * (x, y, theta) as AutoDiff gives it; *valid is 0, and the outputs are zero,
+ * when the functor returns false. A probability handle: CSM_EINVAL. */
+int csm_ceres2d_tsdf_evaluate(csm_context* ctx, const csm_fast2d* tsdf_handle,
+                              const float* points_xyz, int32_t n, double scaling_factor,
+                              const double pose[3], double* residuals, double* jacobian,
+                              int32_t* valid);
+
 /* CeresScanMatcher3D refinement (ConstraintBuilder3D::ComputeConstraint,
  * constraint_builder_3d.cc:264-275; ceres_scan_matcher_3d.cc:84-160): the
  * match pose is refined against the submap's high- and low-resolution
@@ -756,12 +776,46 @@ int csm_tsdf_grid_insert_batch(csm_context* ctx, csm_tsdf_grid* const* grids, in
  * crops to 1 x 1 at offset (0, 0). Later inserts return CSM_EINVAL. */
 int csm_tsdf_grid_finish(csm_tsdf_grid* grid);
 
+/* csm_fast2d_create for a TSDF2D (GridType::TSDF): the
+ * PrecomputationGridStack2D is built from the TSD cells exactly as
+ * csm_fast2d_create builds it, with Grid2D's bounds of a TSDF2D, min = -trunc
+ * and max = +trunc (tsdf_2d.cc:24-27; fast_correlative_scan_matcher_2d.cc:
+ * 97-98, :105-160). The handle also keeps the weights, for the TSDF match cost
+ * of csm_ceres2d_refine_batch. csm_fast2d_match, _match_full_submap,
+ * _match_batch and _read_level work on it unchanged. Arrays as for
+ * csm_rt2d_match_tsdf, copied. Errors as for csm_fast2d_create; one array
+ * without the other, or a truncation distance or max weight <= 0: CSM_EINVAL. */
+int csm_fast2d_create_tsdf(csm_context* ctx, const csm_map_limits* limits,
+                           const uint16_t* tsd_cells, const uint16_t* weight_cells,
+                           float truncation_distance, float max_weight,
+                           const csm_fast2d_options* options, csm_fast2d** out);
+/* The same from a device-resident TSDF2D, without a host copy. The grid may be
+ * inserted into or destroyed afterwards, as for csm_fast2d_create_from_grid. */
+int csm_fast2d_create_from_tsdf_grid(csm_context* ctx, const csm_tsdf_grid* grid,
+                                     const csm_fast2d_options* options, csm_fast2d** out);
+
 /* csm_rt2d_match_tsdf for a device-resident TSDF2D of ctx
  * (real_time_correlative_scan_matcher_2d.cc:38-59, :117-149). The converted
  * (term, weight) grid is cached per (grid id, generation, padding). */
 int csm_rt2d_match_tsdf_grid(csm_context* ctx, const csm_rt_options* options,
                              const csm_tsdf_grid* grid, const csm_pose2d* initial,
                              const float* points_xyz, int32_t n, double* score, csm_pose2d* pose);
+
+/* CeresScanMatcher2D::Match(target_translation, initial, cloud, grid, &pose)
+ * (ceres_scan_matcher_2d.cc:64-105) on a device-resident grid of ctx, as
+ * LocalTrajectoryBuilder2D::ScanMatch calls it on the active submap
+ * (local_trajectory_builder_2d.cc:63-97): no pyramid is built and no plane is
+ * converted, the kernel reads the uint16 cells through the value tables.
+ * Validation as for csm_ceres2d_refine_batch; n >= 1 finite points.
+ * iterations_out may be NULL. summary.final_cost is not returned. */
+int csm_ceres2d_match_grid(csm_context* ctx, const csm_ceres2d_options* options,
+                           const csm_probability_grid* grid, const double target_xy[2],
+                           const csm_pose2d* initial, const float* points_xyz, int32_t n,
+                           csm_pose2d* pose_out, int32_t* iterations_out);
+int csm_ceres2d_match_tsdf_grid(csm_context* ctx, const csm_ceres2d_options* options,
+                                const csm_tsdf_grid* grid, const double target_xy[2],
+                                const csm_pose2d* initial, const float* points_xyz, int32_t n,
+                                csm_pose2d* pose_out, int32_t* iterations_out);
 
 /* Test-visible and host-only, like csm_inserter2d_lookup_table: the per-ray
  * plan of one Insert that the device consumes. order[k] is the index of the
