@@ -193,6 +193,12 @@ class CeresOptions3D(C.Structure):
                               int(bool(use_nonmonotonic_steps)))
 
 
+class CeresIntensityOptions3D(C.Structure):
+    """csm_ceres3d_intensity_options (proto::IntensityCostFunctionOptions)."""
+    _fields_ = [("weight", C.c_double), ("huber_scale", C.c_double),
+                ("intensity_threshold", C.c_double)]
+
+
 class Refine3D(C.Structure):
     _fields_ = [("high_grid", C.c_int32), ("low_grid", C.c_int32), ("node", C.c_int32),
                 ("initial", Pose3D), ("target", C.c_double * 3)]
@@ -367,6 +373,15 @@ _SIGNATURES = {
                                            C.POINTER(Node3D), C.c_int32, C.POINTER(Refine3D),
                                            C.c_int64, C.POINTER(CeresOptions3D),
                                            C.POINTER(Pose3D), C.POINTER(C.c_int32)]),
+    "csm_ceres3d_refine_intensity_batch": (C.c_int, [
+        C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+        C.POINTER(Node3D), C.POINTER(C.POINTER(C.c_float)), C.c_int32, C.POINTER(Refine3D),
+        C.POINTER(C.c_int32), C.c_int64, C.POINTER(CeresOptions3D),
+        C.POINTER(CeresIntensityOptions3D), C.POINTER(Pose3D), C.POINTER(C.c_int32)]),
+    "csm_ceres3d_intensity_evaluate": (C.c_int, [C.c_void_p, C.POINTER(C.c_float),
+                                                 C.POINTER(C.c_float), C.c_int32,
+                                                 C.POINTER(C.c_double), C.c_double, C.c_float,
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "csm_grid2d_cropped_limits": (C.c_int, [C.POINTER(MapLimits), C.POINTER(C.c_uint16),
                                             C.POINTER(C.c_int32), C.POINTER(MapLimits)]),
     "csm_grid2d_crop": (C.c_int, [C.POINTER(MapLimits), C.POINTER(C.c_uint16),
@@ -444,6 +459,25 @@ _SIGNATURES = {
                                                C.POINTER(C.c_float), C.c_int32,
                                                C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "csm_hybrid_grid_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.c_int64]),
+    "csm_intensity_grid_create": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_void_p)]),
+    "csm_intensity_grid_destroy": (None, [C.c_void_p]),
+    "csm_intensity_grid_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32)]),
+    "csm_intensity_grid_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                          C.c_int64]),
+    "csm_intensity_grid_get_intensity": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
+                                                   C.POINTER(C.c_float)]),
+    "csm_intensity_grid_device_bytes": (C.c_int64, [C.c_void_p]),
+    "csm_hybrid_grid_insert_intensities": (C.c_int, [C.c_void_p, C.c_void_p,
+                                                     C.POINTER(Inserter3DOptions), C.c_float,
+                                                     C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                     C.POINTER(C.c_float), C.c_int32]),
+    "csm_hybrid_grid_insert_intensities_batch": (C.c_int, [
+        C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+        C.POINTER(Inserter3DOptions), C.c_float, C.c_int32, C.POINTER(C.c_float),
+        C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_float)), C.c_int32,
+        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+        C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "csm_hybrid_grid_insert_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int64)]),
     "csm_inserter3d_lookup_table": (C.c_int, [C.c_float, C.POINTER(C.c_uint16)]),
@@ -1605,8 +1639,10 @@ class SyntheticWorld2D:
 
 # 3D matchers (RealTimeCorrelativeScanMatcher3D, FastCorrelativeScanMatcher3D).
 from .matching3d import (FastCorrelativeScanMatcher3D, FastCorrelativeScanMatcherOptions3D,  # noqa: E402,F401
-                         HybridGrid, NodeData3D, NodeSet3D, PAIR3_DTYPE, RESULT3_DTYPE,
-                         RealTimeCorrelativeScanMatcher3D, SyntheticWorld3D, ceres_refine_batch_3d,
+                         HybridGrid, IntensityHybridGrid, NodeData3D, NodeSet3D, PAIR3_DTYPE,
+                         RESULT3_DTYPE,
+                         RealTimeCorrelativeScanMatcher3D, SyntheticWorld3D,
+                         ceres_intensity_evaluate_3d, ceres_refine_batch_3d,
                          inserter3d_lookup_table, make_pairs_3d, match_batch_3d, rotate_histogram)
 
 
@@ -1826,5 +1862,7 @@ def synchronize(context: "Context"):
 from .submap_2d import (ActiveSubmaps2D, FastMatcherFor, ProbabilityGridRangeDataInserter2D,  # noqa: E402,F401
                         ProbabilityGridRangeDataInserterOptions2D, RangeData, Submap2D,
                         TSDFRangeDataInserter2D, TSDFRangeDataInserterOptions2D)
-from .submap_3d import (ActiveSubmaps3D, RangeDataInserter3D,  # noqa: E402,F401
-                        RangeDataInserterOptions3D, Submap3D, SubmapsOptions3D)
+from .submap_3d import (ActiveSubmaps3D, CeresScanMatcher3D,  # noqa: E402,F401
+                        CeresScanMatcherOptions3D, IntensityCostFunctionOptions,
+                        RangeDataInserter3D, RangeDataInserterOptions3D, Submap3D,
+                        SubmapsOptions3D)

@@ -14,11 +14,25 @@
 // J^T J (6 x 6) and J^T r in double and one lane takes a Levenberg-Marquardt
 // trust-region step with Ceres' defaults, as oracle/ceres3d.cc restates
 // (parity with Ceres unpinned).
+//
+// With an intensity grid (LocalTrajectoryBuilder3D::ScanMatch,
+// local_trajectory_builder_3d.cc:488-501; ceres_scan_matcher_3d.cc:126-142)
+// the high-resolution cloud also feeds IntensityCostFunction3D
+// (intensity_cost_function_3d.h:67-85) under ceres::HuberLoss: in the same pass
+// over the points its sum of squares, J^T J and J^T r go into a second set of
+// sums, and after the block reduction 0.5 rho(S) joins the cost and rho' J^T J,
+// rho' J^T r the normal equations. That is Ceres' Corrector for a loss with
+// rho'' <= 0, which Huber's is in both regimes: residuals and Jacobian scaled
+// by sqrt(rho'). The Huber and Corrector rules are written from memory of
+// Ceres 1.13 and are unpinned like the LM loop. The second set is compiled out
+// of the kernel for items without an intensity grid (kIntens), whose
+// arithmetic is unchanged.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "ceres_lm.h"
@@ -49,6 +63,37 @@ struct Refine3Opts {
   int nonmonotonic;  // ceres_solver_options.use_nonmonotonic_steps
 };
 
+// IntensityHybridGrid on the device (csm_intensity_grid).
+struct IntensView3 {
+  const float* sum;
+  const int32_t* count;
+  Brick3 b;
+  float res;
+};
+
+// The intensity block of one item: IntensityCostFunction3D's arguments and the
+// Huber scale.
+struct IntensBlock3 {
+  IntensView3 g;
+  int64_t offset;  // of the high-resolution cloud's intensities in the values buffer
+  double scale;    // weight / sqrt(N)
+  double huber;
+  float threshold;
+};
+
+// InterpolatedGrid::GetValue for the intensity grid: GetIntensity
+// (hybrid_grid.h:563-570), 0 for a cell that no return fell into.
+__device__ __forceinline__ double Prob(const IntensView3& g, int x, int y, int z) {
+  const int lx = x - g.b.ox, ly = y - g.b.oy, lz = z - g.b.oz;
+  if (static_cast<unsigned>(lx) >= static_cast<unsigned>(g.b.nx) ||
+      static_cast<unsigned>(ly) >= static_cast<unsigned>(g.b.ny) ||
+      static_cast<unsigned>(lz) >= static_cast<unsigned>(g.b.nz))
+    return 0.;
+  const int64_t i = (static_cast<int64_t>(lz) * g.b.ny + ly) * g.b.nx + lx;
+  const int32_t c = g.count[i];
+  return c == 0 ? 0. : static_cast<double>(__fdiv_rn(g.sum[i], static_cast<float>(c)));
+}
+
 __device__ __forceinline__ double Prob(const GridView3& g, int x, int y, int z) {
   const int lx = x - g.b.ox, ly = y - g.b.oy, lz = z - g.b.oz;
   if (static_cast<unsigned>(lx) >= static_cast<unsigned>(g.b.nx) ||
@@ -71,8 +116,10 @@ struct StepF {
   __device__ double db() const { return -2. * ttt + 3. * tt; }
 };
 
-// InterpolatedGrid::GetInterpolatedValue and its gradient.
-__device__ double Interpolate(const GridView3& g, double x, double y, double z, double* grad) {
+// InterpolatedGrid::GetInterpolatedValue and its gradient; View is the grid
+// (GridView3: probabilities, IntensView3: mean intensities).
+template <typename View>
+__device__ double Interpolate(const View& g, double x, double y, double z, double* grad) {
   const float res = g.res;
   const float fx = static_cast<float>(x), fy = static_cast<float>(y), fz = static_cast<float>(z);
   float cx = __fmul_rn(static_cast<float>(CellF(fx, res)), res);
@@ -164,12 +211,51 @@ __device__ __forceinline__ void Accumulate(double* acc, double r, const double* 
   for (int a = 0; a < 6; ++a) acc[22 + a] += j[a] * r;
 }
 
+// IntensityCostFunction3D's residual i and its tangent Jacobian row (zero
+// above the threshold) at the transformed point w; Jq is Rotate's derivative
+// and L the parameterization's Jacobian.
 template <bool kJac>
+__device__ void IntensityRow(const IntensBlock3& b, float intensity, const double* w,
+                             const double* Jq, const double* L, double* r, double* j) {
+  *r = 0.;
+  if (intensity > b.threshold) return;
+  double grad[3];
+  const double val = Interpolate(b.g, w[0], w[1], w[2], kJac ? grad : nullptr);
+  *r = b.scale * (val - static_cast<double>(intensity));
+  if (kJac) {
+    double dq[4] = {0., 0., 0., 0.};
+    for (int c = 0; c < 4; ++c)
+      for (int a = 0; a < 3; ++a) dq[c] += b.scale * grad[a] * Jq[4 * a + c];
+    for (int a = 0; a < 3; ++a) j[a] = b.scale * grad[a];
+    for (int c = 0; c < 3; ++c) {
+      double s = 0.;
+      for (int m = 0; m < 4; ++m) s += dq[m] * L[3 * m + c];
+      j[3 + c] = s;
+    }
+  }
+}
+
+// ceres::HuberLoss(a) at s: rho and rho' (loss_function.cc); rho'' <= 0.
+__device__ __forceinline__ void Huber(double a, double s, double* rho, double* rho1) {
+  if (s > a * a) {
+    const double r = sqrt(s);
+    *rho = 2. * a * r - a * a;
+    *rho1 = fmax(2.2250738585072014e-308, a / r);  // std::numeric_limits<double>::min()
+  } else {
+    *rho = s;
+    *rho1 = 1.;
+  }
+}
+
+template <bool kJac, bool kIntens>
 __device__ void Pass3(const Refine3Desc& d, const float* pts, const double* scale,
                       const Refine3Opts& o, const double* t, const double* q,
-                      const double* target_inv, double* out, double (*red)[kSums]) {
-  double acc[kSums];
+                      const double* target_inv, double* out, double (*red)[kSums],
+                      const IntensBlock3* ib, const float* values) {
+  double acc[kSums], acc2[kIntens ? kSums : 1];
   for (int k = 0; k < kSums; ++k) acc[k] = 0.;
+  if (kIntens)
+    for (int k = 0; k < kSums; ++k) acc2[k] = 0.;
   // QuaternionParameterization::ComputeJacobian (4 x 3).
   const double L[12] = {-q[1], -q[2], -q[3], q[0], q[3], -q[2], -q[3], q[0], q[1], q[2], -q[1], q[0]};
   const int n0 = d.n[0], total = d.n[0] + d.n[1] + 6;
@@ -183,6 +269,11 @@ __device__ void Pass3(const Refine3Desc& d, const float* pts, const double* scal
       double w[3], Jq[12], grad[3];
       Rotate(q, v, w, kJac ? Jq : nullptr);
       for (int a = 0; a < 3; ++a) w[a] += t[a];
+      if (kIntens && k == 0) {
+        double r2, j2[6] = {0., 0., 0., 0., 0., 0.};
+        IntensityRow<kJac>(*ib, values[ib->offset + i], w, Jq, L, &r2, j2);
+        Accumulate(acc2, r2, j2, kJac);
+      }
       const double val = Interpolate(d.grid[k], w[0], w[1], w[2], kJac ? grad : nullptr);
       r = scale[k] * (1. - val);
       if (kJac) {
@@ -219,6 +310,13 @@ __device__ void Pass3(const Refine3Desc& d, const float* pts, const double* scal
   }
   BlockSum(acc, red);
   for (int k = 0; k < kSums; ++k) out[k] = acc[k];
+  if (kIntens) {
+    BlockSum(acc2, red);
+    double rho, rho1;
+    Huber(ib->huber, acc2[0], &rho, &rho1);
+    out[0] += rho;
+    for (int k = 1; k < kSums; ++k) out[k] += rho1 * acc2[k];
+  }
 }
 
 __device__ bool Solve6(double* M, double* b, double* out) {
@@ -262,17 +360,22 @@ __device__ void Unpack(const double* S, double* Au, double* gu) {
 
 // Ceres 1.13 TrustRegionMinimizer::Minimize as in ceres2d.hip: every thread
 // runs the 6-dimensional step logic on the same block-reduced sums.
+template <bool kIntens>
 __global__ void __launch_bounds__(kR3Threads)
 ceres3d_refine(const Refine3Desc* __restrict__ items, const float* __restrict__ points,
-               Refine3Opts o, double* __restrict__ out, int32_t* __restrict__ out_iters) {
+               Refine3Opts o, double* __restrict__ out, int32_t* __restrict__ out_iters,
+               const IntensBlock3* __restrict__ blocks, const float* __restrict__ values) {
   __shared__ double red[kR3Threads / 64][kSums];
   const Refine3Desc d = items[blockIdx.x];
+  IntensBlock3 block;
+  if (kIntens) block = blocks[blockIdx.x];
+  const IntensBlock3* ib = kIntens ? &block : nullptr;
   const double scale[2] = {o.w0 / sqrt(static_cast<double>(d.n[0])),
                            o.w1 / sqrt(static_cast<double>(d.n[1]))};
   const double target_inv[4] = {d.q[0], -d.q[1], -d.q[2], -d.q[3]};
   double t[3] = {d.t[0], d.t[1], d.t[2]}, q[4] = {d.q[0], d.q[1], d.q[2], d.q[3]};
   double S[kSums], T[kSums];
-  Pass3<true>(d, points, scale, o, t, q, target_inv, S, red);
+  Pass3<true, kIntens>(d, points, scale, o, t, q, target_inv, S, red, ib, values);
   double cost = 0.5 * S[0];
   double Au[36], gu[6], js[6];
   Unpack(S, Au, gu);
@@ -328,7 +431,7 @@ ceres3d_refine(const Refine3Desc* __restrict__ items, const float* __restrict__ 
       } else {
         for (int a = 0; a < 4; ++a) qn[a] = q[a];
       }
-      Pass3<false>(d, points, scale, o, tn, qn, target_inv, T, red);
+      Pass3<false, kIntens>(d, points, scale, o, tn, qn, target_inv, T, red, ib, values);
       const double new_cost = 0.5 * T[0];
       if (sqrt(step_norm) <= (sqrt(x_norm) + 1e-8) * 1e-8) break;  // parameter tolerance
       if (fabs(cost - new_cost) <= 1e-6 * cost) break;             // function tolerance
@@ -336,7 +439,7 @@ ceres3d_refine(const Refine3Desc* __restrict__ items, const float* __restrict__ 
       if (quality > 1e-3) {
         for (int a = 0; a < 3; ++a) t[a] = tn[a];
         for (int a = 0; a < 4; ++a) q[a] = qn[a];
-        Pass3<true>(d, points, scale, o, t, q, target_inv, S, red);
+        Pass3<true, kIntens>(d, points, scale, o, t, q, target_inv, S, red, ib, values);
         cost = 0.5 * S[0];
         Unpack(S, Au, gu);
         lm.Accepted(quality);
@@ -393,17 +496,42 @@ int GridLookup(const csm_hybrid_grid* g, const In* in, int64_t n, Out* out, K ke
   return CSM_OK;
 }
 
-}  // namespace
-}  // namespace csm
+// csm_ceres3d_intensity_evaluate: IntensityCostFunction3D alone, one thread
+// per point, through IntensityRow.
+__global__ void ceres3d_intensity_eval(IntensBlock3 block, const float* __restrict__ points,
+                                       const float* __restrict__ values, int32_t n,
+                                       const double* __restrict__ pose,
+                                       double* __restrict__ residuals,
+                                       double* __restrict__ jacobian) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* t = pose;
+  const double* q = pose + 3;
+  const double L[12] = {-q[1], -q[2], -q[3], q[0], q[3], -q[2], -q[3], q[0], q[1], q[2], -q[1], q[0]};
+  const double v[3] = {static_cast<double>(points[3 * i]), static_cast<double>(points[3 * i + 1]),
+                       static_cast<double>(points[3 * i + 2])};
+  double w[3], Jq[12], r, j[6] = {0., 0., 0., 0., 0., 0.};
+  Rotate(q, v, w, Jq);
+  for (int a = 0; a < 3; ++a) w[a] += t[a];
+  IntensityRow<true>(block, values[i], w, Jq, L, &r, j);
+  residuals[i] = r;
+  for (int a = 0; a < 6; ++a) jacobian[6 * i + a] = j[a];
+}
 
-extern "C" {
+// The intensity half of csm_ceres3d_refine_intensity_batch; null for
+// csm_ceres3d_refine_batch.
+struct Intens3Args {
+  const csm_intensity_grid* const* grids;
+  int32_t num_grids;
+  const float* const* node_intensities;  // per node, of its high-resolution cloud
+  const int32_t* grid_of_item;           // -1: none
+  const csm_ceres3d_intensity_options* options;
+};
 
-int csm_ceres3d_refine_batch(csm_context* ctx, const csm_hybrid_grid* const* grids,
-                             int32_t num_grids, const csm_node3d* nodes, int32_t num_nodes,
-                             const csm_refine3d* items, int64_t n,
-                             const csm_ceres3d_options* options, csm_pose3d* out,
-                             int32_t* iterations) {
-  using namespace csm;
+int Refine3Batch(csm_context* ctx, const csm_hybrid_grid* const* grids, int32_t num_grids,
+                 const csm_node3d* nodes, int32_t num_nodes, const csm_refine3d* items, int64_t n,
+                 const csm_ceres3d_options* options, csm_pose3d* out, int32_t* iterations,
+                 const Intens3Args* ia) {
   if (!ctx || !options || (n > 0 && (!items || !out || !grids || !nodes))) return CSM_EINVAL;
   if (n == 0) return CSM_OK;
   if (!(options->occupied_space_weight_0 > 0.) || !(options->occupied_space_weight_1 > 0.) ||
@@ -411,10 +539,30 @@ int csm_ceres3d_refine_batch(csm_context* ctx, const csm_hybrid_grid* const* gri
       options->max_num_iterations < 0)
     return CSM_EINVAL;  // CHECK_GTs of ceres_scan_matcher_3d.cc:106-156
   if (n > 0x7fffffff) return CSM_ERANGE;
-  // Node clouds once each, high then low resolution.
+  // Items with an intensity grid run the kernel with the intensity block, after
+  // the others: item i is descriptor slot[i].
+  std::vector<int64_t> slot(static_cast<size_t>(n));
+  int64_t num_plain = n;
+  if (ia && ia->grid_of_item) {
+    num_plain = 0;
+    for (int64_t i = 0; i < n; ++i) num_plain += ia->grid_of_item[i] < 0;
+  }
+  const int64_t num_intens = n - num_plain;
+  if (num_intens > 0) {
+    const csm_ceres3d_intensity_options* io = ia->options;
+    // CHECK_GTs of ceres_scan_matcher_3d.cc:127-130.
+    if (!io || !(io->weight > 0.) || !(io->huber_scale > 0.) || !(io->intensity_threshold > 0.))
+      return CSM_EINVAL;
+  }
+  for (int64_t i = 0, p = 0, q = num_plain; i < n; ++i)
+    slot[i] = num_intens > 0 && ia->grid_of_item[i] >= 0 ? q++ : p++;
+  // Node clouds once each, high then low resolution; the high-resolution
+  // cloud's intensities once each.
   std::vector<int64_t> off(2 * static_cast<size_t>(num_nodes), -1);
-  std::vector<float> pts;
+  std::vector<int64_t> voff(static_cast<size_t>(num_nodes), -1);
+  std::vector<float> pts, vals;
   std::vector<Refine3Desc> desc(static_cast<size_t>(n));
+  std::vector<IntensBlock3> blocks(static_cast<size_t>(num_intens));
   for (int64_t i = 0; i < n; ++i) {
     const csm_refine3d& it = items[i];
     if (it.high_grid < 0 || it.high_grid >= num_grids || it.low_grid < 0 ||
@@ -431,7 +579,7 @@ int csm_ceres3d_refine_batch(csm_context* ctx, const csm_hybrid_grid* const* gri
       off[2 * it.node + 1] = static_cast<int64_t>(pts.size() / 3);
       pts.insert(pts.end(), nd.low_resolution_xyz, nd.low_resolution_xyz + 3 * nd.num_low_resolution);
     }
-    Refine3Desc& d = desc[i];
+    Refine3Desc& d = desc[slot[i]];
     const csm_hybrid_grid* g[2] = {grids[it.high_grid], grids[it.low_grid]};
     for (int k = 0; k < 2; ++k) {
       // Grids from any context on ctx's device (e.g. one whose stream built
@@ -447,16 +595,41 @@ int csm_ceres3d_refine_batch(csm_context* ctx, const csm_hybrid_grid* const* gri
       d.target[a] = it.target[a];
     }
     for (int a = 0; a < 4; ++a) d.q[a] = it.initial.q[a];
+    if (slot[i] < num_plain) continue;
+    // The intensity block on the high-resolution cloud (cloud 0) only.
+    const int32_t ig = ia->grid_of_item[i];
+    if (ig >= ia->num_grids || !ia->grids[ig] || !ia->node_intensities ||
+        !ia->node_intensities[it.node])
+      return CSM_EINVAL;
+    const csm_intensity_grid* igrid = ia->grids[ig];
+    if (!igrid->ctx || igrid->ctx->device != ctx->device) return CSM_EINVAL;
+    if (voff[it.node] < 0) {
+      const float* v = ia->node_intensities[it.node];
+      for (int32_t k = 0; k < nd.num_high_resolution; ++k)
+        if (!std::isfinite(v[k])) return CSM_EINVAL;
+      voff[it.node] = static_cast<int64_t>(vals.size());
+      vals.insert(vals.end(), v, v + nd.num_high_resolution);
+    }
+    blocks[slot[i] - num_plain] = IntensBlock3{
+        IntensView3{igrid->sum.as<float>(), igrid->count.as<int32_t>(), igrid->brick,
+                    igrid->resolution},
+        voff[it.node], ia->options->weight / std::sqrt(static_cast<double>(nd.num_high_resolution)),
+        ia->options->huber_scale, static_cast<float>(ia->options->intensity_threshold)};
   }
   std::lock_guard<std::mutex> lock(ctx->mu);
   if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
   int rc;
-  if ((rc = ctx->cr3_items.Reserve(sizeof(Refine3Desc) * n))) return rc;
-  if ((rc = ctx->cr3_points.Reserve(sizeof(float) * std::max<size_t>(pts.size(), 3)))) return rc;
+  const size_t desc_bytes = (sizeof(Refine3Desc) * n + 15) & ~size_t{15};
+  if ((rc = ctx->cr3_items.Reserve(desc_bytes + sizeof(IntensBlock3) * num_intens))) return rc;
+  if ((rc = ctx->cr3_points.Reserve(sizeof(float) * std::max<size_t>(pts.size() + vals.size(), 3))))
+    return rc;
   if ((rc = ctx->cr3_out.Reserve(sizeof(double) * 7 * n + sizeof(int32_t) * n))) return rc;
   hipStream_t st = ctx->stream;
   for (int32_t k = 0; k < num_grids; ++k)  // grids another context's stream built
     if (grids[k] && (rc = WaitBuilt(grids[k]->ready, grids[k]->ctx->stream, st))) return rc;
+  for (int32_t k = 0; num_intens > 0 && k < ia->num_grids; ++k)
+    if (ia->grids[k] && (rc = WaitBuilt(ia->grids[k]->ready, ia->grids[k]->ctx->stream, st)))
+      return rc;
   CSM_HIP(hipMemcpyAsync(ctx->cr3_items.ptr, desc.data(), sizeof(Refine3Desc) * n,
                          hipMemcpyHostToDevice, st));
   CSM_HIP(hipMemcpyAsync(ctx->cr3_points.ptr, pts.data(), sizeof(float) * pts.size(),
@@ -466,18 +639,111 @@ int csm_ceres3d_refine_batch(csm_context* ctx, const csm_hybrid_grid* const* gri
                       options->max_num_iterations, options->use_nonmonotonic_steps ? 1 : 0};
   double* dout = ctx->cr3_out.as<double>();
   int32_t* diters = reinterpret_cast<int32_t*>(dout + 7 * n);
-  hipLaunchKernelGGL(ceres3d_refine, dim3(static_cast<unsigned>(n)), dim3(kR3Threads), 0, st,
-                     ctx->cr3_items.as<Refine3Desc>(), ctx->cr3_points.as<float>(), o, dout, diters);
-  CSM_HIP(hipGetLastError());
+  const Refine3Desc* ditems = ctx->cr3_items.as<Refine3Desc>();
+  const float* dpts = ctx->cr3_points.as<float>();
+  if (num_plain > 0) {
+    hipLaunchKernelGGL(ceres3d_refine<false>, dim3(static_cast<unsigned>(num_plain)),
+                       dim3(kR3Threads), 0, st, ditems, dpts, o, dout, diters, nullptr, nullptr);
+    CSM_HIP(hipGetLastError());
+  }
+  if (num_intens > 0) {
+    IntensBlock3* dblocks = reinterpret_cast<IntensBlock3*>(ctx->cr3_items.as<char>() + desc_bytes);
+    float* dvals = ctx->cr3_points.as<float>() + pts.size();
+    CSM_HIP(hipMemcpyAsync(dblocks, blocks.data(), sizeof(IntensBlock3) * num_intens,
+                           hipMemcpyHostToDevice, st));
+    CSM_HIP(hipMemcpyAsync(dvals, vals.data(), sizeof(float) * vals.size(), hipMemcpyHostToDevice,
+                           st));
+    hipLaunchKernelGGL(ceres3d_refine<true>, dim3(static_cast<unsigned>(num_intens)),
+                       dim3(kR3Threads), 0, st, ditems + num_plain, dpts, o, dout + 7 * num_plain,
+                       diters + num_plain, dblocks, dvals);
+    CSM_HIP(hipGetLastError());
+  }
   std::vector<double> host(7 * static_cast<size_t>(n));
+  std::vector<int32_t> host_iters(static_cast<size_t>(n));
   CSM_HIP(hipMemcpyAsync(host.data(), dout, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, st));
   if (iterations)
-    CSM_HIP(hipMemcpyAsync(iterations, diters, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    CSM_HIP(hipMemcpyAsync(host_iters.data(), diters, sizeof(int32_t) * n, hipMemcpyDeviceToHost,
+                           st));
   CSM_HIP(hipStreamSynchronize(st));
   for (int64_t i = 0; i < n; ++i) {
-    for (int a = 0; a < 3; ++a) out[i].t[a] = host[7 * i + a];
-    for (int a = 0; a < 4; ++a) out[i].q[a] = host[7 * i + 3 + a];
+    for (int a = 0; a < 3; ++a) out[i].t[a] = host[7 * slot[i] + a];
+    for (int a = 0; a < 4; ++a) out[i].q[a] = host[7 * slot[i] + 3 + a];
+    if (iterations) iterations[i] = host_iters[slot[i]];
   }
+  return CSM_OK;
+}
+
+}  // namespace
+}  // namespace csm
+
+extern "C" {
+
+int csm_ceres3d_refine_batch(csm_context* ctx, const csm_hybrid_grid* const* grids,
+                             int32_t num_grids, const csm_node3d* nodes, int32_t num_nodes,
+                             const csm_refine3d* items, int64_t n,
+                             const csm_ceres3d_options* options, csm_pose3d* out,
+                             int32_t* iterations) {
+  return csm::Refine3Batch(ctx, grids, num_grids, nodes, num_nodes, items, n, options, out,
+                           iterations, nullptr);
+}
+
+int csm_ceres3d_refine_intensity_batch(
+    csm_context* ctx, const csm_hybrid_grid* const* grids, int32_t num_grids,
+    const csm_intensity_grid* const* intensity_grids, int32_t num_intensity_grids,
+    const csm_node3d* nodes, const float* const* node_intensities, int32_t num_nodes,
+    const csm_refine3d* items, const int32_t* intensity_grid_of_item, int64_t n,
+    const csm_ceres3d_options* options, const csm_ceres3d_intensity_options* intensity_options,
+    csm_pose3d* out, int32_t* iterations) {
+  if (num_intensity_grids < 0 || (num_intensity_grids > 0 && !intensity_grids))
+    return CSM_EINVAL;
+  const csm::Intens3Args ia{intensity_grids, num_intensity_grids, node_intensities,
+                            intensity_grid_of_item, intensity_options};
+  return csm::Refine3Batch(ctx, grids, num_grids, nodes, num_nodes, items, n, options, out,
+                           iterations, &ia);
+}
+
+int csm_ceres3d_intensity_evaluate(const csm_intensity_grid* grid, const float* points_xyz,
+                                   const float* intensities, int32_t n, const double pose[7],
+                                   double scaling_factor, float intensity_threshold,
+                                   double* residuals, double* jacobian) {
+  using namespace csm;
+  if (!grid || n < 0 || !pose || (n > 0 && (!points_xyz || !intensities || !residuals || !jacobian)))
+    return CSM_EINVAL;
+  if (!std::isfinite(scaling_factor) || std::isnan(intensity_threshold)) return CSM_EINVAL;
+  for (int a = 0; a < 7; ++a)
+    if (!std::isfinite(pose[a])) return CSM_EINVAL;
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(intensities[i]) || !std::isfinite(points_xyz[3 * i]) ||
+        !std::isfinite(points_xyz[3 * i + 1]) || !std::isfinite(points_xyz[3 * i + 2]))
+      return CSM_EINVAL;
+  if (n == 0) return CSM_OK;
+  csm_context* ctx = grid->ctx;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  DevBuf din, dout;
+  int rc;
+  const size_t in_bytes = sizeof(double) * 7 + sizeof(float) * 4 * n;
+  if ((rc = din.Reserve(in_bytes)) || (rc = dout.Reserve(sizeof(double) * 7 * n))) return rc;
+  std::vector<char> host(in_bytes);
+  std::memcpy(host.data(), pose, sizeof(double) * 7);
+  std::memcpy(host.data() + sizeof(double) * 7, points_xyz, sizeof(float) * 3 * n);
+  std::memcpy(host.data() + sizeof(double) * 7 + sizeof(float) * 3 * n, intensities,
+              sizeof(float) * n);
+  hipStream_t st = ctx->stream;
+  CSM_HIP(hipMemcpyAsync(din.ptr, host.data(), in_bytes, hipMemcpyHostToDevice, st));
+  const double* dpose = din.as<double>();
+  const float* dpts = reinterpret_cast<const float*>(dpose + 7);
+  const IntensBlock3 block{IntensView3{grid->sum.as<float>(), grid->count.as<int32_t>(),
+                                       grid->brick, grid->resolution},
+                           0, scaling_factor, 0., intensity_threshold};
+  hipLaunchKernelGGL(ceres3d_intensity_eval, dim3(static_cast<unsigned>((n + 255) / 256)),
+                     dim3(256), 0, st, block, dpts, dpts + 3 * static_cast<size_t>(n), n, dpose,
+                     dout.as<double>(), dout.as<double>() + n);
+  CSM_HIP(hipGetLastError());
+  CSM_HIP(hipMemcpyAsync(residuals, dout.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipMemcpyAsync(jacobian, dout.as<double>() + n, sizeof(double) * 6 * n,
+                         hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
   return CSM_OK;
 }
 

@@ -327,6 +327,9 @@ struct csm_context {
   // last (hit, miss) pair, the value-to-probability table, a batch's job
   // descriptors and returns with their pinned staging.
   csm::DevBuf ins3_tabs, ins3_ptab, ins3_dev;
+  // An insert with intensities: the (cell key, return index) pairs of a round,
+  // their sorted copies and the sort's scratch.
+  csm::DevBuf ins3_sort;
   float ins3_tab_key[2] = {-1.f, -1.f};
   csm::StageRing ins3_stage;
   // TSDF range-data insertion (insert_tsdf2d.hip): per (truncation, max
@@ -454,6 +457,20 @@ struct csm_hybrid_grid {
   uint64_t prob_pad_gen = 0, prob_wide_gen = 0, prob_col_gen = 0;
   // csm_hybrid_grid_insert_stats' two counters, made by the first insert.
   csm::DevBuf insert_stats;
+};
+
+// An IntensityHybridGrid on the device (insert3d.hip): the float sum and the
+// int32 count of every cell over the bounding box of the cells with
+// count > 0, x fastest. Host state and bricks as for csm_hybrid_grid.
+struct csm_intensity_grid {
+  csm_context* ctx = nullptr;
+  hipEvent_t ready = nullptr;
+  float resolution = 0.f;
+  int32_t grid_size = 128;  // DynamicGrid's initial size (hybrid_grid.h:255)
+  csm::Brick3 brick{};
+  csm::DevBuf sum;    // float brick
+  csm::DevBuf count;  // int32 brick
+  uint64_t generation = 0;
 };
 
 namespace csm {

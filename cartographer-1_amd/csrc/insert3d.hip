@@ -29,7 +29,26 @@
 //                  the same span, with the probability brick's update.
 //   insert3d_grow  a grown grid's new bricks: the old cells at their offset,
 //                  unknown (0, kMinProbability) elsewhere.
+//
+// Intensities (InsertIntensitiesIntoGrid, :76-89, into a csm_intensity_grid).
+// cell->sum += intensity is a float sum in returns order, so a cell that
+// several returns of a scan share must take them in index order, continued
+// from its old sum. No float atomic touches the sums:
+//   insert3d_intensity_keys  one thread per return writes (job of the round,
+//                  cell index in the brick) as a 64-bit key and the return's
+//                  index as the value; a return that is filtered out, above
+//                  the threshold or of a job without intensities gets a key
+//                  past every real one.
+//   rocprim::radix_sort_pairs  stable, so equal keys keep index order.
+//   insert3d_intensity_sums  one thread per sorted pair; the one at the head
+//                  of a run of equal keys (found in an LDS tile of the
+//                  block's keys) walks the run, adds in index order, stores
+//                  the sum once and adds the run's length to the count.
+// Work is proportional to the returns; the bricks are touched only at the
+// cells that change.
 #include <hip/hip_runtime.h>
+// The radix sort alone: rocprim.hpp also pulls in texture iterators.
+#include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <atomic>
@@ -257,10 +276,12 @@ insert3d_rays(const Job3* __restrict__ jobs, const float* __restrict__ points,
   }
 }
 
+// A: uint16 values, B: float probabilities (HybridGrid); A: float sums,
+// B: int32 counts (IntensityHybridGrid).
+template <typename A, typename B>
 __global__ void __launch_bounds__(256)
-insert3d_grow(const uint16_t* __restrict__ old_values, const float* __restrict__ old_prob,
-              Brick3 ob, uint16_t* __restrict__ values, float* __restrict__ prob, Brick3 nb,
-              float unknown) {
+insert3d_grow(const A* __restrict__ old_values, const B* __restrict__ old_prob, Brick3 ob,
+              A* __restrict__ values, B* __restrict__ prob, Brick3 nb, B unknown) {
   const int64_t total = static_cast<int64_t>(nb.nx) * nb.ny * nb.nz;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
@@ -268,9 +289,90 @@ insert3d_grow(const uint16_t* __restrict__ old_values, const float* __restrict__
     const int y = static_cast<int>(i / nb.nx % nb.ny) + nb.oy;
     const int z = static_cast<int>(i / nb.nx / nb.ny) + nb.oz;
     const int64_t k = BrickIndex(ob, x, y, z);
-    values[i] = k < 0 ? uint16_t{0} : old_values[k];
+    values[i] = k < 0 ? A{0} : old_values[k];
     prob[i] = k < 0 ? unknown : old_prob[k];
   }
+}
+
+// The intensity half of a job: the Job3 gives the returns, their transform
+// and the range filter; the cell is the intensity grid's own GetCellIndex.
+struct IJob3 {
+  float* sum;
+  int32_t* count;
+  Brick3 b;
+  float resolution;
+  float threshold;
+  int job;       // the Job3, as an index into the call's descriptors
+  int64_t slot;  // the job's first pair in the launch set's key array
+};
+
+__global__ void __launch_bounds__(256)
+insert3d_intensity_keys(const IJob3* __restrict__ ijobs, const Job3* __restrict__ jobs,
+                        const float* __restrict__ points, const float* __restrict__ intensities,
+                        uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const IJob3 ij = ijobs[blockIdx.y];
+  const Job3 j = jobs[ij.job];
+  const uint64_t none = static_cast<uint64_t>(gridDim.y) << 32;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < j.num_returns;
+       i += gridDim.x * blockDim.x) {
+    uint64_t key = none;
+    float p[3];
+    if (JobPoint(j, points + 3 * (j.begin + i), p) &&
+        !(intensities[j.begin + i] > ij.threshold)) {
+      const int64_t c = BrickIndex(ij.b, static_cast<int>(CellF(p[0], ij.resolution)),
+                                   static_cast<int>(CellF(p[1], ij.resolution)),
+                                   static_cast<int>(CellF(p[2], ij.resolution)));
+      // The host sized the brick from these very cells; a cell outside it is
+      // dropped, never written.
+      if (c >= 0) key = static_cast<uint64_t>(blockIdx.y) << 32 | static_cast<uint64_t>(c);
+    }
+    keys[ij.slot + i] = key;
+    vals[ij.slot + i] = static_cast<uint32_t>(i);
+  }
+}
+
+// keys sorted, n of them, `none` and above are not cells. Jobs of a launch
+// set write different grids and one thread owns a (job, cell) run, so the
+// plain stores do not race.
+__global__ void __launch_bounds__(256)
+insert3d_intensity_sums(const IJob3* __restrict__ ijobs, const Job3* __restrict__ jobs,
+                        const float* __restrict__ intensities,
+                        const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                        int64_t n, uint64_t none) {
+  __shared__ uint64_t tile[257];  // the key before the block's first, then the block's
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * 256;
+  const int64_t s = base + threadIdx.x;
+  tile[threadIdx.x + 1] = s < n ? keys[s] : none;
+  if (threadIdx.x == 0) tile[0] = base > 0 ? keys[base - 1] : none;
+  __syncthreads();
+  const uint64_t key = tile[threadIdx.x + 1];
+  if (key >= none || key == tile[threadIdx.x]) return;  // not the head of a run
+  const IJob3 ij = ijobs[key >> 32];
+  const float* __restrict__ v = intensities + jobs[ij.job].begin;
+  const int64_t cell = static_cast<int64_t>(key & 0xffffffffu);
+  float sum = ij.sum[cell];
+  int32_t count = 0;
+  for (int64_t t = s;;) {
+    sum = __fadd_rn(sum, v[vals[t]]);
+    ++count;
+    if (++t >= n) break;
+    const uint64_t next = t - base < 256 ? tile[t - base + 1] : keys[t];
+    if (next != key) break;
+  }
+  ij.sum[cell] = sum;
+  ij.count[cell] += count;
+}
+
+// IntensityHybridGrid::GetIntensity (hybrid_grid.h:563-570).
+__global__ void intensity_grid_lookup(const float* __restrict__ sum,
+                                      const int32_t* __restrict__ count, Brick3 b,
+                                      const int32_t* __restrict__ ijk, int64_t n,
+                                      float* __restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t k = BrickIndex(b, ijk[3 * i], ijk[3 * i + 1], ijk[3 * i + 2]);
+  const int32_t c = k < 0 ? 0 : count[k];
+  out[i] = c == 0 ? 0.f : __fdiv_rn(sum[k], static_cast<float>(c));
 }
 
 // ---------------------------------------------------------------- host -----
@@ -382,6 +484,7 @@ struct PlanTask {
   int job, i0, i1;
   Box3 box;
   int rc;
+  Box3 ibox;  // the cells of the job's intensity grid that gain a return
 };
 
 // The box of the cells returns [i0, i1) of job j touch: per ray the hit cell
@@ -407,6 +510,66 @@ int PlanReturns(const Job3& j, const float* returns, int i0, int i1, int free_vo
   return CSM_OK;
 }
 
+// The intensity half of a call (csm_hybrid_grid_insert_intensities*); null
+// for the entry points without one.
+struct Intens3 {
+  csm_intensity_grid* const* grids;
+  int32_t num_grids;
+  const int32_t* grid_of_job;            // -1: the job has none
+  const float* const* scan_intensities;  // per scan, null: the scan has none
+  float threshold;
+};
+
+// The box of the cells of job j's intensity grid that returns [i0, i1) add to
+// (InsertIntensitiesIntoGrid, :76-89).
+int PlanIntensities(const Job3& j, const float* returns, const float* intensities, float resolution,
+                    float threshold, int i0, int i1, Box3* box) {
+  for (int i = i0; i < i1; ++i) {
+    float p[3];
+    if (intensities[i] > threshold || !JobPoint(j, returns + 3 * (j.begin + i), p)) continue;
+    int x, y, z;
+    if (!HostCell(p[0], resolution, &x) || !HostCell(p[1], resolution, &y) ||
+        !HostCell(p[2], resolution, &z))
+      return CSM_ERANGE;
+    box->Add(x, y, z);
+  }
+  return CSM_OK;
+}
+
+// DynamicGrid::Grow (hybrid_grid.h:283-296, :384-399) and the brick over the
+// old box united with `box`. CSM_ERANGE past 2^31 cells.
+int GrownBrick(const Brick3& b, const Box3& box, Brick3* after, int* grid_size) {
+  const bool had = b.nx > 0;
+  const int olo[3] = {b.ox, b.oy, b.oz};
+  const int ohi[3] = {b.ox + b.nx - 1, b.oy + b.ny - 1, b.oz + b.nz - 1};
+  int lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = had ? std::min(olo[a], box.lo[a]) : box.lo[a];
+    hi[a] = had ? std::max(ohi[a], box.hi[a]) : box.hi[a];
+    while (box.lo[a] < -(*grid_size / 2) || box.hi[a] >= *grid_size / 2) *grid_size *= 2;
+  }
+  *after = Brick3{lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1, 0};
+  const int64_t n = static_cast<int64_t>(after->nx) * after->ny * after->nz;
+  return n > (int64_t{1} << 31) ? CSM_ERANGE : CSM_OK;
+}
+
+struct IntensPlan3 {
+  Box3 box;
+  Brick3 after{};
+  int grid_size = 0;
+  int paired = -1;  // the HybridGrid its jobs insert into
+  bool touched = false, grew = false;
+  DevBuf sum, count;
+};
+
+// The intensity jobs of one keys / sort / sums launch set.
+struct IntensSet3 {
+  int round, first, num;
+  int64_t pairs;    // the jobs' returns: one pair each
+  int max_returns;
+  int end_bit = 0;  // of the key: 32 bits of cell, then the job and `none`
+};
+
 struct GridPlan3 {
   Box3 box;          // the cells this call touches
   Brick3 after{};    // the brick once the call is done
@@ -421,7 +584,7 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
                  const float* returns, const int64_t* ret_off, int32_t num_jobs,
                  const int32_t* grid_of_job, const int32_t* scan_of_job, const float* transforms,
                  int32_t num_transforms, const int32_t* transform_of_job,
-                 const float* max_ranges, bool ctx_of_grid) {
+                 const float* max_ranges, bool ctx_of_grid, const Intens3* in = nullptr) {
   if ((!ctx && !ctx_of_grid) || !grids || !o || num_grids < 1 || num_scans < 0 || num_jobs < 0 ||
       num_transforms < 0)
     return CSM_EINVAL;
@@ -454,6 +617,28 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     if (transform_of_job && transform_of_job[k] >= num_transforms) return CSM_EINVAL;
     if (max_ranges && std::isnan(max_ranges[k])) return CSM_EINVAL;
   }
+  // ipair[i]: the HybridGrid intensity grid i is filled with. Its jobs run in
+  // that grid's rounds, so one call pairs it with one HybridGrid only.
+  std::vector<int> ipair;
+  if (in) {
+    if (in->num_grids < 0 || (in->num_grids > 0 && !in->grids) || std::isnan(in->threshold))
+      return CSM_EINVAL;
+    for (int g = 0; g < in->num_grids; ++g)
+      if (!in->grids[g]) return CSM_EINVAL;
+    for (int s = 0; s < num_scans && in->scan_intensities; ++s) {
+      const float* v = in->scan_intensities[s];
+      for (int64_t i = 0, n = ret_off[s + 1] - ret_off[s]; v && i < n; ++i)
+        if (!std::isfinite(v[i])) return CSM_EINVAL;
+    }
+    ipair.assign(in->num_grids, -1);
+    for (int k = 0; k < num_jobs && in->grid_of_job; ++k) {
+      const int ig = in->grid_of_job[k];
+      if (ig < 0) continue;
+      if (ig >= in->num_grids) return CSM_EINVAL;
+      if (ipair[ig] >= 0 && ipair[ig] != grid_of_job[k]) return CSM_EINVAL;
+      ipair[ig] = grid_of_job[k];
+    }
+  }
   // The points are checked before any handle is read.
   if (ctx_of_grid) ctx = grids[0]->ctx;
   if (!ctx) return CSM_EINVAL;
@@ -461,6 +646,11 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     if (grids[g]->ctx != ctx) return CSM_EINVAL;
     for (int h = 0; h < g; ++h)
       if (grids[h] == grids[g]) return CSM_EINVAL;
+  }
+  for (int g = 0; in && g < in->num_grids; ++g) {
+    if (in->grids[g]->ctx != ctx) return CSM_EINVAL;
+    for (int h = 0; h < g; ++h)
+      if (in->grids[h] == in->grids[g]) return CSM_EINVAL;
   }
   std::lock_guard<std::mutex> lock(ctx->mu);
   if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
@@ -475,6 +665,13 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   std::vector<GridPlan3> plan(num_grids);
   std::vector<int> round_of(num_jobs);
   std::vector<PlanTask> tasks;
+  // The job's intensity grid, -1 where it has none or its scan carries no
+  // intensities (:79), and that scan's intensities.
+  std::vector<int> igrid_of(num_jobs, -1);
+  std::vector<IntensPlan3> iplan(in ? in->num_grids : 0);
+  auto intensities_of = [&](int k) { return in->scan_intensities[scan_of_job[k]]; };
+  for (int k = 0; in && in->grid_of_job && in->scan_intensities && k < num_jobs; ++k)
+    if (in->grid_of_job[k] >= 0 && intensities_of(k)) igrid_of[k] = in->grid_of_job[k];
   int64_t planned = 0;
   int num_rounds = 0;
   for (int k = 0; k < num_jobs; ++k) {
@@ -507,7 +704,8 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
         !HostCell(org[2], j.resolution, &j.cz))
       return CSM_ERANGE;
     for (int i0 = 0; i0 < j.num_returns; i0 += kPlanChunk)
-      tasks.push_back(PlanTask{k, i0, std::min(j.num_returns, i0 + kPlanChunk), Box3{}, CSM_OK});
+      tasks.push_back(
+          PlanTask{k, i0, std::min(j.num_returns, i0 + kPlanChunk), Box3{}, CSM_OK, Box3{}});
     planned += j.num_returns;
   }
   {
@@ -516,7 +714,18 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     auto work = [&] {
       for (size_t t; (t = next.fetch_add(1)) < tasks.size();) {
         PlanTask& task = tasks[t];
-        task.rc = PlanReturns(jobs[task.job], returns, task.i0, task.i1, free_voxels, &task.box);
+        // The boxes grow in locals and are stored once: neighbouring tasks
+        // share cache lines, and a store per return from every thread made
+        // the 55 000-return plan two to three times slower.
+        Box3 box, ibox;
+        int rc = PlanReturns(jobs[task.job], returns, task.i0, task.i1, free_voxels, &box);
+        const int ig = igrid_of[task.job];
+        if (rc == CSM_OK && ig >= 0)
+          rc = PlanIntensities(jobs[task.job], returns, intensities_of(task.job),
+                               in->grids[ig]->resolution, in->threshold, task.i0, task.i1, &ibox);
+        task.box = box;
+        task.ibox = ibox;
+        task.rc = rc;
       }
     };
     const size_t hw = std::max(1u, std::thread::hardware_concurrency());
@@ -536,7 +745,23 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
         box.Add(task.box.lo[0], task.box.lo[1], task.box.lo[2]);
         box.Add(task.box.hi[0], task.box.hi[1], task.box.hi[2]);
       }
+      if (!task.ibox.empty()) {
+        Box3& box = iplan[igrid_of[task.job]].box;
+        box.Add(task.ibox.lo[0], task.ibox.lo[1], task.ibox.lo[2]);
+        box.Add(task.ibox.hi[0], task.ibox.hi[1], task.ibox.hi[2]);
+      }
     }
+  }
+  for (size_t gi = 0; gi < iplan.size(); ++gi) {
+    IntensPlan3& ip = iplan[gi];
+    const csm_intensity_grid* g = in->grids[gi];
+    ip.after = g->brick;
+    ip.grid_size = g->grid_size;
+    ip.touched = !ip.box.empty();
+    if (!ip.touched) continue;
+    if (GrownBrick(g->brick, ip.box, &ip.after, &ip.grid_size) != CSM_OK) return CSM_ERANGE;
+    ip.grew = ip.after.nx != g->brick.nx || ip.after.ny != g->brick.ny ||
+              ip.after.nz != g->brick.nz;
   }
   for (int gi = 0; gi < num_grids; ++gi) {
     GridPlan3& gp = plan[gi];
@@ -547,20 +772,8 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     if (!gp.touched) continue;
     const Brick3& b = g->brick;
     const bool had = b.nx > 0;
-    const int olo[3] = {b.ox, b.oy, b.oz};
-    const int ohi[3] = {b.ox + b.nx - 1, b.oy + b.ny - 1, b.oz + b.nz - 1};
-    int lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = had ? std::min(olo[a], gp.box.lo[a]) : gp.box.lo[a];
-      hi[a] = had ? std::max(ohi[a], gp.box.hi[a]) : gp.box.hi[a];
-      // DynamicGrid::Grow (hybrid_grid.h:283-296, :384-399).
-      while (gp.box.lo[a] < -(gp.grid_size / 2) || gp.box.hi[a] >= gp.grid_size / 2)
-        gp.grid_size *= 2;
-    }
-    gp.after = Brick3{lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1,
-                      hi[2] - lo[2] + 1, 0};
+    if (GrownBrick(b, gp.box, &gp.after, &gp.grid_size) != CSM_OK) return CSM_ERANGE;
     const int64_t n = static_cast<int64_t>(gp.after.nx) * gp.after.ny * gp.after.nz;
-    if (n > (int64_t{1} << 31)) return CSM_ERANGE;
     // A brick csm_hybrid_grid_create sized to an odd cell count is moved once
     // so that its last cell has a whole word.
     gp.grew = !had || gp.after.nx != b.nx || gp.after.ny != b.ny || gp.after.nz != b.nz ||
@@ -575,6 +788,10 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
       if (gp.values.ptr) ctx->pool.Give(&gp.values);
       if (gp.prob.ptr) ctx->pool.Give(&gp.prob);
       if (gp.stats.ptr) ctx->pool.Give(&gp.stats);
+    }
+    for (IntensPlan3& ip : iplan) {
+      if (ip.sum.ptr) ctx->pool.Give(&ip.sum);
+      if (ip.count.ptr) ctx->pool.Give(&ip.count);
     }
   };
   for (int gi = 0; gi < num_grids && rc == CSM_OK; ++gi) {
@@ -595,7 +812,68 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
                    [&](int a, int b) { return round_of[a] < round_of[b]; });
   const int live = static_cast<int>(order.size());
   const size_t desc_bytes = (sizeof(Job3) * std::max(live, 1) + 255) & ~size_t(255);
-  const size_t bytes = desc_bytes + sizeof(float) * 3 * total_ret;
+  size_t bytes = desc_bytes + sizeof(float) * 3 * total_ret;
+  // The intensity halves, in the same order: a launch set is the jobs of one
+  // round (at most gridDim.y of them) whose intensity grid gains a return.
+  auto align = [](size_t n) { return (n + 255) & ~size_t(255); };
+  std::vector<IJob3> ijobs;
+  std::vector<IntensSet3> isets;
+  for (int i = 0; i < live; ++i) {
+    const int k = order[i], ig = igrid_of[k];
+    if (ig < 0 || !iplan[ig].touched) continue;
+    if (isets.empty() || isets.back().round != round_of[k] || isets.back().num == 65535)
+      isets.push_back(IntensSet3{round_of[k], static_cast<int>(ijobs.size()), 0, 0, 1});
+    IntensSet3& set = isets.back();
+    IJob3 ij{};
+    ij.resolution = in->grids[ig]->resolution;
+    ij.threshold = in->threshold;
+    ij.job = i;
+    ij.slot = set.pairs;
+    ijobs.push_back(ij);
+    ++set.num;
+    set.pairs += jobs[k].num_returns;
+    set.max_returns = std::max(set.max_returns, jobs[k].num_returns);
+  }
+  size_t idesc_at = 0, ival_at = 0, sort_bytes = 0, pair_cap = 0, scratch_bytes = 256;
+  if (!ijobs.empty()) {
+    idesc_at = align(bytes);
+    ival_at = idesc_at + align(sizeof(IJob3) * ijobs.size());
+    bytes = ival_at + sizeof(float) * total_ret;
+    for (IntensSet3& set : isets) {
+      if (set.pairs >= (int64_t{1} << 31)) rc = CSM_ERANGE;  // the sort counts in 32 bits
+      set.end_bit = 33;
+      while ((1u << (set.end_bit - 32)) <= static_cast<unsigned>(set.num)) ++set.end_bit;
+      size_t need = 0;
+      if (rc == CSM_OK &&
+          rocprim::radix_sort_pairs(nullptr, need, static_cast<uint64_t*>(nullptr),
+                                    static_cast<uint64_t*>(nullptr),
+                                    static_cast<uint32_t*>(nullptr),
+                                    static_cast<uint32_t*>(nullptr),
+                                    static_cast<unsigned>(set.pairs), 0u,
+                                    static_cast<unsigned>(set.end_bit), ctx->stream) != hipSuccess)
+        rc = CSM_EHIP;
+      scratch_bytes = std::max(scratch_bytes, need);
+      pair_cap = std::max(pair_cap, static_cast<size_t>(set.pairs));
+    }
+    // keys, sorted keys, indices, sorted indices, scratch.
+    sort_bytes = 2 * align(8 * pair_cap) + 2 * align(4 * pair_cap) + align(scratch_bytes);
+  }
+  for (size_t gi = 0; gi < iplan.size() && rc == CSM_OK; ++gi) {
+    IntensPlan3& ip = iplan[gi];
+    csm_intensity_grid* g = in->grids[gi];
+    if (!ip.touched) continue;
+    if (!g->ready && hipEventCreateWithFlags(&g->ready, hipEventDisableTiming) != hipSuccess)
+      rc = CSM_EHIP;
+    if (rc != CSM_OK || !ip.grew) continue;
+    const int64_t n = static_cast<int64_t>(ip.after.nx) * ip.after.ny * ip.after.nz;
+    if ((rc = ctx->pool.Take(sizeof(float) * n, &ip.sum)) == CSM_OK)
+      rc = ctx->pool.Take(sizeof(int32_t) * n, &ip.count);
+  }
+  if (rc == CSM_OK && ctx->ins3_sort.bytes < sort_bytes) {
+    // As ins3_dev below: an earlier insert may still sort in it.
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CSM_EHIP;
+    else rc = ctx->ins3_sort.Reserve(sort_bytes + sort_bytes / 2);
+  }
   StageRing::Slot* slot = nullptr;
   if (rc == CSM_OK && live > 0) rc = ctx->ins3_stage.Take(bytes, &slot);
   if (rc == CSM_OK && live > 0 && ctx->ins3_dev.bytes < bytes) {
@@ -641,6 +919,27 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     g->grid_size = gp.grid_size;
     ++g->generation;
   }
+  for (size_t gi = 0; gi < iplan.size(); ++gi) {
+    IntensPlan3& ip = iplan[gi];
+    csm_intensity_grid* g = in->grids[gi];
+    if (!ip.touched) continue;
+    if (ip.grew) {
+      const int64_t n = static_cast<int64_t>(ip.after.nx) * ip.after.ny * ip.after.nz;
+      hipLaunchKernelGGL(insert3d_grow, dim3(Blocks(n, 1024, 8192)), dim3(256), 0, st,
+                         g->sum.as<float>(), g->count.as<int32_t>(), g->brick,
+                         ip.sum.as<float>(), ip.count.as<int32_t>(), ip.after, int32_t{0});
+      CSM_HIP(hipGetLastError());
+      retired.emplace_back();
+      MoveBuf(&g->sum, &retired.back());
+      retired.emplace_back();
+      MoveBuf(&g->count, &retired.back());
+      MoveBuf(&ip.sum, &g->sum);
+      MoveBuf(&ip.count, &g->count);
+    }
+    g->brick = ip.after;
+    g->grid_size = ip.grid_size;
+    ++g->generation;
+  }
   if (live > 0) {
     Job3* hd = slot->buf.as<Job3>();
     for (int i = 0; i < live; ++i) {
@@ -654,6 +953,19 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     }
     if (total_ret)
       std::memcpy(slot->buf.as<char>() + desc_bytes, returns, sizeof(float) * 3 * total_ret);
+    if (!ijobs.empty()) {
+      for (IJob3& ij : ijobs) {
+        const int k = order[ij.job];
+        const csm_intensity_grid* g = in->grids[igrid_of[k]];
+        ij.sum = g->sum.as<float>();
+        ij.count = g->count.as<int32_t>();
+        ij.b = g->brick;
+        // The scan's intensities lie where its returns do.
+        std::memcpy(slot->buf.as<char>() + ival_at + sizeof(float) * jobs[k].begin,
+                    intensities_of(k), sizeof(float) * jobs[k].num_returns);
+      }
+      std::memcpy(slot->buf.as<char>() + idesc_at, ijobs.data(), sizeof(IJob3) * ijobs.size());
+    }
     CSM_HIP(hipMemcpyAsync(ctx->ins3_dev.ptr, slot->buf.ptr, bytes, hipMemcpyHostToDevice, st));
     CSM_HIP(hipEventRecord(slot->copied, st));
     const Job3* dd = ctx->ins3_dev.as<Job3>();
@@ -665,6 +977,15 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     int group_bits = 0;
     while (group_bits < 6 && (1 << group_bits) < free_voxels) ++group_bits;
     const int rays_per_block = 256 >> group_bits;
+    const IJob3* dij = reinterpret_cast<const IJob3*>(ctx->ins3_dev.as<char>() + idesc_at);
+    const float* dval = reinterpret_cast<const float*>(ctx->ins3_dev.as<char>() + ival_at);
+    char* sort_at = ctx->ins3_sort.as<char>();
+    uint64_t* keys = reinterpret_cast<uint64_t*>(sort_at);
+    uint64_t* sorted_keys = reinterpret_cast<uint64_t*>(sort_at + align(8 * pair_cap));
+    uint32_t* vals = reinterpret_cast<uint32_t*>(sort_at + 2 * align(8 * pair_cap));
+    uint32_t* sorted_vals = vals + align(4 * pair_cap) / sizeof(uint32_t);
+    void* scratch = sorted_vals + align(4 * pair_cap) / sizeof(uint32_t);
+    size_t next_set = 0;
     int i0 = 0;
     for (int r = 0; r < num_rounds && i0 < live; ++r) {
       int i1 = i0;
@@ -687,12 +1008,31 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
                            tabs, ptab, free_voxels, group_bits);
         CSM_HIP(hipGetLastError());
       }
+      for (; next_set < isets.size() && isets[next_set].round == r; ++next_set) {
+        const IntensSet3& set = isets[next_set];
+        const IJob3* dset = dij + set.first;
+        hipLaunchKernelGGL(insert3d_intensity_keys,
+                           dim3(Blocks(set.max_returns, 256, 1024), set.num), dim3(256), 0, st,
+                           dset, dd, dpts, dval, keys, vals);
+        CSM_HIP(hipGetLastError());
+        size_t scratch_size = scratch_bytes;
+        CSM_HIP(rocprim::radix_sort_pairs(scratch, scratch_size, keys, sorted_keys, vals,
+                                          sorted_vals, static_cast<unsigned>(set.pairs), 0u,
+                                          static_cast<unsigned>(set.end_bit), st));
+        hipLaunchKernelGGL(insert3d_intensity_sums,
+                           dim3(static_cast<unsigned>((set.pairs + 255) / 256)), dim3(256), 0, st,
+                           dset, dd, dval, sorted_keys, sorted_vals, set.pairs,
+                           static_cast<uint64_t>(set.num) << 32);
+        CSM_HIP(hipGetLastError());
+      }
       i0 = i1;
     }
   }
   // Consumers on other streams wait for the last insert.
   for (int gi = 0; gi < num_grids; ++gi)
     if (plan[gi].touched) CSM_HIP(hipEventRecord(grids[gi]->ready, st));
+  for (size_t gi = 0; gi < iplan.size(); ++gi)
+    if (iplan[gi].touched) CSM_HIP(hipEventRecord(in->grids[gi]->ready, st));
   // The old bricks of grown grids: reused by later takes on this stream.
   for (DevBuf& b : retired)
     if (b.ptr) ctx->pool.Give(&b);
@@ -752,6 +1092,115 @@ int csm_hybrid_grid_insert(csm_hybrid_grid* g, const csm_inserter3d_options* opt
   csm_hybrid_grid* const grids[1] = {g};
   return InsertBatch3(nullptr, grids, 1, options, 1, origin, returns, off, 1, &zero, &zero,
                       nullptr, 0, nullptr, nullptr, true);
+}
+
+int csm_hybrid_grid_insert_intensities_batch(
+    csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_grids,
+    csm_intensity_grid* const* intensity_grids, int32_t num_intensity_grids,
+    const csm_inserter3d_options* options, float intensity_threshold, int32_t num_scans,
+    const float* origins_xyz, const float* returns_xyz, const int64_t* return_offsets,
+    const float* const* scan_intensities, int32_t num_jobs, const int32_t* grid_of_job,
+    const int32_t* scan_of_job, const int32_t* intensity_grid_of_job, const float* transforms,
+    int32_t num_transforms, const int32_t* transform_of_job, const float* max_ranges) {
+  const Intens3 in{intensity_grids, num_intensity_grids, intensity_grid_of_job, scan_intensities,
+                   intensity_threshold};
+  return InsertBatch3(ctx, grids, num_grids, options, num_scans, origins_xyz, returns_xyz,
+                      return_offsets, num_jobs, grid_of_job, scan_of_job, transforms,
+                      num_transforms, transform_of_job, max_ranges, false, &in);
+}
+
+int csm_hybrid_grid_insert_intensities(csm_hybrid_grid* g, csm_intensity_grid* intensity_grid,
+                                       const csm_inserter3d_options* options,
+                                       float intensity_threshold, const float* origin,
+                                       const float* returns, const float* intensities,
+                                       int32_t n) {
+  if (!g || !options || !origin || n < 0 || (n > 0 && !returns)) return CSM_EINVAL;
+  const int32_t zero = 0;
+  const int64_t off[2] = {0, n};
+  csm_hybrid_grid* const grids[1] = {g};
+  csm_intensity_grid* const igrids[1] = {intensity_grid};
+  const Intens3 in{igrids, intensity_grid ? 1 : 0, intensity_grid ? &zero : nullptr, &intensities,
+                   intensity_threshold};
+  return InsertBatch3(nullptr, grids, 1, options, 1, origin, returns, off, 1, &zero, &zero,
+                      nullptr, 0, nullptr, nullptr, true, &in);
+}
+
+int csm_intensity_grid_create(csm_context* ctx, float resolution, csm_intensity_grid** out) {
+  if (!ctx || !out || !(resolution > 0.f) || !std::isfinite(resolution)) return CSM_EINVAL;
+  csm_intensity_grid* g = new csm_intensity_grid;
+  g->ctx = ctx;
+  g->resolution = resolution;
+  *out = g;
+  return CSM_OK;
+}
+
+void csm_intensity_grid_destroy(csm_intensity_grid* g) {
+  if (!g) return;
+  if (g->sum.ptr || g->ready) (void)hipSetDevice(g->ctx->device);
+  g->ctx->pool.Give(&g->sum);  // reused by the next grid
+  g->ctx->pool.Give(&g->count);
+  if (g->ready) (void)hipEventDestroy(g->ready);
+  delete g;
+}
+
+int csm_intensity_grid_info(const csm_intensity_grid* g, int32_t* origin3, int32_t* dims3,
+                            int32_t* grid_size) {
+  if (!g) return CSM_EINVAL;
+  if (origin3) {
+    origin3[0] = g->brick.ox;
+    origin3[1] = g->brick.oy;
+    origin3[2] = g->brick.oz;
+  }
+  if (dims3) {
+    dims3[0] = g->brick.nx;
+    dims3[1] = g->brick.ny;
+    dims3[2] = g->brick.nz;
+  }
+  if (grid_size) *grid_size = g->grid_size;
+  return CSM_OK;
+}
+
+int64_t csm_intensity_grid_device_bytes(const csm_intensity_grid* g) {
+  return g ? static_cast<int64_t>(g->sum.bytes + g->count.bytes) : 0;
+}
+
+int csm_intensity_grid_read(const csm_intensity_grid* g, float* sums_out, int32_t* counts_out,
+                            int64_t capacity) {
+  if (!g || capacity < 0) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(g->ctx->mu);
+  const int64_t n = static_cast<int64_t>(g->brick.nx) * g->brick.ny * g->brick.nz;
+  if (capacity < n || (n > 0 && (!sums_out || !counts_out))) return CSM_EINVAL;
+  if (n == 0) return CSM_OK;  // nothing was ever enqueued for this grid
+  if (hipSetDevice(g->ctx->device) != hipSuccess) return CSM_EHIP;
+  CSM_HIP(hipMemcpyAsync(sums_out, g->sum.ptr, n * sizeof(float), hipMemcpyDeviceToHost,
+                         g->ctx->stream));
+  CSM_HIP(hipMemcpyAsync(counts_out, g->count.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                         g->ctx->stream));
+  CSM_HIP(hipStreamSynchronize(g->ctx->stream));
+  return CSM_OK;
+}
+
+int csm_intensity_grid_get_intensity(const csm_intensity_grid* g, const int32_t* xyz_indices,
+                                     int64_t n, float* out) {
+  if (!g || n < 0 || (n > 0 && (!xyz_indices || !out))) return CSM_EINVAL;
+  if (n == 0) return CSM_OK;
+  csm_context* ctx = g->ctx;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  DevBuf din, dout;
+  int rc;
+  if ((rc = din.Reserve(sizeof(int32_t) * 3 * n)) || (rc = dout.Reserve(sizeof(float) * n)))
+    return rc;
+  hipStream_t st = ctx->stream;
+  CSM_HIP(hipMemcpyAsync(din.ptr, xyz_indices, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice,
+                         st));
+  hipLaunchKernelGGL(intensity_grid_lookup, dim3(static_cast<unsigned>((n + 255) / 256)),
+                     dim3(256), 0, st, g->sum.as<float>(), g->count.as<int32_t>(), g->brick,
+                     din.as<int32_t>(), n, dout.as<float>());
+  CSM_HIP(hipGetLastError());
+  CSM_HIP(hipMemcpyAsync(out, dout.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  return CSM_OK;
 }
 
 int csm_hybrid_grid_read(const csm_hybrid_grid* g, uint16_t* out, int64_t capacity) {

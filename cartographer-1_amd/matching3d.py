@@ -2,6 +2,9 @@
 
 * :class:`HybridGrid` — a HybridGrid's known cells on the device
   (``mapping/3d/hybrid_grid.h:463-545``; cells as the iterator / ToProto yields them).
+* :class:`IntensityHybridGrid` — an IntensityHybridGrid on the device
+  (``hybrid_grid.h:547-571``), filled by :meth:`HybridGrid.insert` /
+  :meth:`HybridGrid.insert_batch` when intensities are passed.
 * :class:`RealTimeCorrelativeScanMatcher3D` — ``Match``
   (``real_time_correlative_scan_matcher_3d.h:47-50``).
 * :class:`FastCorrelativeScanMatcher3D` — ``Match`` / ``MatchFullSubmap``
@@ -102,33 +105,64 @@ class HybridGrid:
         return out
 
     def insert(self, origin, returns, hit_probability: float = 0.55,
-               miss_probability: float = 0.49, num_free_space_voxels: int = 2) -> None:
+               miss_probability: float = 0.49, num_free_space_voxels: int = 2,
+               intensity_grid: Optional["IntensityHybridGrid"] = None, intensities=None,
+               intensity_threshold: float = 0.0) -> None:
         """RangeDataInserter3D::Insert on the device (csm_hybrid_grid_insert);
-        origin and returns in the grid's frame."""
+        origin and returns in the grid's frame. With ``intensity_grid`` it is
+        the three-argument Insert (csm_hybrid_grid_insert_intensities):
+        returns whose intensity is not above ``intensity_threshold`` are added
+        to that grid; ``intensities`` None is a cloud without intensities."""
         o = Inserter3DOptions(hit_probability, miss_probability, int(num_free_space_voxels))
         org = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
         r = np.ascontiguousarray(np.asarray(returns, np.float32).reshape(-1, 3))
-        _check(self._lib.csm_hybrid_grid_insert(self.handle, C.byref(o), _ptr(org, C.c_float),
-                                                _ptr(r, C.c_float), len(r)),
-               "csm_hybrid_grid_insert")
+        if intensity_grid is None:
+            _check(self._lib.csm_hybrid_grid_insert(self.handle, C.byref(o), _ptr(org, C.c_float),
+                                                    _ptr(r, C.c_float), len(r)),
+                   "csm_hybrid_grid_insert")
+            return
+        v = None
+        if intensities is not None:
+            v = np.ascontiguousarray(np.asarray(intensities, np.float32).reshape(-1))
+            if len(v) != len(r):
+                raise ValueError("returns and intensities differ in length")
+        _check(self._lib.csm_hybrid_grid_insert_intensities(
+            self.handle, intensity_grid.handle, C.byref(o), float(intensity_threshold),
+            _ptr(org, C.c_float), _ptr(r, C.c_float), None if v is None else _ptr(v, C.c_float),
+            len(r)), "csm_hybrid_grid_insert_intensities")
 
     @staticmethod
     def insert_batch(grids: Sequence["HybridGrid"], scans, jobs, hit_probability: float = 0.55,
-                     miss_probability: float = 0.49, num_free_space_voxels: int = 2) -> None:
+                     miss_probability: float = 0.49, num_free_space_voxels: int = 2,
+                     intensity_grids: Optional[Sequence["IntensityHybridGrid"]] = None,
+                     intensity_threshold: float = 0.0) -> None:
         """Many inserts in one call (csm_hybrid_grid_insert_batch). ``scans``:
         (origin, returns) pairs in the local frame, uploaded once. ``jobs``:
         (grid index, scan index[, transform[, max_range]]) tuples; transform is
         None or ((tx, ty, tz), (qw, qx, qy, qz)), submap from local; max_range
-        None or <= 0 keeps every return. Jobs on one grid apply in order."""
+        None or <= 0 keeps every return. Jobs on one grid apply in order.
+
+        With ``intensity_grids`` (csm_hybrid_grid_insert_intensities_batch) a
+        scan may be (origin, returns, intensities), intensities None for a
+        cloud without them, and a job may carry a fifth entry, the index of
+        its intensity grid (None or -1: none)."""
         ctx = grids[0].context
         o = Inserter3DOptions(hit_probability, miss_probability, int(num_free_space_voxels))
         origins = np.zeros((max(len(scans), 1), 3), np.float32)
         off = np.zeros(len(scans) + 1, np.int64)
         rets = []
-        for s, (org, ret) in enumerate(scans):
+        vals = []
+        for s, scan in enumerate(scans):
+            org, ret = scan[0], scan[1]
             origins[s] = np.asarray(org, np.float32).reshape(3)
             rets.append(np.asarray(ret, np.float32).reshape(-1, 3))
             off[s + 1] = off[s] + len(rets[-1])
+            v = scan[2] if len(scan) > 2 else None
+            if v is not None:
+                v = np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1))
+                if len(v) != len(rets[-1]):
+                    raise ValueError("returns and intensities differ in length")
+            vals.append(v)
         r = np.ascontiguousarray(np.concatenate(rets) if rets else np.zeros((0, 3), np.float32))
         n = len(jobs)
         gj = np.zeros(max(n, 1), np.int32)
@@ -146,6 +180,24 @@ class HybridGrid:
                 mr[k] = job[3]
         tf = np.ascontiguousarray(np.asarray(tfs, np.float32).reshape(-1, 7))
         handles = (C.c_void_p * len(grids))(*[g.handle for g in grids])
+        if intensity_grids is not None:
+            ij = np.full(max(n, 1), -1, np.int32)
+            for k, job in enumerate(jobs):
+                if len(job) > 4 and job[4] is not None:
+                    ij[k] = int(job[4])
+            ihandles = (C.c_void_p * max(len(intensity_grids), 1))(
+                *[g.handle for g in intensity_grids])
+            FP = C.POINTER(C.c_float)
+            vptr = (FP * max(len(scans), 1))(
+                *[FP() if v is None else _ptr(v, C.c_float) for v in vals])
+            _check(ctx._lib.csm_hybrid_grid_insert_intensities_batch(
+                ctx.handle, handles, len(grids), ihandles, len(intensity_grids), C.byref(o),
+                float(intensity_threshold), len(scans), _ptr(origins, C.c_float),
+                _ptr(r, C.c_float), _ptr(off, C.c_int64), vptr, n, _ptr(gj, C.c_int32),
+                _ptr(sj, C.c_int32), _ptr(ij, C.c_int32),
+                _ptr(tf, C.c_float) if len(tf) else None, len(tf), _ptr(tj, C.c_int32),
+                _ptr(mr, C.c_float)), "csm_hybrid_grid_insert_intensities_batch")
+            return
         _check(ctx._lib.csm_hybrid_grid_insert_batch(
             ctx.handle, handles, len(grids), C.byref(o), len(scans), _ptr(origins, C.c_float),
             _ptr(r, C.c_float), _ptr(off, C.c_int64), n, _ptr(gj, C.c_int32), _ptr(sj, C.c_int32),
@@ -181,6 +233,61 @@ class HybridGrid:
     def close(self):
         if getattr(self, "handle", None):
             self._lib.csm_hybrid_grid_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IntensityHybridGrid:
+    """An IntensityHybridGrid on the device (csm_intensity_grid): empty when
+    made, filled by :meth:`HybridGrid.insert` / :meth:`HybridGrid.insert_batch`."""
+
+    def __init__(self, resolution: float, context: Optional[Context] = None):
+        self.context = context or default_context()
+        self._lib = self.context._lib
+        self.resolution = float(resolution)
+        h = C.c_void_p()
+        _check(self._lib.csm_intensity_grid_create(self.context.handle, self.resolution,
+                                                   C.byref(h)), "csm_intensity_grid_create")
+        self.handle = h
+
+    def device_bytes(self) -> int:
+        return int(self._lib.csm_intensity_grid_device_bytes(self.handle))
+
+    def info(self):
+        """(origin, dims, grid_size) of the box of the cells with count > 0."""
+        o, d, g = (C.c_int32 * 3)(), (C.c_int32 * 3)(), C.c_int32()
+        _check(self._lib.csm_intensity_grid_info(self.handle, o, d, C.byref(g)),
+               "csm_intensity_grid_info")
+        return tuple(o), tuple(d), g.value
+
+    def read(self):
+        """(sums float32, counts int32), each indexed [z, y, x] over the box
+        :meth:`info` reports (csm_intensity_grid_read); waits for the device."""
+        _, d, _ = self.info()
+        sums = np.zeros((d[2], d[1], d[0]), np.float32)
+        counts = np.zeros((d[2], d[1], d[0]), np.int32)
+        _check(self._lib.csm_intensity_grid_read(self.handle, _ptr(sums, C.c_float),
+                                                 _ptr(counts, C.c_int32), sums.size),
+               "csm_intensity_grid_read")
+        return sums, counts
+
+    def get_intensity(self, indices):
+        """IntensityHybridGrid::GetIntensity at cell indices (n, 3), on the device."""
+        idx = np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3))
+        out = np.zeros(len(idx), np.float32)
+        _check(self._lib.csm_intensity_grid_get_intensity(self.handle, _ptr(idx, C.c_int32),
+                                                          len(idx), _ptr(out, C.c_float)),
+               "csm_intensity_grid_get_intensity")
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.csm_intensity_grid_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -498,15 +605,28 @@ def match_batch_3d(matchers: Sequence[FastCorrelativeScanMatcher3D], nodes: Sequ
 
 
 def ceres_refine_batch_3d(grids: Sequence[HybridGrid], nodes: Sequence[NodeData3D], items,
-                          options=None, context: Optional[Context] = None):
+                          options=None, context: Optional[Context] = None,
+                          intensity_grids: Optional[Sequence[IntensityHybridGrid]] = None,
+                          node_intensities=None, intensity_options=None):
     """CeresScanMatcher3D::Match on the device for each item
     (high_grid, low_grid, node, initial ((t), (w, x, y, z)), target (t))
-    (ceres_scan_matcher_3d.cc:84-160): returns ([((t), (q)), ...], iterations)."""
-    from . import CeresOptions3D, Refine3D
+    (ceres_scan_matcher_3d.cc:84-160): returns ([((t), (q)), ...], iterations).
+
+    With ``intensity_grids`` (csm_ceres3d_refine_intensity_batch) an item may
+    carry a sixth entry, the index of its intensity grid (None or -1: none):
+    the match then has the IntensityCostFunction3D block under the Huber loss
+    on the high-resolution cloud. ``node_intensities``: per node the
+    intensities of its high-resolution cloud, or None; ``intensity_options``:
+    CeresIntensityOptions3D or (weight, huber_scale, intensity_threshold)."""
+    from . import CeresIntensityOptions3D, CeresOptions3D, Refine3D
     ctx = context or (grids[0].context if grids else default_context())
     n = len(items)
     citems = (Refine3D * max(n, 1))()
-    for i, (hg, lg, nd, init, target) in enumerate(items):
+    igrid = np.full(max(n, 1), -1, np.int32)
+    for i, item in enumerate(items):
+        hg, lg, nd, init, target = item[:5]
+        if len(item) > 5 and item[5] is not None:
+            igrid[i] = int(item[5])
         citems[i].high_grid, citems[i].low_grid, citems[i].node = hg, lg, nd
         citems[i].initial = _pose(init)
         for a in range(3):
@@ -516,11 +636,50 @@ def ceres_refine_batch_3d(grids: Sequence[HybridGrid], nodes: Sequence[NodeData3
     out = (Pose3D * max(n, 1))()
     iters = np.zeros(max(n, 1), np.int32)
     opts = options or CeresOptions3D.make()
+    if intensity_grids is not None:
+        FP = C.POINTER(C.c_float)
+        vals = [None if v is None else np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1))
+                for v in (node_intensities if node_intensities is not None else [None] * len(nodes))]
+        for v, node in zip(vals, nodes):
+            if v is not None and len(v) != len(_f32_points(node.high_resolution_point_cloud)):
+                raise ValueError("a node's intensities and high-resolution cloud differ in length")
+        vptr = (FP * max(len(nodes), 1))(*[FP() if v is None else _ptr(v, C.c_float) for v in vals])
+        ihandles = (C.c_void_p * max(len(intensity_grids), 1))(
+            *[g.handle for g in intensity_grids])
+        io = intensity_options
+        if io is not None and not isinstance(io, CeresIntensityOptions3D):
+            io = CeresIntensityOptions3D(*[float(v) for v in io])
+        _check(ctx._lib.csm_ceres3d_refine_intensity_batch(
+            ctx.handle, handles, len(grids), ihandles, len(intensity_grids), cnodes, vptr,
+            len(nodes), citems, _ptr(igrid, C.c_int32), n, C.byref(opts),
+            None if io is None else C.byref(io), out, _ptr(iters, C.c_int32)),
+            "csm_ceres3d_refine_intensity_batch")
+        return [out[i].as_tuple() for i in range(n)], iters[:n]
     _check(ctx._lib.csm_ceres3d_refine_batch(ctx.handle, handles, len(grids), cnodes, len(nodes),
                                              citems, n, C.byref(opts), out,
                                              _ptr(iters, C.c_int32)),
            "csm_ceres3d_refine_batch")
     return [out[i].as_tuple() for i in range(n)], iters[:n]
+
+
+def ceres_intensity_evaluate_3d(grid: IntensityHybridGrid, points, intensities, pose,
+                                scaling_factor: float, intensity_threshold: float):
+    """IntensityCostFunction3D alone at ``pose`` ((t), (w, x, y, z)) through the
+    refinement's device functions (csm_ceres3d_intensity_evaluate, test-visible):
+    (residuals (n,), Jacobian (n, 6) in the tangent space), without the loss."""
+    pts = _f32_points(points)
+    v = np.ascontiguousarray(np.asarray(intensities, np.float32).reshape(-1))
+    if len(v) != len(pts):
+        raise ValueError("points and intensities differ in length")
+    p = np.ascontiguousarray(np.concatenate([np.asarray(pose[0], np.float64),
+                                             np.asarray(pose[1], np.float64)]))
+    r = np.zeros(len(pts), np.float64)
+    jac = np.zeros((len(pts), 6), np.float64)
+    _check(grid._lib.csm_ceres3d_intensity_evaluate(
+        grid.handle, _ptr(pts, C.c_float), _ptr(v, C.c_float), len(pts), _ptr(p, C.c_double),
+        float(scaling_factor), float(np.float32(intensity_threshold)), _ptr(r, C.c_double),
+        _ptr(jac, C.c_double)), "csm_ceres3d_intensity_evaluate")
+    return r, jac
 
 
 # --------------------------------------------------------------------------

@@ -33,6 +33,9 @@ class RangeData:
     origin: np.ndarray                       # (3,)
     returns: np.ndarray                      # (n, 3)
     misses: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
+    # returns.intensities() (sensor/point_cloud.h:46-58): None, or (n,). Read by
+    # the 3D inserter only.
+    intensities: Optional[np.ndarray] = None
 
 
 @dataclass

@@ -1,9 +1,11 @@
 """Submap3D, ActiveSubmaps3D and RangeDataInserter3D on device-resident
 HybridGrids (reference mapping/3d/submap_3d.{h,cc},
 range_data_inserter_3d.{h,cc}): the Python mirror of
-include/cartographer_amd/submap_3d.h. The intensity grid
-(IntensityHybridGrid, range_data_inserter_3d.cc:76-89) is not kept: no matcher
-here reads it."""
+include/cartographer_amd/submap_3d.h. With ``use_intensities`` a submap also
+keeps its high-resolution IntensityHybridGrid (range_data_inserter_3d.cc:76-89,
+submap_3d.cc:332-339), filled in the same batch call as its HybridGrids, read
+by :class:`CeresScanMatcher3D` and forgotten when the submap leaves the active
+pair (submap_3d.cc:396-405)."""
 from __future__ import annotations
 
 import math
@@ -13,7 +15,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import Context, default_context
-from .matching3d import HybridGrid, rotate_histogram
+from .matching3d import (HybridGrid, IntensityHybridGrid, NodeData3D, ceres_refine_batch_3d,
+                         rotate_histogram)
 from .submap_2d import RangeData
 
 
@@ -24,16 +27,19 @@ class RangeDataInserterOptions3D:
     hit_probability: float = 0.55
     miss_probability: float = 0.49
     num_free_space_voxels: int = 2
+    intensity_threshold: float = 40.0
 
 
 @dataclass
 class SubmapsOptions3D:
-    """proto::SubmapsOptions3D; defaults from trajectory_builder_3d.lua:92-104."""
+    """proto::SubmapsOptions3D; defaults from trajectory_builder_3d.lua:92-104.
+    ``use_intensities`` is LocalTrajectoryBuilderOptions3D's (:109-112, false)."""
     high_resolution: float = 0.10
     high_resolution_max_range: float = 20.0
     low_resolution: float = 0.45
     num_range_data: int = 160
     range_data_inserter_options: Optional[RangeDataInserterOptions3D] = None
+    use_intensities: bool = False
 
 
 # Rigid3d pieces in double, with Eigen's operation order.
@@ -72,12 +78,19 @@ class RangeDataInserter3D:
         o = self.options
         return o.hit_probability, o.miss_probability, o.num_free_space_voxels
 
-    def Insert(self, range_data: RangeData, grid: HybridGrid) -> None:
-        grid.insert(range_data.origin, range_data.returns, *self._args())
+    def Insert(self, range_data: RangeData, grid: HybridGrid,
+               intensity_grid: Optional[IntensityHybridGrid] = None) -> None:
+        """Insert(range_data, hybrid_grid, intensity_hybrid_grid or nullptr)."""
+        grid.insert(range_data.origin, range_data.returns, *self._args(),
+                    intensity_grid=intensity_grid, intensities=range_data.intensities,
+                    intensity_threshold=self.options.intensity_threshold)
 
-    def InsertBatch(self, grids: Sequence[HybridGrid], scans, jobs) -> None:
+    def InsertBatch(self, grids: Sequence[HybridGrid], scans, jobs,
+                    intensity_grids: Optional[Sequence[IntensityHybridGrid]] = None) -> None:
         """HybridGrid.insert_batch with this inserter's options."""
-        HybridGrid.insert_batch(grids, scans, jobs, *self._args())
+        HybridGrid.insert_batch(grids, scans, jobs, *self._args(),
+                                intensity_grids=intensity_grids or None,
+                                intensity_threshold=self.options.intensity_threshold)
 
 
 class Submap3D:
@@ -85,13 +98,16 @@ class Submap3D:
     and the accumulated rotational scan matcher histogram."""
 
     def __init__(self, high_resolution: float, low_resolution: float, local_pose,
-                 histogram_size: int, context: Optional[Context] = None):
+                 histogram_size: int, context: Optional[Context] = None,
+                 use_intensities: bool = False):
         t, q = local_pose
         self._local_pose = (tuple(float(v) for v in t), tuple(float(v) for v in q))
         ctx = context or default_context()
         empty = np.zeros((0, 3), np.int32), np.zeros(0, np.uint16)
         self._high = HybridGrid(high_resolution, *empty, context=ctx)
         self._low = HybridGrid(low_resolution, *empty, context=ctx)
+        self._high_intensity = (IntensityHybridGrid(high_resolution, context=ctx)
+                                if use_intensities else None)
         self._histogram = np.zeros(histogram_size, np.float32)
         self._num_range_data = 0
         self._insertion_finished = False
@@ -104,6 +120,15 @@ class Submap3D:
 
     def low_resolution_hybrid_grid(self) -> HybridGrid:
         return self._low
+
+    def high_resolution_intensity_hybrid_grid(self) -> Optional[IntensityHybridGrid]:
+        """None without use_intensities and once forgotten."""
+        return self._high_intensity
+
+    def ForgetIntensityHybridGrid(self) -> None:
+        if self._high_intensity is not None:
+            self._high_intensity.close()
+            self._high_intensity = None
 
     def rotational_scan_matcher_histogram(self) -> np.ndarray:
         return self._histogram
@@ -119,10 +144,13 @@ class Submap3D:
         t, q = _inverse(*self._local_pose)
         return ([float(np.float32(v)) for v in t], [float(np.float32(v)) for v in q])
 
-    def _jobs(self, first_grid: int, scan: int, high_resolution_max_range: float):
-        """The two batch jobs of InsertData (submap_3d.cc:329-339)."""
+    def _jobs(self, first_grid: int, scan: int, high_resolution_max_range: float,
+              intensity_grid: Optional[int] = None):
+        """The two batch jobs of InsertData (submap_3d.cc:329-339); the
+        high-resolution one fills intensity grid ``intensity_grid`` too."""
         tf = self._submap_from_local()
-        return [(first_grid, scan, tf, high_resolution_max_range), (first_grid + 1, scan, tf, None)]
+        return [(first_grid, scan, tf, high_resolution_max_range, intensity_grid),
+                (first_grid + 1, scan, tf, None, None)]
 
     def _after_insert(self, local_from_gravity_aligned, scan_histogram_in_gravity) -> None:
         """submap_3d.cc:340-346."""
@@ -137,9 +165,12 @@ class Submap3D:
                    high_resolution_max_range: float, local_from_gravity_aligned,
                    scan_histogram_in_gravity) -> None:
         assert not self._insertion_finished  # submap_3d.cc:328
+        kept = self._high_intensity is not None
         inserter.InsertBatch([self._high, self._low],
-                             [(range_data_in_local.origin, range_data_in_local.returns)],
-                             self._jobs(0, 0, high_resolution_max_range))
+                             [(range_data_in_local.origin, range_data_in_local.returns,
+                               range_data_in_local.intensities)],
+                             self._jobs(0, 0, high_resolution_max_range, 0 if kept else None),
+                             [self._high_intensity] if kept else None)
         self._after_insert(local_from_gravity_aligned, scan_histogram_in_gravity)
 
     def Finish(self) -> None:
@@ -166,10 +197,11 @@ class ActiveSubmaps3D:
     def AddSubmap(self, local_submap_pose, histogram_size: int) -> None:
         if len(self._submaps) >= 2:
             assert self._submaps[0].insertion_finished()  # :397
+            self._submaps[0].ForgetIntensityHybridGrid()  # :399-404
             self._submaps.pop(0)
         o = self.options
         self._submaps.append(Submap3D(o.high_resolution, o.low_resolution, local_submap_pose,
-                                      histogram_size, self.context))
+                                      histogram_size, self.context, o.use_intensities))
 
     def InsertData(self, range_data: RangeData, local_from_gravity_aligned,
                    rotational_scan_matcher_histogram_in_gravity) -> List[Submap3D]:
@@ -178,14 +210,74 @@ class ActiveSubmaps3D:
         if not self._submaps or self._submaps[-1].num_range_data() == o.num_range_data:
             origin = np.asarray(range_data.origin, np.float32)
             self.AddSubmap(([float(v) for v in origin], local_from_gravity_aligned), len(hist))
-        grids, jobs = [], []
+        grids, jobs, intensity_grids = [], [], []
         for s in self._submaps:
             assert not s.insertion_finished()
-            jobs += s._jobs(len(grids), 0, o.high_resolution_max_range)
+            kept = s.high_resolution_intensity_hybrid_grid()
+            jobs += s._jobs(len(grids), 0, o.high_resolution_max_range,
+                            len(intensity_grids) if kept is not None else None)
             grids += [s.high_resolution_hybrid_grid(), s.low_resolution_hybrid_grid()]
-        self.range_data_inserter.InsertBatch(grids, [(range_data.origin, range_data.returns)], jobs)
+            if kept is not None:
+                intensity_grids.append(kept)
+        self.range_data_inserter.InsertBatch(
+            grids, [(range_data.origin, range_data.returns, range_data.intensities)], jobs,
+            intensity_grids)
         for s in self._submaps:
             s._after_insert(local_from_gravity_aligned, hist)
         if self._submaps[0].num_range_data() == 2 * o.num_range_data:
             self._submaps[0].Finish()
         return self.submaps()
+
+
+@dataclass
+class IntensityCostFunctionOptions:
+    """proto::IntensityCostFunctionOptions; defaults from trajectory_builder_3d.lua:47-51."""
+    weight: float = 0.5
+    huber_scale: float = 0.3
+    intensity_threshold: float = 40.0
+
+
+@dataclass
+class CeresScanMatcherOptions3D:
+    """proto::CeresScanMatcherOptions3D; defaults from trajectory_builder_3d.lua:44-60."""
+    occupied_space_weight_0: float = 1.0
+    occupied_space_weight_1: float = 6.0
+    intensity_cost_function_options_0: Optional[IntensityCostFunctionOptions] = None
+    translation_weight: float = 5.0
+    rotation_weight: float = 4e2
+    use_nonmonotonic_steps: bool = False
+    max_num_iterations: int = 12
+
+
+class CeresScanMatcher3D:
+    """ceres_scan_matcher_3d.h:44-64 on device grids, for the two pairs
+    LocalTrajectoryBuilder3D::ScanMatch passes (local_trajectory_builder_3d.cc:
+    488-501): (high-resolution cloud, HybridGrid, IntensityHybridGrid or None)
+    and (low-resolution cloud, HybridGrid, None)."""
+
+    def __init__(self, options: Optional[CeresScanMatcherOptions3D] = None):
+        self.options = options or CeresScanMatcherOptions3D()
+
+    def Match(self, target_translation, initial_pose_estimate, point_clouds_and_hybrid_grids,
+              intensities=None):
+        """Returns (pose ((t), (w, x, y, z)), iterations). ``intensities``: those
+        of the first (high-resolution) cloud, needed when its pair has an
+        intensity grid."""
+        from . import CeresOptions3D
+        (high_cloud, high, intensity_grid), (low_cloud, low, none) = point_clouds_and_hybrid_grids
+        if none is not None:
+            raise ValueError("only the first pair may have an intensity grid")
+        o = self.options
+        io = o.intensity_cost_function_options_0 or IntensityCostFunctionOptions()
+        node = NodeData3D(high_cloud, low_cloud, np.zeros(0, np.float32))
+        item = (0, 1, 0, initial_pose_estimate, target_translation,
+                0 if intensity_grid is not None else None)
+        poses, iters = ceres_refine_batch_3d(
+            [high, low], [node], [item],
+            CeresOptions3D.make(o.occupied_space_weight_0, o.occupied_space_weight_1,
+                                o.translation_weight, o.rotation_weight, o.max_num_iterations,
+                                o.use_nonmonotonic_steps),
+            intensity_grids=[intensity_grid] if intensity_grid is not None else [],
+            node_intensities=[intensities],
+            intensity_options=(io.weight, io.huber_scale, io.intensity_threshold))
+        return poses[0], int(iters[0])

@@ -40,11 +40,18 @@ struct Rigid2d {
 // sensor::PointCloud: RangefinderPoint positions, xyz floats.
 struct PointCloud {
   std::vector<float> xyz;  // 3 floats per point
+  // sensor::PointCloud::intensities() (point_cloud.h:46-58): empty, or one
+  // value per point. Only the 3D inserter and CeresScanMatcher3D read them.
+  std::vector<float> intensities;
   size_t size() const { return xyz.size() / 3; }
   void push_back(float x, float y, float z) {
     xyz.push_back(x);
     xyz.push_back(y);
     xyz.push_back(z);
+  }
+  void push_back(float x, float y, float z, float intensity) {
+    push_back(x, y, z);
+    intensities.push_back(intensity);
   }
 };
 

@@ -5,6 +5,8 @@
 //   constraint_builder_3d.cc:221-223  MatchFullSubmap(node_rot, submap_rot, data, min)
 //   constraint_builder_3d.cc:239-241  Match(node_pose, submap_pose, data, min)
 //   local_trajectory_builder_3d.cc:481  RealTimeCorrelativeScanMatcher3D::Match
+//   local_trajectory_builder_3d.cc:488-501  CeresScanMatcher3D::Match, with the
+//                                       intensity grid when use_intensities
 //
 // The reference types (HybridGrid, TrajectoryNode::Data, transform::Rigid3d,
 // Eigen::Quaterniond, the option protos) are represented by the POD views
@@ -216,6 +218,95 @@ class RealTimeCorrelativeScanMatcher3D {
 
  private:
   csm_rt_options options_;
+};
+
+// proto::IntensityCostFunctionOptions (trajectory_builder_3d.lua:47-51
+// defaults).
+struct IntensityCostFunctionOptions {
+  double weight = 0.5;
+  double huber_scale = 0.3;
+  double intensity_threshold = 40.;
+};
+
+// proto::CeresScanMatcherOptions3D (trajectory_builder_3d.lua:44-60 defaults).
+struct CeresScanMatcherOptions3D {
+  double occupied_space_weight_0 = 1.;
+  double occupied_space_weight_1 = 6.;
+  IntensityCostFunctionOptions intensity_cost_function_options_0;
+  double translation_weight = 5.;
+  double rotation_weight = 4e2;
+  bool use_nonmonotonic_steps = false;
+  int max_num_iterations = 12;
+};
+
+// ceres_scan_matcher_3d.h:37-42, on device grids (HybridGrid::handle(),
+// IntensityHybridGrid::handle() of submap_3d.h, HybridGrid3D::handle()).
+struct PointCloudAndHybridGridsPointers {
+  const PointCloud* point_cloud;
+  const csm_hybrid_grid* hybrid_grid;
+  const csm_intensity_grid* intensity_hybrid_grid;  // optional
+};
+
+// ceres_scan_matcher_3d.h:44-64 for the two pairs LocalTrajectoryBuilder3D and
+// ConstraintBuilder3D pass: (high-resolution cloud, high-resolution grid,
+// intensity grid or null) and (low-resolution cloud, low-resolution grid, null).
+class CeresScanMatcher3D {
+ public:
+  explicit CeresScanMatcher3D(const CeresScanMatcherOptions3D& options) : options_(options) {}
+
+  // Returns the number of solver iterations in place of the summary.
+  int Match(const double target_translation[3], const Rigid3d& initial_pose_estimate,
+            const std::vector<PointCloudAndHybridGridsPointers>& point_clouds_and_hybrid_grids,
+            Rigid3d* pose_estimate, csm_context* context = nullptr) const {
+    const auto& p = point_clouds_and_hybrid_grids;
+    CheckOk(p.size() == 2 && p[0].point_cloud && p[1].point_cloud && p[0].hybrid_grid &&
+                    p[1].hybrid_grid && !p[1].intensity_hybrid_grid
+                ? CSM_OK
+                : CSM_EINVAL,
+            "CeresScanMatcher3D::Match");
+    const csm_hybrid_grid* grids[2] = {p[0].hybrid_grid, p[1].hybrid_grid};
+    csm_node3d node{};
+    node.high_resolution_xyz = p[0].point_cloud->xyz.data();
+    node.num_high_resolution = static_cast<int32_t>(p[0].point_cloud->size());
+    node.low_resolution_xyz = p[1].point_cloud->xyz.data();
+    node.num_low_resolution = static_cast<int32_t>(p[1].point_cloud->size());
+    node.gravity_alignment[0] = 1.;
+    csm_refine3d item{};
+    item.high_grid = 0;
+    item.low_grid = 1;
+    item.node = 0;
+    item.initial = initial_pose_estimate.ToC();
+    for (int a = 0; a < 3; ++a) item.target[a] = target_translation[a];
+    const csm_ceres3d_options o{options_.occupied_space_weight_0,
+                                options_.occupied_space_weight_1, options_.translation_weight,
+                                options_.rotation_weight, options_.max_num_iterations,
+                                options_.use_nonmonotonic_steps ? 1 : 0};
+    const IntensityCostFunctionOptions& io = options_.intensity_cost_function_options_0;
+    const csm_ceres3d_intensity_options intensity{io.weight, io.huber_scale,
+                                                  io.intensity_threshold};
+    const csm_intensity_grid* intensity_grid = p[0].intensity_hybrid_grid;
+    // A cloud without intensities has no intensity block to add.
+    const float* intensities =
+        p[0].point_cloud->intensities.empty() ? nullptr : p[0].point_cloud->intensities.data();
+    CheckOk(intensities == nullptr ||
+                    p[0].point_cloud->intensities.size() == p[0].point_cloud->size()
+                ? CSM_OK
+                : CSM_EINVAL,
+            "CeresScanMatcher3D::Match intensities");
+    const int32_t grid_of_item = intensity_grid ? 0 : -1;
+    csm_pose3d out{};
+    int32_t iterations = 0;
+    CheckOk(csm_ceres3d_refine_intensity_batch(
+                context ? context : ThreadContext(), grids, 2, &intensity_grid,
+                intensity_grid ? 1 : 0, &node, &intensities, 1, &item, &grid_of_item, 1, &o,
+                &intensity, &out, &iterations),
+            "CeresScanMatcher3D::Match");
+    *pose_estimate = Rigid3d::FromC(out);
+    return iterations;
+  }
+
+ private:
+  CeresScanMatcherOptions3D options_;
 };
 
 }  // namespace cartographer_amd

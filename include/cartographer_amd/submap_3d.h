@@ -4,13 +4,17 @@
 //   submap_3d.h:119-152     ActiveSubmaps3D::InsertData, AddSubmap (.cc:362-416)
 //   range_data_inserter_3d.h:35-51  RangeDataInserter3D::Insert (.cc:109-137)
 //   hybrid_grid.h:463-545   HybridGrid
+//   hybrid_grid.h:547-571   IntensityHybridGrid
 //
 // The grids live on the device: Insert updates and grows them there with the
 // reference's values bit for bit, and the 3D matchers read them without a host
 // copy (FastMatcherFor, MatchRealTime below). One batch call per scan covers
-// every grid of the active submaps. The intensity grid (IntensityHybridGrid,
-// range_data_inserter_3d.cc:76-89, submap_3d.cc high_resolution_intensity_
-// hybrid_grid) is not kept: no matcher here reads it. As in the reference,
+// every grid of the active submaps. With use_intensities a submap also keeps
+// its high_resolution_intensity_hybrid_grid() (range_data_inserter_3d.cc:76-89,
+// submap_3d.cc:332-339), filled in the same batch call, read by
+// CeresScanMatcher3D::Match (scan_matching_3d.h) and forgotten when the submap
+// leaves the active pair (submap_3d.cc:396-405); without it nothing is
+// allocated for intensities. As in the reference,
 // matchers are built from finished submaps only: a submap must not be
 // inserted into while a FastMatcherFor result built from it is alive.
 // Negative return codes abort like the reference's CHECKs.
@@ -26,12 +30,13 @@
 
 namespace cartographer_amd {
 
-// proto::RangeDataInserterOptions3D (trajectory_builder_3d.lua:97-104
-// defaults), without the intensity threshold.
+// proto::RangeDataInserterOptions3D (trajectory_builder_3d.lua:100-106
+// defaults).
 struct RangeDataInserterOptions3D {
   float hit_probability = 0.55f;
   float miss_probability = 0.49f;
   int num_free_space_voxels = 2;
+  float intensity_threshold = 40.f;
 };
 
 // hybrid_grid.h:463-545: RAII holder of a device grid that starts empty.
@@ -68,12 +73,58 @@ class HybridGrid {
   csm_hybrid_grid* handle_ = nullptr;
 };
 
+// hybrid_grid.h:547-571: RAII holder of a device intensity grid that starts
+// empty.
+class IntensityHybridGrid {
+ public:
+  explicit IntensityHybridGrid(float resolution, csm_context* context = nullptr)
+      : context_(context ? context : ThreadContext()) {
+    CheckOk(csm_intensity_grid_create(context_, resolution, &handle_), "IntensityHybridGrid");
+  }
+  ~IntensityHybridGrid() { csm_intensity_grid_destroy(handle_); }
+  IntensityHybridGrid(const IntensityHybridGrid&) = delete;
+  IntensityHybridGrid& operator=(const IntensityHybridGrid&) = delete;
+
+  // The box of the cells with count > 0 and DynamicGrid::grid_size().
+  void info(int32_t origin[3], int32_t dims[3], int32_t* grid_size) const {
+    CheckOk(csm_intensity_grid_info(handle_, origin, dims, grid_size),
+            "IntensityHybridGrid::info");
+  }
+  // The sums and counts over that box, x fastest (waits for the device).
+  void read(std::vector<float>* sums, std::vector<int32_t>* counts) const {
+    int32_t o[3], d[3], gs;
+    info(o, d, &gs);
+    const size_t n = static_cast<size_t>(d[0]) * d[1] * d[2];
+    sums->assign(n, 0.f);
+    counts->assign(n, 0);
+    CheckOk(csm_intensity_grid_read(handle_, sums->data(), counts->data(),
+                                    static_cast<int64_t>(n)),
+            "IntensityHybridGrid::read");
+  }
+  // GetIntensity at one cell (waits for the device).
+  float GetIntensity(int32_t x, int32_t y, int32_t z) const {
+    const int32_t index[3] = {x, y, z};
+    float out = 0.f;
+    CheckOk(csm_intensity_grid_get_intensity(handle_, index, 1, &out),
+            "IntensityHybridGrid::GetIntensity");
+    return out;
+  }
+
+  csm_intensity_grid* handle() const { return handle_; }
+  csm_context* context() const { return context_; }
+
+ private:
+  csm_context* context_;
+  csm_intensity_grid* handle_ = nullptr;
+};
+
 // range_data_inserter_3d.h:35-51
 class RangeDataInserter3D {
  public:
   explicit RangeDataInserter3D(const RangeDataInserterOptions3D& options)
       : options_{options.hit_probability, options.miss_probability,
-                 options.num_free_space_voxels} {}
+                 options.num_free_space_voxels},
+        intensity_threshold_(options.intensity_threshold) {}
 
   // Insert(range_data, hybrid_grid, nullptr): range_data in the grid's frame.
   void Insert(const RangeData& range_data, HybridGrid* grid) const {
@@ -83,10 +134,29 @@ class RangeDataInserter3D {
             "RangeDataInserter3D::Insert");
   }
 
+  // Insert(range_data, hybrid_grid, intensity_hybrid_grid); the latter may be
+  // null, and a cloud without intensities leaves it alone.
+  void Insert(const RangeData& range_data, HybridGrid* grid,
+              IntensityHybridGrid* intensity_grid) const {
+    const PointCloud& returns = range_data.returns;
+    CheckOk(returns.intensities.empty() || returns.intensities.size() == returns.size()
+                ? CSM_OK
+                : CSM_EINVAL,
+            "RangeDataInserter3D::Insert intensities");
+    CheckOk(csm_hybrid_grid_insert_intensities(
+                grid->handle(), intensity_grid ? intensity_grid->handle() : nullptr, &options_,
+                intensity_threshold_, range_data.origin, returns.xyz.data(),
+                returns.intensities.empty() ? nullptr : returns.intensities.data(),
+                static_cast<int32_t>(returns.size())),
+            "RangeDataInserter3D::Insert");
+  }
+
   const csm_inserter3d_options& options() const { return options_; }
+  float intensity_threshold() const { return intensity_threshold_; }
 
  private:
   csm_inserter3d_options options_;
+  float intensity_threshold_;
 };
 
 namespace submap_3d_internal {
@@ -119,15 +189,23 @@ inline Rigid3d Inverse(const Rigid3d& r) {
 class Submap3D {
  public:
   Submap3D(float high_resolution, float low_resolution, const Rigid3d& local_submap_pose,
-           int rotational_scan_matcher_histogram_size, csm_context* context = nullptr)
+           int rotational_scan_matcher_histogram_size, csm_context* context = nullptr,
+           bool use_intensities = false)
       : local_pose_(local_submap_pose),
         high_(new HybridGrid(high_resolution, context)),
         low_(new HybridGrid(low_resolution, context)),
+        high_intensity_(use_intensities ? new IntensityHybridGrid(high_resolution, context)
+                                        : nullptr),
         histogram_(rotational_scan_matcher_histogram_size, 0.f) {}
 
   const Rigid3d& local_pose() const { return local_pose_; }
   const HybridGrid& high_resolution_hybrid_grid() const { return *high_; }
   const HybridGrid& low_resolution_hybrid_grid() const { return *low_; }
+  // submap_3d.h:73-82: null without use_intensities and once forgotten.
+  const IntensityHybridGrid* high_resolution_intensity_hybrid_grid() const {
+    return high_intensity_.get();
+  }
+  void ForgetIntensityHybridGrid() { high_intensity_.reset(); }
   const std::vector<float>& rotational_scan_matcher_histogram() const { return histogram_; }
   int num_range_data() const { return num_range_data_; }
   bool insertion_finished() const { return insertion_finished_; }
@@ -151,7 +229,9 @@ class Submap3D {
   // InsertData of the same scan for several submaps of one context: one
   // csm_hybrid_grid_insert_batch call, two jobs (high resolution with the
   // range filter, low resolution without) per submap, each with the submap's
-  // local_pose().inverse().cast<float>().
+  // local_pose().inverse().cast<float>(). When a submap keeps an intensity
+  // grid the call is csm_hybrid_grid_insert_intensities_batch and the
+  // high-resolution job fills that grid too.
   static void InsertBatch(const std::vector<Submap3D*>& submaps, const RangeData& range_data,
                           const RangeDataInserter3D& range_data_inserter,
                           float high_resolution_max_range,
@@ -159,7 +239,8 @@ class Submap3D {
                           const std::vector<float>& scan_histogram_in_gravity) {
     if (submaps.empty()) return;
     std::vector<csm_hybrid_grid*> grids;
-    std::vector<int32_t> grid_of_job, scan_of_job, transform_of_job;
+    std::vector<csm_intensity_grid*> intensity_grids;
+    std::vector<int32_t> grid_of_job, scan_of_job, transform_of_job, intensity_grid_of_job;
     std::vector<float> transforms, max_ranges;
     for (size_t s = 0; s < submaps.size(); ++s) {
       Submap3D* submap = submaps[s];
@@ -176,16 +257,42 @@ class Submap3D {
         scan_of_job.push_back(0);
         transform_of_job.push_back(static_cast<int32_t>(s));
         max_ranges.push_back(k == 0 ? high_resolution_max_range : 0.f);
+        if (k == 0 && submap->high_intensity_) {
+          intensity_grid_of_job.push_back(static_cast<int32_t>(intensity_grids.size()));
+          intensity_grids.push_back(submap->high_intensity_->handle());
+        } else {
+          intensity_grid_of_job.push_back(-1);
+        }
       }
     }
     const int64_t offsets[2] = {0, static_cast<int64_t>(range_data.returns.size())};
-    CheckOk(csm_hybrid_grid_insert_batch(
-                submaps[0]->high_->context(), grids.data(), static_cast<int32_t>(grids.size()),
-                &range_data_inserter.options(), 1, range_data.origin,
-                range_data.returns.xyz.data(), offsets, static_cast<int32_t>(grid_of_job.size()),
-                grid_of_job.data(), scan_of_job.data(), transforms.data(),
-                static_cast<int32_t>(submaps.size()), transform_of_job.data(), max_ranges.data()),
-            "Submap3D::InsertData");
+    const PointCloud& returns = range_data.returns;
+    if (intensity_grids.empty()) {
+      CheckOk(csm_hybrid_grid_insert_batch(
+                  submaps[0]->high_->context(), grids.data(), static_cast<int32_t>(grids.size()),
+                  &range_data_inserter.options(), 1, range_data.origin, returns.xyz.data(),
+                  offsets, static_cast<int32_t>(grid_of_job.size()), grid_of_job.data(),
+                  scan_of_job.data(), transforms.data(), static_cast<int32_t>(submaps.size()),
+                  transform_of_job.data(), max_ranges.data()),
+              "Submap3D::InsertData");
+    } else {
+      CheckOk(returns.intensities.empty() || returns.intensities.size() == returns.size()
+                  ? CSM_OK
+                  : CSM_EINVAL,
+              "Submap3D::InsertData intensities");
+      const float* intensities =
+          returns.intensities.empty() ? nullptr : returns.intensities.data();
+      CheckOk(csm_hybrid_grid_insert_intensities_batch(
+                  submaps[0]->high_->context(), grids.data(), static_cast<int32_t>(grids.size()),
+                  intensity_grids.data(), static_cast<int32_t>(intensity_grids.size()),
+                  &range_data_inserter.options(), range_data_inserter.intensity_threshold(), 1,
+                  range_data.origin, returns.xyz.data(), offsets, &intensities,
+                  static_cast<int32_t>(grid_of_job.size()), grid_of_job.data(),
+                  scan_of_job.data(), intensity_grid_of_job.data(), transforms.data(),
+                  static_cast<int32_t>(submaps.size()), transform_of_job.data(),
+                  max_ranges.data()),
+              "Submap3D::InsertData");
+    }
     for (Submap3D* submap : submaps) {
       ++submap->num_range_data_;
       // submap_3d.cc:341-346: the yaw in double, cast to float.
@@ -209,6 +316,7 @@ class Submap3D {
  private:
   Rigid3d local_pose_;
   std::unique_ptr<HybridGrid> high_, low_;
+  std::unique_ptr<IntensityHybridGrid> high_intensity_;
   std::vector<float> histogram_;
   int num_range_data_ = 0;
   bool insertion_finished_ = false;
@@ -221,6 +329,10 @@ struct SubmapsOptions3D {
   float low_resolution = 0.45f;
   int num_range_data = 160;
   RangeDataInserterOptions3D range_data_inserter_options;
+  // LocalTrajectoryBuilderOptions3D::use_intensities
+  // (trajectory_builder_3d.lua:109-112: false): keep and fill
+  // high_resolution_intensity_hybrid_grid() per submap.
+  bool use_intensities = false;
 };
 
 // submap_3d.h:119-152
@@ -259,12 +371,14 @@ class ActiveSubmaps3D {
   void AddSubmap(const Rigid3d& local_submap_pose, int rotational_scan_matcher_histogram_size) {
     if (submaps_.size() >= 2) {
       CheckOk(submaps_.front()->insertion_finished() ? CSM_OK : CSM_EINVAL, "AddSubmap");
+      // The active submaps' intensity grids are for scan matching only
+      // (submap_3d.cc:399-404).
+      submaps_.front()->ForgetIntensityHybridGrid();
       submaps_.erase(submaps_.begin());
     }
-    submaps_.push_back(std::make_shared<Submap3D>(options_.high_resolution,
-                                                  options_.low_resolution, local_submap_pose,
-                                                  rotational_scan_matcher_histogram_size,
-                                                  context_));
+    submaps_.push_back(std::make_shared<Submap3D>(
+        options_.high_resolution, options_.low_resolution, local_submap_pose,
+        rotational_scan_matcher_histogram_size, context_, options_.use_intensities));
   }
 
  private:

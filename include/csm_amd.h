@@ -351,6 +351,7 @@ int csm_rt2d_score_candidates_tsdf(csm_context* ctx, const csm_rt_options* optio
  * the indices with DynamicGrid's growth rule (128 << k, indices in
  * [-size/2, size/2)). The cells are copied. */
 typedef struct csm_hybrid_grid csm_hybrid_grid;
+typedef struct csm_intensity_grid csm_intensity_grid; /* below: device-resident IntensityHybridGrid */
 int csm_hybrid_grid_create(csm_context* ctx, float resolution, const int32_t* xyz_indices,
                            const uint16_t* values, int64_t count, int32_t grid_size,
                            csm_hybrid_grid** out);
@@ -590,6 +591,52 @@ int csm_ceres3d_refine_batch(csm_context* ctx, const csm_hybrid_grid* const* gri
                              const csm_refine3d* items, int64_t n,
                              const csm_ceres3d_options* options, csm_pose3d* out,
                              int32_t* iterations);
+
+/* CeresScanMatcher3D::Match as LocalTrajectoryBuilder3D::ScanMatch calls it
+ * with use_intensities (local_trajectory_builder_3d.cc:488-501):
+ * csm_ceres3d_refine_batch plus, for item i with intensity_grid_of_item[i] >=
+ * 0, an IntensityCostFunction3D block (intensity_cost_function_3d.h:67-85) on
+ * the high-resolution cloud (cloud 0 only) in
+ * intensity_grids[intensity_grid_of_item[i]], under ceres::HuberLoss
+ * (ceres_scan_matcher_3d.cc:126-142): residual k is 0 where the point's
+ * intensity is above the threshold and else weight / sqrt(N) * (I(T p_k) -
+ * intensity_k), I the InterpolatedGrid over GetIntensity (0 for cells without
+ * a return) and N the whole cloud's size. node_intensities[j] are the
+ * intensities of node j's high-resolution cloud (NULL: none;
+ * node_intensities NULL: no node has any). Items without a grid
+ * (intensity_grid_of_item NULL: all of them) run csm_ceres3d_refine_batch's
+ * arithmetic and return its result bit for bit; one call may mix both kinds.
+ * CSM_EINVAL, when any item has a grid: a weight, huber_scale or
+ * intensity_threshold that is not positive (the reference's CHECK_GTs,
+ * :127-130), an item whose node has no intensities, a non-finite intensity. A
+ * resolution that differs from the high-resolution grid's is allowed, as in
+ * the reference. Ceres is not part of this build: the Huber loss and the
+ * Corrector rule are restated from Ceres 1.13 and unpinned, like the solver
+ * loop. */
+typedef struct csm_ceres3d_intensity_options {
+  /* proto::IntensityCostFunctionOptions (ceres_scan_matcher_options_3d.proto). */
+  double weight;
+  double huber_scale;
+  double intensity_threshold;
+} csm_ceres3d_intensity_options;
+
+int csm_ceres3d_refine_intensity_batch(
+    csm_context* ctx, const csm_hybrid_grid* const* grids, int32_t num_grids,
+    const csm_intensity_grid* const* intensity_grids, int32_t num_intensity_grids,
+    const csm_node3d* nodes, const float* const* node_intensities, int32_t num_nodes,
+    const csm_refine3d* items, const int32_t* intensity_grid_of_item, int64_t n,
+    const csm_ceres3d_options* options, const csm_ceres3d_intensity_options* intensity_options,
+    csm_pose3d* out, int32_t* iterations);
+
+/* Test-visible, like csm_ceres2d_tsdf_evaluate: IntensityCostFunction3D alone
+ * (no loss, no other block) at pose (t, then q as w, x, y, z), through the
+ * device functions the refinement uses: residuals[n] and the row-major n x 6
+ * Jacobian in the tangent space (translation, then the rotation increment of
+ * ceres::QuaternionParameterization). Waits for the stream. */
+int csm_ceres3d_intensity_evaluate(const csm_intensity_grid* grid, const float* points_xyz,
+                                   const float* intensities, int32_t n, const double pose[7],
+                                   double scaling_factor, float intensity_threshold,
+                                   double* residuals, double* jacobian);
 
 /* ---- submap grid formats ---------------------------------------------------
  * Submap2D::Finish (submap_2d.cc:146-150) crops a finished submap's grid to
@@ -855,11 +902,12 @@ int csm_tsdf_round_trip_tables(float truncation_distance, float max_weight,
  * a live csm_fast3d was built from, or holds as its low-resolution grid, is
  * not supported. Calls that read a grid from another context's stream must
  * not overlap an insert into it. The intensity grid (IntensityHybridGrid,
- * range_data_inserter_3d.cc:76-89) is not kept: no matcher here reads it. */
+ * range_data_inserter_3d.cc:76-89) is a handle of its own, csm_intensity_grid
+ * below, filled by csm_hybrid_grid_insert_intensities*. */
 
 /* proto::RangeDataInserterOptions3D
- * (mapping/proto/range_data_inserter_options_3d.proto), without the intensity
- * threshold. */
+ * (mapping/proto/range_data_inserter_options_3d.proto); the intensity
+ * threshold is an argument of csm_hybrid_grid_insert_intensities*. */
 typedef struct csm_inserter3d_options {
   float hit_probability, miss_probability;
   int32_t num_free_space_voxels;
@@ -903,6 +951,70 @@ int csm_hybrid_grid_insert_batch(csm_context* ctx, csm_hybrid_grid* const* grids
                                  const int32_t* scan_of_job, const float* transforms,
                                  int32_t num_transforms, const int32_t* transform_of_job,
                                  const float* max_ranges);
+
+/* ---- device-resident IntensityHybridGrid ------------------------------------
+ * IntensityHybridGrid (hybrid_grid.h:547-571) in the shape csm_hybrid_grid has:
+ * a dense brick, x fastest, over the bounding box of the cells with count > 0,
+ * in two planes, the float sum and the int32 count of AverageIntensityData.
+ * The bricks come from the context's pool, every insert is enqueued on the
+ * context's stream and re-records the grid's ready event. create makes the
+ * empty grid (no device call); destroy is what ActiveSubmaps3D does when it
+ * forgets a finished submap's intensity grid (submap_3d.cc:396-405). */
+int csm_intensity_grid_create(csm_context* ctx, float resolution, csm_intensity_grid** out);
+void csm_intensity_grid_destroy(csm_intensity_grid* grid);
+/* The box of the cells with count > 0 (dims 0 while there is none) and the
+ * size DynamicGrid::Grow has reached (128 at first), exact after every insert. */
+int csm_intensity_grid_info(const csm_intensity_grid* grid, int32_t* origin3, int32_t* dims3,
+                            int32_t* grid_size);
+/* The sums and counts over that box, capacity >= nx * ny * nz each. Waits for
+ * the stream. */
+int csm_intensity_grid_read(const csm_intensity_grid* grid, float* sums_out, int32_t* counts_out,
+                            int64_t capacity);
+/* IntensityHybridGrid::GetIntensity at n cell indices, on the device: sum /
+ * count in one float division, 0 for a cell with count 0 or outside the box. */
+int csm_intensity_grid_get_intensity(const csm_intensity_grid* grid, const int32_t* xyz_indices,
+                                     int64_t n, float* out);
+int64_t csm_intensity_grid_device_bytes(const csm_intensity_grid* grid);
+
+/* RangeDataInserter3D::Insert(range_data, hybrid_grid, intensity_hybrid_grid)
+ * (range_data_inserter_3d.cc:117-137). The HybridGrid is updated by the code
+ * of csm_hybrid_grid_insert, so its bytes are the same. Then
+ * InsertIntensitiesIntoGrid (:76-89): every return with !(intensity >
+ * intensity_threshold) adds 1 to the count and its intensity to the sum of
+ * the cell intensity_grid's own GetCellIndex gives it (the two resolutions
+ * may differ, as in the reference). A cell's new sum is ((old + v_a) + v_b) +
+ * ... in float, a < b < ... the indices of its returns, as the reference's
+ * loop leaves it: the returns are sorted by cell on the device with their
+ * order kept and one thread adds a cell's run, so the result is the same on
+ * every run; no float atomic is used. intensities NULL (a cloud without
+ * intensities, :79) or intensity_grid NULL: the intensity grid is left alone.
+ * CSM_EINVAL also for a non-finite intensity or a NaN threshold, CSM_ERANGE
+ * also for an intensity brick past 2^31 cells; either leaves both grids as
+ * they were and enqueues nothing. */
+int csm_hybrid_grid_insert_intensities(csm_hybrid_grid* grid, csm_intensity_grid* intensity_grid,
+                                       const csm_inserter3d_options* options,
+                                       float intensity_threshold, const float origin_xyz[3],
+                                       const float* returns_xyz, const float* intensities,
+                                       int32_t num_returns);
+
+/* csm_hybrid_grid_insert_batch with intensities: scan s has the intensities
+ * scan_intensities[s][0 .. its number of returns), or none where that pointer
+ * (or scan_intensities itself) is NULL. Job k adds them to
+ * intensity_grids[intensity_grid_of_job[k]] (-1, or intensity_grid_of_job
+ * NULL: to none) after its transform and under its max_range mask, as
+ * PointCloud::copy_if keeps them (point_cloud.h:60-84). The intensity grids
+ * belong to ctx and are distinct, and within one call every job of an
+ * intensity grid names the same HybridGrid (a submap's high-resolution grid,
+ * submap_3d.cc:332-339): jobs on it are applied in array order with that
+ * grid's. */
+int csm_hybrid_grid_insert_intensities_batch(
+    csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_grids,
+    csm_intensity_grid* const* intensity_grids, int32_t num_intensity_grids,
+    const csm_inserter3d_options* options, float intensity_threshold, int32_t num_scans,
+    const float* origins_xyz, const float* returns_xyz, const int64_t* return_offsets,
+    const float* const* scan_intensities, int32_t num_jobs, const int32_t* grid_of_job,
+    const int32_t* scan_of_job, const int32_t* intensity_grid_of_job, const float* transforms,
+    int32_t num_transforms, const int32_t* transform_of_job, const float* max_ranges);
 
 /* The uint16 values of the device brick (x fastest) over the box
  * csm_hybrid_grid_info reports, capacity >= nx * ny * nz values: with the box

@@ -17,8 +17,14 @@ RealTimeCorrelativeScanMatcher3D::Match runs on the first submap's 0.1 m grid.
 Run at two sizes: a voxel-filtered scan (3000 returns) and a C4-sized one
 (55000). Also: one insert into a 0.1 m grid that grows the brick against the
 same insert repeated (no growth). Every timed window ends in a device
-synchronise; each leg is warmed up once and the two sides alternate. Prints
-one JSON line.
+synchronise; each leg is warmed up once and the two sides alternate.
+
+Intensities (`intensity_ms_<n>`): the same four-grid insert without and with
+intensity grids on the two 0.1 m grids (csm_hybrid_grid_insert_intensities_batch,
+seeded intensities in [0, 255], threshold 200), each window between two
+synchronises; and CeresScanMatcher3D on the first submap's grids for 16 poses
+around the true one (a 2000-point high-resolution cloud, 500 points low)
+without and with the intensity block. Prints one JSON line.
 
     python tools/insert3d_bench.py [--scans 8] [--repeats 3]
 """
@@ -160,6 +166,68 @@ def main():
         out[f"insert_ms_{n}"] = {"growing": 1e3 * statistics.median(p[0] for p in pairs),
                                  "not_growing": 1e3 * statistics.median(p[1] for p in pairs),
                                  "brick": list(pairs[0][2])}
+
+        vals = [rng.uniform(0.0, 255.0, n).astype(np.float32) for _ in scans]
+        ijobs = [(0, 0, tfs[0], MAX_RANGE, 0), (1, 0, tfs[0], None, None),
+                 (2, 0, tfs[1], MAX_RANGE, 1), (3, 0, tfs[1], None, None)]
+
+        def insert_leg(with_intensities):
+            grids = [csm.HybridGrid(r, *empty, context=ctx) for r in resolutions]
+            igrids = [csm.IntensityHybridGrid(HIGH, context=ctx) for _ in range(2)]
+            t = []
+            for scan, v in zip(scans, vals):
+                csm.synchronize(ctx)
+                t0 = time.perf_counter()
+                if with_intensities:
+                    csm.HybridGrid.insert_batch(grids, [scan + (v,)], ijobs, HIT, MISS, FREE,
+                                                intensity_grids=igrids, intensity_threshold=200.0)
+                else:
+                    csm.HybridGrid.insert_batch(grids, [scan], jobs, HIT, MISS, FREE)
+                csm.synchronize(ctx)
+                t.append(time.perf_counter() - t0)
+            return t, grids, igrids
+
+        insert_leg(True)
+        plain_t, with_t = [], []
+        for r in range(args.repeats):
+            plain_t += insert_leg(False)[0]
+            tw, grids, igrids = insert_leg(True)
+            with_t += tw
+        high = scans[-1][1][:: max(1, n // 2000)][:2000]
+        node = csm.NodeData3D(high, high[::4], np.zeros(0, np.float32))
+        node_vals = vals[-1][:: max(1, n // 2000)][:2000]
+        prng = np.random.default_rng(7)
+        items = []
+        for _ in range(16):
+            t = tuple(float(v) for v in np.asarray(tfs[0][0]) + prng.normal(0, 0.03, 3))
+            items.append((0, 1, 0, (t, tuple(tfs[0][1])), t))
+        copts = csm.CeresOptions3D.make(1.0, 6.0, 5.0, 4e2, 12)  # trajectory_builder_3d.lua:44-60
+
+        def refine_leg(with_block):
+            t0 = time.perf_counter()
+            if with_block:
+                csm.ceres_refine_batch_3d(grids, [node], [it + (0,) for it in items], copts,
+                                          intensity_grids=igrids, node_intensities=[node_vals],
+                                          intensity_options=(0.5, 0.3, 200.0))
+            else:
+                csm.ceres_refine_batch_3d(grids, [node], items, copts)
+            return time.perf_counter() - t0
+
+        refine_leg(False)
+        refine_leg(True)
+        ref_plain, ref_with = [], []
+        for r in range(max(5, args.repeats)):
+            ref_plain.append(refine_leg(False))
+            ref_with.append(refine_leg(True))
+
+        def spread(t):
+            return {"median": 1e3 * statistics.median(t), "min": 1e3 * min(t), "max": 1e3 * max(t)}
+
+        out[f"intensity_ms_{n}"] = {
+            "insert": spread(plain_t), "insert_with_intensities": spread(with_t),
+            "refine16": spread(ref_plain), "refine16_with_block": spread(ref_with),
+            "intensity_brick": list(igrids[0].info()[1]),
+            "intensity_returns": int(igrids[0].read()[1].sum())}
     print(json.dumps(out))
 
 
