@@ -30,10 +30,25 @@ namespace csm {
 // allocation that fails calls it and tries once more.
 void ReleaseIdlePools();
 
-// Grow-only device buffer.
+// Grow-only device buffer. Owns its pointer: moved, never copied.
 struct DevBuf {
   void* ptr = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), bytes(o.bytes) {
+    o.ptr = nullptr;
+    o.bytes = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      if (ptr) (void)hipFree(ptr);
+      ptr = o.ptr;
+      bytes = o.bytes;
+      o.ptr = nullptr;
+      o.bytes = 0;
+    }
+    return *this;
+  }
   ~DevBuf() {
     if (ptr) (void)hipFree(ptr);
   }
@@ -89,6 +104,9 @@ class BufPool {
 struct PinnedBuf {
   void* ptr = nullptr;
   size_t bytes = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;  // owns its pointer; nothing moves one either
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
   ~PinnedBuf() {
     if (ptr) (void)hipHostFree(ptr);
   }

@@ -30,10 +30,10 @@
 //   ray_mask_count / ray_mask_write  csm_ray_to_pixel_mask, test-visible: the
 //                   same ColumnRun, one thread per ray, cells in the
 //                   reference's order.
-// The column walk (RayWalk, ColumnRun), the growth of the limits and the
-// copy_rect / box kernels are shared with the TSDF inserter:
-// insert2d_common.h.
-//
+// The column walk (RayWalk, ColumnRun), the copy_rect / box kernels and the
+// host steps of growth, create and crop over a grid's list of planes are
+// shared with the TSDF inserter (insert2d_common.h); the steps of an insert
+// call around the kernels with all three inserters (insert_host.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -201,8 +201,6 @@ uint16_t CorrespondenceCostToValue(float cc) {
   const float c = cc > hi ? hi : (cc < lo ? lo : cc);
   return static_cast<uint16_t>(static_cast<int>(std::lround((c - lo) * (32766.f / (hi - lo)))) + 1);
 }
-float Odds(float p) { return p / (1.f - p); }
-float ProbabilityFromOdds(float odds) { return odds / (odds + 1.f); }
 
 // probability_values.cc:89-106.
 void LookupTable(float odds, uint16_t* out) {
@@ -216,30 +214,57 @@ void LookupTable(float odds, uint16_t* out) {
                 kUpdateMarker;
 }
 
-struct ScanPlan {
-  int grid = 0, round = 0;
-  bool grew = false;
-  int off_x = 0, off_y = 0;
-  csm_map_limits before{}, after{};
-  DevBuf cells, marks;  // the grown grid's buffers
-};
+size_t CellBytes(size_t nx, size_t ny) { return nx * ny * sizeof(uint16_t); }
+size_t MarkBytes(size_t nx, size_t ny) {
+  return static_cast<size_t>(MarkWords(static_cast<int>(nx))) * ny * sizeof(uint32_t);
+}
+// The planes of a ProbabilityGrid as growth sees them (insert2d_common.h).
+const Plane2<csm_probability_grid> kPlanes[] = {
+    {&csm_probability_grid::cells, CellBytes, 0, true},
+    {&csm_probability_grid::marks, MarkBytes, 0, false}};
 
-int EnsureTables(csm_context* ctx, const csm_inserter2d_options* o) {
-  if (ctx->ins_tab_key[0] == o->hit_probability && ctx->ins_tab_key[1] == o->miss_probability)
-    return CSM_OK;
-  std::vector<uint16_t> tabs(2 * 32768);
-  LookupTable(Odds(o->hit_probability), tabs.data());
-  LookupTable(Odds(o->miss_probability), tabs.data() + 32768);
-  for (uint16_t& v : tabs) v &= 0x7fff;  // the device keeps no marker
-  int rc;
-  // Earlier inserts on the stream may still read the previous tables.
-  CSM_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = ctx->ins_tabs.Reserve(tabs.size() * sizeof(uint16_t)))) return rc;
-  CSM_HIP(hipMemcpy(ctx->ins_tabs.ptr, tabs.data(), tabs.size() * sizeof(uint16_t),
-                    hipMemcpyHostToDevice));
-  ctx->ins_tab_key[0] = o->hit_probability;
-  ctx->ins_tab_key[1] = o->miss_probability;
-  return CSM_OK;
+// One scan's plan on the host's copy of its grid's limits: its growth
+// (GrowAsNeeded, :35-50: the float bounding box of origin, returns and
+// misses), its round, and the cells it can touch. False past kMaxSide.
+bool PlanScan(int grid, const float* org, const float* returns, int num_returns,
+              const float* misses, int num_misses, std::vector<csm_map_limits>* limits,
+              std::vector<int>* rounds, GrowPlan2* p, ScanDev* out) {
+  float bmin_x = org[0], bmax_x = org[0], bmin_y = org[1], bmax_y = org[1];
+  auto extend = [&](const float* q) {
+    bmin_x = std::min(bmin_x, q[0]);
+    bmax_x = std::max(bmax_x, q[0]);
+    bmin_y = std::min(bmin_y, q[1]);
+    bmax_y = std::max(bmax_y, q[1]);
+  };
+  for (int i = 0; i < num_returns; ++i) extend(returns + 3 * i);
+  for (int i = 0; i < num_misses; ++i) extend(misses + 3 * i);
+  const float box[4] = {bmin_x, bmin_y, bmax_x, bmax_y};
+  if (!PlanGrowth2(grid, box, limits, rounds, p)) return false;
+  const csm_map_limits& l = p->after;
+  // The fine index falls as the coordinate rises, so the box corners bound
+  // every point's cell; one cell of slack, clamped to the grid.
+  ScanDev& d = *out;
+  d.nx = l.num_x_cells;
+  d.ny = l.num_y_cells;
+  d.max_x = l.max_x;
+  d.max_y = l.max_y;
+  d.fine_resolution = l.resolution / kSubpixelScale;
+  d.ox = org[0];
+  d.oy = org[1];
+  d.num_returns = num_returns;
+  d.num_misses = num_misses;
+  long fx0, fy0, fx1, fy1;
+  CellIndex(l, d.fine_resolution, bmax_x, bmax_y, &fx0, &fy0);
+  CellIndex(l, d.fine_resolution, bmin_x, bmin_y, &fx1, &fy1);
+  auto cell = [](long f, int n) {
+    const long c = (f < 0 ? -((-f + kSubpixelScale - 1) / kSubpixelScale) : f / kSubpixelScale);
+    return static_cast<int>(std::min<long>(std::max<long>(c, 0), n - 1));
+  };
+  d.box_x0 = cell(fx0 - kSubpixelScale, d.nx);
+  d.box_y0 = cell(fy0 - kSubpixelScale, d.ny);
+  d.box_x1 = cell(fx1 + kSubpixelScale, d.nx);
+  d.box_y1 = cell(fy1 + kSubpixelScale, d.ny);
+  return true;
 }
 
 int InsertBatch(csm_context* ctx, csm_probability_grid* const* grids, int32_t num_grids,
@@ -248,199 +273,84 @@ int InsertBatch(csm_context* ctx, csm_probability_grid* const* grids, int32_t nu
                 const float* misses, const int64_t* miss_off) {
   if (!ctx || !grids || !o || num_grids < 1 || num_scans < 0) return CSM_EINVAL;
   if (num_scans > 0 && (!grid_of_scan || !origins || !ret_off)) return CSM_EINVAL;
-  if (!miss_off) misses = nullptr;
   if (!(o->hit_probability > 0.f && o->hit_probability < 1.f && o->miss_probability > 0.f &&
         o->miss_probability < 1.f))
     return CSM_EINVAL;
   for (int g = 0; g < num_grids; ++g)
     if (!grids[g]) return CSM_EINVAL;
   if (num_scans == 0) return CSM_OK;
-  const int64_t total_ret = ret_off[num_scans], total_miss = miss_off ? miss_off[num_scans] : 0;
-  if (ret_off[0] != 0 || (miss_off && miss_off[0] != 0)) return CSM_EINVAL;
-  if ((total_ret > 0 && !returns) || (total_miss > 0 && !misses)) return CSM_EINVAL;
-  for (int s = 0; s < num_scans; ++s) {
+  if (!ValidScans(num_scans, origins, ret_off, returns) ||
+      (miss_off && !ValidPoints(num_scans, miss_off, misses)))
+    return CSM_EINVAL;
+  for (int s = 0; s < num_scans; ++s)
     if (grid_of_scan[s] < 0 || grid_of_scan[s] >= num_grids) return CSM_EINVAL;
-    if (ret_off[s + 1] < ret_off[s] || ret_off[s + 1] - ret_off[s] > (1 << 24)) return CSM_EINVAL;
-    if (miss_off && (miss_off[s + 1] < miss_off[s] || miss_off[s + 1] - miss_off[s] > (1 << 24)))
-      return CSM_EINVAL;
-    if (!Finite3(origins + 3 * s)) return CSM_EINVAL;
-  }
-  for (int64_t i = 0; i < total_ret; ++i)
-    if (!Finite3(returns + 3 * i)) return CSM_EINVAL;
-  for (int64_t i = 0; i < total_miss; ++i)
-    if (!Finite3(misses + 3 * i)) return CSM_EINVAL;
-
+  const int64_t total_ret = ret_off[num_scans], total_miss = miss_off ? miss_off[num_scans] : 0;
   // The points are checked before any handle is read.
-  for (int g = 0; g < num_grids; ++g) {
-    if (grids[g]->ctx != ctx) return CSM_EINVAL;
-    for (int h = 0; h < g; ++h)
-      if (grids[h] == grids[g]) return CSM_EINVAL;
-  }
+  if (!ValidHandles(ctx, grids, num_grids)) return CSM_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);
   if (EnsureDevice(ctx)) return CSM_EHIP;
   for (int g = 0; g < num_grids; ++g)
     if (grids[g]->finished) return CSM_EINVAL;
 
-  // Plan, on the host's copy of the limits: each scan's growth (GrowAsNeeded,
-  // :35-50: the float bounding box of origin, returns and misses, padded by
-  // 1e-6f), its round, and the cells it can touch.
-  std::vector<ScanPlan> plan(num_scans);
+  std::vector<GrowPlan2> plan(num_scans);
   std::vector<csm_map_limits> cur(num_grids);
   std::vector<int> rounds(num_grids, 0);
   std::vector<ScanDev> descs(num_scans);
   for (int g = 0; g < num_grids; ++g) cur[g] = grids[g]->limits;
-  int num_rounds = 0;
   for (int s = 0; s < num_scans; ++s) {
-    ScanPlan& p = plan[s];
-    p.grid = grid_of_scan[s];
-    p.round = rounds[p.grid]++;
-    num_rounds = std::max(num_rounds, p.round + 1);
-    const float* org = origins + 3 * s;
-    float bmin_x = org[0], bmax_x = org[0], bmin_y = org[1], bmax_y = org[1];
-    auto extend = [&](const float* q) {
-      bmin_x = std::min(bmin_x, q[0]);
-      bmax_x = std::max(bmax_x, q[0]);
-      bmin_y = std::min(bmin_y, q[1]);
-      bmax_y = std::max(bmax_y, q[1]);
-    };
-    for (int64_t i = ret_off[s]; i < ret_off[s + 1]; ++i) extend(returns + 3 * i);
-    if (miss_off)
-      for (int64_t i = miss_off[s]; i < miss_off[s + 1]; ++i) extend(misses + 3 * i);
-    constexpr float kPadding = 1e-6f;
-    csm_map_limits& l = cur[p.grid];
-    p.before = l;
-    if (!GrowLimits(&l, bmin_x - kPadding, bmin_y - kPadding, &p.off_x, &p.off_y) ||
-        !GrowLimits(&l, bmax_x + kPadding, bmax_y + kPadding, &p.off_x, &p.off_y))
-      return CSM_ERANGE;
-    p.after = l;
-    p.grew = l.num_x_cells != p.before.num_x_cells;
-    // The fine index falls as the coordinate rises, so the box corners bound
-    // every point's cell; one cell of slack, clamped to the grid.
     ScanDev& d = descs[s];
-    d.nx = l.num_x_cells;
-    d.ny = l.num_y_cells;
-    d.max_x = l.max_x;
-    d.max_y = l.max_y;
-    d.fine_resolution = l.resolution / kSubpixelScale;
-    d.ox = org[0];
-    d.oy = org[1];
-    d.num_returns = static_cast<int>(ret_off[s + 1] - ret_off[s]);
-    d.num_misses = miss_off ? static_cast<int>(miss_off[s + 1] - miss_off[s]) : 0;
     d.ret_begin = ret_off[s];
     d.miss_begin = miss_off ? miss_off[s] : 0;
-    long fx0, fy0, fx1, fy1;
-    CellIndex(l, d.fine_resolution, bmax_x, bmax_y, &fx0, &fy0);
-    CellIndex(l, d.fine_resolution, bmin_x, bmin_y, &fx1, &fy1);
-    auto cell = [](long f, int n) {
-      const long c = (f < 0 ? -((-f + kSubpixelScale - 1) / kSubpixelScale) : f / kSubpixelScale);
-      return static_cast<int>(std::min<long>(std::max<long>(c, 0), n - 1));
-    };
-    d.box_x0 = cell(fx0 - kSubpixelScale, d.nx);
-    d.box_y0 = cell(fy0 - kSubpixelScale, d.ny);
-    d.box_x1 = cell(fx1 + kSubpixelScale, d.nx);
-    d.box_y1 = cell(fy1 + kSubpixelScale, d.ny);
+    if (!PlanScan(grid_of_scan[s], origins + 3 * s, returns + 3 * d.ret_begin,
+                  static_cast<int>(ret_off[s + 1] - ret_off[s]), misses + 3 * d.miss_begin,
+                  miss_off ? static_cast<int>(miss_off[s + 1] - miss_off[s]) : 0, &cur, &rounds,
+                  &plan[s], &d))
+      return CSM_ERANGE;
   }
-
-  // Allocate every grown grid before anything is enqueued: a failure leaves
-  // the grids as they were.
-  int rc = EnsureTables(ctx, o);
-  auto give_back = [&] {
-    for (ScanPlan& p : plan) {
-      if (p.cells.ptr) ctx->pool.Give(&p.cells);
-      if (p.marks.ptr) ctx->pool.Give(&p.marks);
-    }
-  };
-  for (int s = 0; s < num_scans && rc == CSM_OK; ++s) {
-    ScanPlan& p = plan[s];
-    if (!p.grew) continue;
-    const size_t nx = p.after.num_x_cells, ny = p.after.num_y_cells;
-    if ((rc = ctx->pool.Take(nx * ny * sizeof(uint16_t), &p.cells)) == CSM_OK)
-      rc = ctx->pool.Take(static_cast<size_t>(MarkWords(nx)) * ny * sizeof(uint32_t), &p.marks);
-  }
-  // Scans in round order (stable), descriptors with the buffers each scan
-  // will see, then one upload: descriptors, returns, misses.
+  // Scans in round order (stable).
   std::vector<int> order(num_scans);
   for (int s = 0; s < num_scans; ++s) order[s] = s;
   std::stable_sort(order.begin(), order.end(),
                    [&](int a, int b) { return plan[a].round < plan[b].round; });
-  const size_t desc_bytes = (sizeof(ScanDev) * num_scans + 255) & ~size_t(255);
-  const size_t ret_bytes = (sizeof(float) * 3 * total_ret + 255) & ~size_t(255);
+
+  // Everything that can fail cleanly, before anything is enqueued: a failure
+  // leaves the grids as they were. One upload: descriptors, returns, misses.
+  const size_t desc_bytes = Align(sizeof(ScanDev) * num_scans);
+  const size_t ret_bytes = Align(sizeof(float) * 3 * total_ret);
   const size_t miss_bytes = sizeof(float) * 3 * total_miss;
   const size_t bytes = desc_bytes + ret_bytes + miss_bytes;
   StageRing::Slot* slot = nullptr;
-  if (rc == CSM_OK) rc = ctx->ins_stage.Take(bytes, &slot);
-  if (rc == CSM_OK && ctx->ins_dev.bytes < bytes) {
-    // The buffer is replaced: earlier inserts on the stream may still read it.
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CSM_EHIP;
-    else rc = ctx->ins_dev.Reserve(bytes + bytes / 2);
-  }
+  int rc = EnsureOddsTables(ctx, o->hit_probability, o->miss_probability, LookupTable,
+                            &ctx->ins_tabs, ctx->ins_tab_key);
+  if (rc == CSM_OK) rc = TakeGrown2(ctx, grids, num_grids, kPlanes, &plan);
+  if (rc == CSM_OK) rc = ReserveUpload(ctx, &ctx->ins_stage, &ctx->ins_dev, bytes, &slot);
   if (rc != CSM_OK) {
-    give_back();
+    GiveBackGrown2(ctx, &plan);
     return rc;
   }
-  {
-    std::vector<uint16_t*> cells(num_grids);
-    std::vector<uint32_t*> marks(num_grids);
-    for (int g = 0; g < num_grids; ++g) {
-      cells[g] = grids[g]->cells.as<uint16_t>();
-      marks[g] = grids[g]->marks.as<uint32_t>();
-    }
-    ScanDev* hd = slot->buf.as<ScanDev>();
-    for (int i = 0; i < num_scans; ++i) {
-      const int s = order[i];
-      ScanPlan& p = plan[s];
-      if (p.grew) {
-        cells[p.grid] = p.cells.as<uint16_t>();
-        marks[p.grid] = p.marks.as<uint32_t>();
-      }
-      descs[s].cells = cells[p.grid];
-      descs[s].marks = marks[p.grid];
-      hd[i] = descs[s];
-    }
-    char* h = slot->buf.as<char>();
-    if (total_ret) std::memcpy(h + desc_bytes, returns, sizeof(float) * 3 * total_ret);
-    if (total_miss) std::memcpy(h + desc_bytes + ret_bytes, misses, miss_bytes);
+  char* h = slot->buf.as<char>();
+  ScanDev* hd = slot->buf.as<ScanDev>();
+  for (int i = 0; i < num_scans; ++i) {
+    hd[i] = descs[order[i]];
+    hd[i].cells = static_cast<uint16_t*>(plan[order[i]].seen[0]);
+    hd[i].marks = static_cast<uint32_t*>(plan[order[i]].seen[1]);
   }
+  if (total_ret) std::memcpy(h + desc_bytes, returns, sizeof(float) * 3 * total_ret);
+  if (total_miss) std::memcpy(h + desc_bytes + ret_bytes, misses, miss_bytes);
+  // From here on a failure is a HIP error (insert_host.h): the grids keep what
+  // they had when it struck.
+  if ((rc = Upload(ctx, slot, &ctx->ins_dev, bytes))) return rc;
   hipStream_t st = ctx->stream;
-  // From here on a failure is a HIP error: the stream's state is unknown and
-  // the grids keep their old buffers and limits.
-  if (hipMemcpyAsync(ctx->ins_dev.ptr, slot->buf.ptr, bytes, hipMemcpyHostToDevice, st) !=
-          hipSuccess ||
-      hipEventRecord(slot->copied, st) != hipSuccess) {
-    give_back();
-    return CSM_EHIP;
-  }
   const ScanDev* dd = ctx->ins_dev.as<ScanDev>();
   const float* dret = reinterpret_cast<const float*>(ctx->ins_dev.as<char>() + desc_bytes);
   const float* dmiss =
       reinterpret_cast<const float*>(ctx->ins_dev.as<char>() + desc_bytes + ret_bytes);
   std::deque<DevBuf> retired;
-  int i0 = 0;
-  for (int r = 0; r < num_rounds; ++r) {
-    int i1 = i0;
+  for (int i0 = 0, i1 = 0; i0 < num_scans; i0 = i1) {  // a round: [i0, i1)
     int64_t max_rays = 1, max_words = 1;
-    for (; i1 < num_scans && plan[order[i1]].round == r; ++i1) {
+    for (; i1 < num_scans && plan[order[i1]].round == plan[order[i0]].round; ++i1) {
       const int s = order[i1];
-      ScanPlan& p = plan[s];
-      csm_probability_grid* g = grids[p.grid];
-      if (p.grew) {
-        const size_t nx = p.after.num_x_cells, ny = p.after.num_y_cells;
-        CSM_HIP(hipMemsetAsync(p.cells.ptr, 0, nx * ny * sizeof(uint16_t), st));
-        CSM_HIP(hipMemsetAsync(p.marks.ptr, 0, MarkWords(nx) * ny * sizeof(uint32_t), st));
-        const int ow = p.before.num_x_cells, oh = p.before.num_y_cells;
-        hipLaunchKernelGGL(insert2d_copy_rect, dim3(Blocks(int64_t{ow} * oh, 256, 4096)),
-                           dim3(256), 0, st, g->cells.as<uint16_t>(), ow, 0, 0,
-                           p.cells.as<uint16_t>(), static_cast<int>(nx), p.off_x, p.off_y, ow, oh);
-        CSM_HIP(hipGetLastError());
-        retired.emplace_back();
-        MoveBuf(&g->cells, &retired.back());
-        retired.emplace_back();
-        MoveBuf(&g->marks, &retired.back());
-        MoveBuf(&p.cells, &g->cells);
-        MoveBuf(&p.marks, &g->marks);
-      }
-      g->limits = p.after;
-      ++g->generation;
+      if ((rc = CommitScan2(ctx, grids[plan[s].grid], kPlanes, &plan[s], &retired))) return rc;
       const ScanDev& d = descs[s];
       max_rays = std::max<int64_t>(max_rays, o->insert_free_space
                                                  ? int64_t{d.num_returns} + d.num_misses
@@ -448,22 +358,18 @@ int InsertBatch(csm_context* ctx, csm_probability_grid* const* grids, int32_t nu
       max_words = std::max<int64_t>(
           max_words, int64_t{(d.box_x1 >> 4) - (d.box_x0 >> 4) + 1} * (d.box_y1 - d.box_y0 + 1));
     }
-    const unsigned ny = static_cast<unsigned>(i1 - i0);
-    // 65535 scans per launch (gridDim.y).
-    for (unsigned y0 = 0; y0 < ny; y0 += 65535) {
-      const unsigned nyy = std::min(65535u, ny - y0);
+    for (int y0 = i0; y0 < i1; y0 += kMaxGridY) {
+      const unsigned nyy = ChunkOf(y0, i1);
       hipLaunchKernelGGL(insert2d_mark, dim3(Blocks(max_rays, 4, 1024), nyy), dim3(256), 0, st,
-                         dd + i0 + y0, dret, dmiss, o->insert_free_space ? 1 : 0);
+                         dd + y0, dret, dmiss, o->insert_free_space ? 1 : 0);
       CSM_HIP(hipGetLastError());
       hipLaunchKernelGGL(insert2d_apply, dim3(Blocks(max_words, 256, 1024), nyy), dim3(256), 0,
-                         st, dd + i0 + y0, ctx->ins_tabs.as<uint16_t>());
+                         st, dd + y0, ctx->ins_tabs.as<uint16_t>());
       CSM_HIP(hipGetLastError());
     }
-    i0 = i1;
   }
   // The old buffers of grown grids: reused by later takes on this stream.
-  for (DevBuf& b : retired)
-    if (b.ptr) ctx->pool.Give(&b);
+  for (DevBuf& b : retired) ctx->pool.Give(&b);
   return CSM_OK;
 }
 
@@ -483,40 +389,15 @@ int csm_inserter2d_lookup_table(float probability, uint16_t* out) {
 int csm_probability_grid_create(csm_context* ctx, const csm_map_limits* limits,
                                 const uint16_t* cells, csm_probability_grid** out) {
   if (!ctx || !limits || !out) return CSM_EINVAL;
-  if (limits->num_x_cells < 1 || limits->num_y_cells < 1 || !(limits->resolution > 0.) ||
-      !std::isfinite(limits->resolution) || !std::isfinite(limits->max_x) ||
-      !std::isfinite(limits->max_y))
-    return CSM_EINVAL;
-  if (limits->num_x_cells > kMaxSide || limits->num_y_cells > kMaxSide) return CSM_ERANGE;
+  if (int rc = CheckLimits2(limits)) return rc;
   std::lock_guard<std::mutex> lock(ctx->mu);
   if (EnsureDevice(ctx)) return CSM_EHIP;
   auto g = std::make_unique<csm_probability_grid>();
   g->ctx = ctx;
   g->limits = *limits;
   g->id = g_next_grid_id.fetch_add(1);
-  const size_t nx = limits->num_x_cells, ny = limits->num_y_cells;
-  const size_t mark_bytes = static_cast<size_t>(MarkWords(nx)) * ny * sizeof(uint32_t);
-  int rc;
-  if ((rc = ctx->pool.Take(nx * ny * sizeof(uint16_t), &g->cells)) ||
-      (rc = ctx->pool.Take(mark_bytes, &g->marks))) {
-    if (g->cells.ptr) ctx->pool.Give(&g->cells);
-    return rc;
-  }
-  hipStream_t st = ctx->stream;
-  bool ok = hipMemsetAsync(g->marks.ptr, 0, mark_bytes, st) == hipSuccess;
-  if (cells) {
-    // The caller's memory is read: finish before returning.
-    ok = ok && hipMemcpyAsync(g->cells.ptr, cells, nx * ny * sizeof(uint16_t),
-                              hipMemcpyHostToDevice, st) == hipSuccess &&
-         hipStreamSynchronize(st) == hipSuccess;
-  } else {
-    ok = ok && hipMemsetAsync(g->cells.ptr, 0, nx * ny * sizeof(uint16_t), st) == hipSuccess;
-  }
-  if (!ok) {
-    ctx->pool.Give(&g->cells);
-    ctx->pool.Give(&g->marks);
-    return CSM_EHIP;
-  }
+  const uint16_t* const host[] = {cells, nullptr};
+  if (int rc = NewPlanes2(g.get(), kPlanes, host)) return rc;
   *out = g.release();
   return CSM_OK;
 }
@@ -524,8 +405,7 @@ int csm_probability_grid_create(csm_context* ctx, const csm_map_limits* limits,
 void csm_probability_grid_destroy(csm_probability_grid* g) {
   if (!g) return;
   (void)hipSetDevice(g->ctx->device);
-  if (g->cells.ptr) g->ctx->pool.Give(&g->cells);
-  if (g->marks.ptr) g->ctx->pool.Give(&g->marks);
+  GivePlanes2(g, kPlanes);
   delete g;
 }
 
@@ -553,14 +433,10 @@ int csm_probability_grid_insert(csm_probability_grid* g, const csm_inserter2d_op
                                 const float* misses, int32_t num_misses) {
   if (!g || !o || !origin || num_returns < 0 || num_misses < 0) return CSM_EINVAL;
   if ((num_returns > 0 && !returns) || (num_misses > 0 && !misses)) return CSM_EINVAL;
-  // The points are checked before the handle is read.
-  if (!Finite3(origin)) return CSM_EINVAL;
-  for (int32_t i = 0; i < num_returns; ++i)
-    if (!Finite3(returns + 3 * i)) return CSM_EINVAL;
-  for (int32_t i = 0; i < num_misses; ++i)
-    if (!Finite3(misses + 3 * i)) return CSM_EINVAL;
   const int32_t zero = 0;
   const int64_t ro[2] = {0, num_returns}, mo[2] = {0, num_misses};
+  // The points are checked before the handle is read.
+  if (!ValidScans(1, origin, ro, returns) || !ValidPoints(1, mo, misses)) return CSM_EINVAL;
   csm_probability_grid* const grids[1] = {g};
   return InsertBatch(g->ctx, grids, 1, o, 1, &zero, origin, returns, ro,
                      num_misses > 0 ? misses : nullptr, num_misses > 0 ? mo : nullptr);
@@ -583,44 +459,23 @@ int csm_probability_grid_finish(csm_probability_grid* g) {
   if (g->finished) return CSM_OK;  // Submap2D::Finish runs once; a second call changes nothing
   if (EnsureDevice(ctx)) return CSM_EHIP;
   hipStream_t st = ctx->stream;
-  int rc;
-  if ((rc = ctx->ins_box.Reserve(4 * sizeof(int))) ||
-      (rc = ctx->ins_box_host.Reserve(4 * sizeof(int))))
-    return rc;
-  int* hb = ctx->ins_box_host.as<int>();
-  hb[0] = hb[1] = INT_MAX;
-  hb[2] = hb[3] = -1;
   const int nx = g->limits.num_x_cells, ny = g->limits.num_y_cells;
-  CSM_HIP(hipMemcpyAsync(ctx->ins_box.ptr, hb, 4 * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(insert2d_box, dim3(Blocks(int64_t{nx} * ny, 1024, 1024)), dim3(256), 0, st,
-                     g->cells.as<uint16_t>(), nx, ny, ctx->ins_box.as<int>());
-  CSM_HIP(hipGetLastError());
-  CSM_HIP(hipMemcpyAsync(hb, ctx->ins_box.ptr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  CSM_HIP(hipStreamSynchronize(st));
-  // Grid2D::ComputeCroppedLimits (grid_2d.cc:121-132) and the new max
-  // (probability_grid.cc:95-99).
-  const bool empty = hb[2] < 0;
-  const int ox = empty ? 0 : hb[0], oy = empty ? 0 : hb[1];
-  const int cnx = empty ? 1 : hb[2] - hb[0] + 1, cny = empty ? 1 : hb[3] - hb[1] + 1;
+  int rc;
+  Crop2 c;
+  if ((rc = CropBox2(ctx, g->cells.as<uint16_t>(), nx, ny, &c))) return rc;
   DevBuf cropped;
-  if ((rc = ctx->pool.Take(static_cast<size_t>(cnx) * cny * sizeof(uint16_t), &cropped))) return rc;
-  if (empty) {
+  if ((rc = ctx->pool.Take(CellBytes(c.nx, c.ny), &cropped))) return rc;
+  if (c.empty) {
     CSM_HIP(hipMemsetAsync(cropped.ptr, 0, sizeof(uint16_t), st));
   } else {
-    hipLaunchKernelGGL(insert2d_copy_rect, dim3(Blocks(int64_t{cnx} * cny, 256, 4096)), dim3(256),
-                       0, st, g->cells.as<uint16_t>(), nx, ox, oy, cropped.as<uint16_t>(), cnx, 0,
-                       0, cnx, cny);
+    hipLaunchKernelGGL(insert2d_copy_rect, dim3(Blocks(int64_t{c.nx} * c.ny, 256, 4096)),
+                       dim3(256), 0, st, g->cells.as<uint16_t>(), nx, c.ox, c.oy,
+                       cropped.as<uint16_t>(), c.nx, 0, 0, c.nx, c.ny);
     CSM_HIP(hipGetLastError());
   }
-  ctx->pool.Give(&g->cells);  // reused by later takes on this stream
-  ctx->pool.Give(&g->marks);
-  MoveBuf(&cropped, &g->cells);
-  g->limits.max_x = g->limits.max_x - g->limits.resolution * static_cast<double>(oy);
-  g->limits.max_y = g->limits.max_y - g->limits.resolution * static_cast<double>(ox);
-  g->limits.num_x_cells = cnx;
-  g->limits.num_y_cells = cny;
-  g->finished = true;
-  ++g->generation;
+  GivePlanes2(g, kPlanes);  // reused by later takes on this stream
+  g->cells = std::move(cropped);
+  FinishCrop2(g, c);
   return CSM_OK;
 }
 

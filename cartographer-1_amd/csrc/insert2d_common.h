@@ -1,9 +1,11 @@
 // Shared by the two 2D range-data inserters (insert2d.hip: ProbabilityGrid,
 // insert_tsdf2d.hip: TSDF2D): the closed-form column walk of RayToPixelMask
 // (ray_to_pixel_mask.cc:29-159), Grid2D::GrowLimits on the limits alone
-// (grid_2d.cc:142-175), and the rect-copy and bounding-box kernels of growth
-// and Finish. Everything here has internal linkage: each translation unit
-// that includes this header compiles its own copy of the kernels.
+// (grid_2d.cc:142-175), the rect-copy and bounding-box kernels of growth and
+// Finish, and the host steps of growth, create and crop written once over a
+// grid's list of planes (Plane2). Everything here has internal linkage: each
+// translation unit that includes this header compiles its own copy of the
+// kernels.
 //
 // ColumnRun. The reference walks a ray one pixel column at a time carrying
 // sub_y, the height at the column's right border in units of 1 / denominator
@@ -29,6 +31,7 @@
 #include <cstdint>
 
 #include "csm_internal.h"
+#include "insert_host.h"
 
 namespace csm {
 
@@ -144,18 +147,6 @@ insert2d_box(const uint16_t* __restrict__ cells, int nx, int ny, int* __restrict
 
 // ---------------------------------------------------------------- host -----
 
-inline int EnsureDevice(csm_context* ctx) {
-  return hipSetDevice(ctx->device) == hipSuccess ? CSM_OK : CSM_EHIP;
-}
-
-// DevBuf owns its pointer and has no move: hand it over by hand (`to` empty).
-inline void MoveBuf(DevBuf* from, DevBuf* to) {
-  to->ptr = from->ptr;
-  to->bytes = from->bytes;
-  from->ptr = nullptr;
-  from->bytes = 0;
-}
-
 // MapLimits::GetCellIndex / Contains (map_limits.h:69-89).
 inline void CellIndex(const csm_map_limits& l, double resolution, float px, float py, long* x,
                       long* y) {
@@ -185,13 +176,177 @@ inline bool GrowLimits(csm_map_limits* l, float px, float py, int* off_x, int* o
   return true;
 }
 
-inline bool Finite3(const float* p) {
-  return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+// ---- growth and crop, the same steps for both inserters -------------------
+
+// One plane of a 2D grid as growth sees it.
+template <typename Grid>
+struct Plane2 {
+  DevBuf Grid::*buf;
+  size_t (*bytes)(size_t nx, size_t ny);
+  int fill;    // memset byte of a new plane
+  bool cells;  // uint16 cells, x fastest: the old ones are copied in at their offset
+};
+
+constexpr int kMaxPlanes = 3;
+
+// One scan's growth of its grid, planned on the host's copy of the limits.
+struct GrowPlan2 {
+  int grid = 0, round = 0;
+  bool grew = false;
+  int off_x = 0, off_y = 0;
+  csm_map_limits before{}, after{};
+  DevBuf grown[kMaxPlanes];  // the grown grid's planes
+  void* seen[kMaxPlanes] = {};  // the planes the scan's kernels run on (TakeGrown2)
+};
+
+// GrowAsNeeded for the float box (min x, min y, max x, max y) of what the
+// scan touches, padded by 1e-6f, and the scan's round within its grid. False
+// past kMaxSide.
+inline bool PlanGrowth2(int grid, const float* box, std::vector<csm_map_limits>* limits,
+                        std::vector<int>* rounds, GrowPlan2* p) {
+  constexpr float kPadding = 1e-6f;
+  p->grid = grid;
+  p->round = (*rounds)[grid]++;
+  csm_map_limits& l = (*limits)[grid];
+  p->before = l;
+  if (!GrowLimits(&l, box[0] - kPadding, box[1] - kPadding, &p->off_x, &p->off_y) ||
+      !GrowLimits(&l, box[2] + kPadding, box[3] + kPadding, &p->off_x, &p->off_y))
+    return false;
+  p->after = l;
+  p->grew = l.num_x_cells != p->before.num_x_cells;
+  return true;
 }
 
-inline unsigned Blocks(int64_t items, int per_block, int cap) {
-  const int64_t b = (items + per_block - 1) / per_block;
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(b, cap)));
+inline void GiveBackGrown2(csm_context* ctx, std::vector<GrowPlan2>* plan) {
+  for (GrowPlan2& p : *plan)
+    for (DevBuf& b : p.grown) ctx->pool.Give(&b);
+}
+
+// Every grown grid's planes, before anything is enqueued, and the planes each
+// scan will see: its own grown ones, else those the latest earlier scan of its
+// grid grew, else the grid's.
+template <typename Grid, size_t N>
+int TakeGrown2(csm_context* ctx, Grid* const* grids, int32_t num_grids,
+               const Plane2<Grid> (&planes)[N], std::vector<GrowPlan2>* plan) {
+  std::vector<void*> cur(static_cast<size_t>(num_grids) * N);
+  for (int g = 0; g < num_grids; ++g)
+    for (size_t k = 0; k < N; ++k) cur[g * N + k] = (grids[g]->*planes[k].buf).ptr;
+  for (GrowPlan2& p : *plan)
+    for (size_t k = 0; k < N; ++k) {
+      const size_t bytes = planes[k].bytes(p.after.num_x_cells, p.after.num_y_cells);
+      if (int rc = p.grew ? ctx->pool.Take(bytes, &p.grown[k]) : CSM_OK) return rc;
+      if (p.grew) cur[p.grid * N + k] = p.grown[k].ptr;
+      p.seen[k] = cur[p.grid * N + k];
+    }
+  return CSM_OK;
+}
+
+// Enqueues a scan's growth (new planes filled, old cells copied to their
+// offset), swaps the grown planes in and moves the grid's host state on.
+template <typename Grid, size_t N>
+int CommitScan2(csm_context* ctx, Grid* g, const Plane2<Grid> (&planes)[N], GrowPlan2* p,
+                std::deque<DevBuf>* retired) {
+  hipStream_t st = ctx->stream;
+  const size_t nx = p->after.num_x_cells, ny = p->after.num_y_cells;
+  const int ow = p->before.num_x_cells, oh = p->before.num_y_cells;
+  for (size_t k = 0; p->grew && k < N; ++k)
+    CSM_HIP(hipMemsetAsync(p->grown[k].ptr, planes[k].fill, planes[k].bytes(nx, ny), st));
+  for (size_t k = 0; p->grew && k < N; ++k) {
+    if (!planes[k].cells) continue;
+    hipLaunchKernelGGL(insert2d_copy_rect, dim3(Blocks(int64_t{ow} * oh, 256, 4096)), dim3(256), 0,
+                       st, (g->*planes[k].buf).template as<uint16_t>(), ow, 0, 0,
+                       p->grown[k].as<uint16_t>(), static_cast<int>(nx), p->off_x, p->off_y, ow,
+                       oh);
+    CSM_HIP(hipGetLastError());
+  }
+  for (size_t k = 0; p->grew && k < N; ++k) {
+    retired->push_back(std::move(g->*planes[k].buf));
+    g->*planes[k].buf = std::move(p->grown[k]);
+  }
+  g->limits = p->after;
+  ++g->generation;
+  return CSM_OK;
+}
+
+template <typename Grid, size_t N>
+void GivePlanes2(Grid* g, const Plane2<Grid> (&planes)[N]) {
+  for (size_t k = 0; k < N; ++k) g->ctx->pool.Give(&(g->*planes[k].buf));
+}
+
+// A new grid's planes, taken from the pool: plane k copied from host[k] (the
+// caller's memory is read, so the copy is waited for), else filled.
+template <typename Grid, size_t N>
+int NewPlanes2(Grid* g, const Plane2<Grid> (&planes)[N], const uint16_t* const (&host)[N]) {
+  const size_t nx = g->limits.num_x_cells, ny = g->limits.num_y_cells;
+  hipStream_t st = g->ctx->stream;
+  for (size_t k = 0; k < N; ++k)
+    if (int rc = g->ctx->pool.Take(planes[k].bytes(nx, ny), &(g->*planes[k].buf))) {
+      GivePlanes2(g, planes);
+      return rc;
+    }
+  bool wait = false;
+  for (size_t k = 0; k < N; ++k) {
+    void* p = (g->*planes[k].buf).ptr;
+    if (host[k]) {
+      CSM_HIP(hipMemcpyAsync(p, host[k], planes[k].bytes(nx, ny), hipMemcpyHostToDevice, st));
+      wait = true;
+    } else {
+      CSM_HIP(hipMemsetAsync(p, planes[k].fill, planes[k].bytes(nx, ny), st));
+    }
+  }
+  if (wait) CSM_HIP(hipStreamSynchronize(st));
+  return CSM_OK;
+}
+
+// Grid2D::ComputeCroppedLimits (grid_2d.cc:121-132) for Finish: the box of the
+// nonzero cells of `cells`, 1 x 1 at the origin when there is none. Waits for
+// the device.
+struct Crop2 {
+  bool empty;
+  int ox, oy, nx, ny;
+};
+inline int CropBox2(csm_context* ctx, const uint16_t* cells, int nx, int ny, Crop2* c) {
+  hipStream_t st = ctx->stream;
+  int rc;
+  if ((rc = ctx->ins_box.Reserve(4 * sizeof(int))) ||
+      (rc = ctx->ins_box_host.Reserve(4 * sizeof(int))))
+    return rc;
+  int* hb = ctx->ins_box_host.as<int>();
+  hb[0] = hb[1] = INT_MAX;
+  hb[2] = hb[3] = -1;
+  CSM_HIP(hipMemcpyAsync(ctx->ins_box.ptr, hb, 4 * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(insert2d_box, dim3(Blocks(int64_t{nx} * ny, 1024, 1024)), dim3(256), 0, st,
+                     cells, nx, ny, ctx->ins_box.as<int>());
+  CSM_HIP(hipGetLastError());
+  CSM_HIP(hipMemcpyAsync(hb, ctx->ins_box.ptr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  c->empty = hb[2] < 0;
+  c->ox = c->empty ? 0 : hb[0];
+  c->oy = c->empty ? 0 : hb[1];
+  c->nx = c->empty ? 1 : hb[2] - hb[0] + 1;
+  c->ny = c->empty ? 1 : hb[3] - hb[1] + 1;
+  return CSM_OK;
+}
+
+// The cropped grid's limits and the handle's host state after Finish
+// (probability_grid.cc:95-99, tsdf_2d.cc:122-124).
+template <typename Grid>
+void FinishCrop2(Grid* g, const Crop2& c) {
+  g->limits.max_x = g->limits.max_x - g->limits.resolution * static_cast<double>(c.oy);
+  g->limits.max_y = g->limits.max_y - g->limits.resolution * static_cast<double>(c.ox);
+  g->limits.num_x_cells = c.nx;
+  g->limits.num_y_cells = c.ny;
+  g->finished = true;
+  ++g->generation;
+}
+
+// What csm_*_grid_create asks of the limits.
+inline int CheckLimits2(const csm_map_limits* limits) {
+  if (limits->num_x_cells < 1 || limits->num_y_cells < 1 || !(limits->resolution > 0.) ||
+      !std::isfinite(limits->resolution) || !std::isfinite(limits->max_x) ||
+      !std::isfinite(limits->max_y))
+    return CSM_EINVAL;
+  return limits->num_x_cells > kMaxSide || limits->num_y_cells > kMaxSide ? CSM_ERANGE : CSM_OK;
 }
 
 }  // namespace

@@ -46,21 +46,22 @@
 //                  the sum once and adds the run's length to the count.
 // Work is proportional to the returns; the bricks are touched only at the
 // cells that change.
+//
+// The host steps of an insert call around the kernels are insert_host.h's.
 #include <hip/hip_runtime.h>
 // The radix sort alone: rocprim.hpp also pulls in texture iterators.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include <deque>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "csm_internal.h"
+#include "insert_host.h"
 
 namespace csm {
 namespace {
@@ -377,13 +378,6 @@ __global__ void intensity_grid_lookup(const float* __restrict__ sum,
 
 // ---------------------------------------------------------------- host -----
 
-void MoveBuf(DevBuf* from, DevBuf* to) {
-  to->ptr = from->ptr;
-  to->bytes = from->bytes;
-  from->ptr = nullptr;
-  from->bytes = 0;
-}
-
 // probability_values.h:32-45, :37-43 and common/math.h Clamp, in float.
 constexpr float kMinP = 0.1f, kMaxP = 1.f - kMinP;
 uint16_t ProbabilityToValue(float p) {
@@ -391,20 +385,11 @@ uint16_t ProbabilityToValue(float p) {
   return static_cast<uint16_t>(
       static_cast<int>(std::lround((c - kMinP) * (32766.f / (kMaxP - kMinP)))) + 1);
 }
-float Odds(float p) { return p / (1.f - p); }
-float ProbabilityFromOdds(float odds) { return odds / (odds + 1.f); }
-
-// kValueToProbability (probability_values.cc:26-66), the table
-// csm_hybrid_grid_create fills the probability brick from.
-void ProbabilityTable(float* out) {
-  const float scale = (kMaxP - kMinP) / (32768 - 2.f);
-  for (int v = 0; v < 32768; ++v) out[v] = v == 0 ? kMinP : v * scale + (kMinP - scale);
-}
 
 // ComputeLookupTableToApplyOdds (probability_values.cc:76-87).
 void LookupTable3(float odds, uint16_t* out) {
   std::vector<float> ptab(32768);
-  ProbabilityTable(ptab.data());
+  ConversionTable(kMinP, kMinP, kMaxP, ptab.data());  // kValueToProbability (:26-66)
   constexpr uint16_t kUpdateMarker = 1u << 15;
   out[0] = ProbabilityToValue(ProbabilityFromOdds(odds)) + kUpdateMarker;
   for (int cell = 1; cell < 32768; ++cell)
@@ -414,35 +399,16 @@ void LookupTable3(float odds, uint16_t* out) {
 int EnsureTables3(csm_context* ctx, const csm_inserter3d_options* o) {
   int rc;
   if (!ctx->ins3_ptab.ptr) {
+    // kValueToProbability, the table csm_hybrid_grid_create fills the
+    // probability brick from.
     std::vector<float> ptab(32768);
-    ProbabilityTable(ptab.data());
+    ConversionTable(kMinP, kMinP, kMaxP, ptab.data());
     if ((rc = ctx->ins3_ptab.Reserve(sizeof(float) * 32768))) return rc;
     CSM_HIP(hipMemcpy(ctx->ins3_ptab.ptr, ptab.data(), sizeof(float) * 32768,
                       hipMemcpyHostToDevice));
   }
-  if (ctx->ins3_tab_key[0] == o->hit_probability && ctx->ins3_tab_key[1] == o->miss_probability)
-    return CSM_OK;
-  std::vector<uint16_t> tabs(2 * 32768);
-  LookupTable3(Odds(o->hit_probability), tabs.data());
-  LookupTable3(Odds(o->miss_probability), tabs.data() + 32768);
-  for (uint16_t& v : tabs) v &= 0x7fff;  // the kernels keep the marker themselves
-  // Earlier inserts on the stream may still read the previous tables.
-  CSM_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = ctx->ins3_tabs.Reserve(tabs.size() * sizeof(uint16_t)))) return rc;
-  CSM_HIP(hipMemcpy(ctx->ins3_tabs.ptr, tabs.data(), tabs.size() * sizeof(uint16_t),
-                    hipMemcpyHostToDevice));
-  ctx->ins3_tab_key[0] = o->hit_probability;
-  ctx->ins3_tab_key[1] = o->miss_probability;
-  return CSM_OK;
-}
-
-unsigned Blocks(int64_t items, int per_block, int cap) {
-  const int64_t b = (items + per_block - 1) / per_block;
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(b, cap)));
-}
-
-bool Finite3(const float* p) {
-  return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+  return EnsureOddsTables(ctx, o->hit_probability, o->miss_probability, LookupTable3,
+                          &ctx->ins3_tabs, ctx->ins3_tab_key);
 }
 
 // Bytes of a value brick of n cells: the kernels address it in 32-bit words.
@@ -459,6 +425,11 @@ struct Box3 {
       lo[a] = std::min(lo[a], c[a]);
       hi[a] = std::max(hi[a], c[a]);
     }
+  }
+  void Add(const Box3& o) {
+    if (o.empty()) return;
+    Add(o.lo[0], o.lo[1], o.lo[2]);
+    Add(o.hi[0], o.hi[1], o.hi[2]);
   }
 };
 
@@ -478,8 +449,6 @@ bool HostCell(float v, float resolution, int* out) {
 
 // A chunk of one job's returns for the planning pass.
 constexpr int kPlanChunk = 8192;
-constexpr int64_t kPlanThreaded = 32768;  // returns per call from which threads pay off
-constexpr size_t kPlanThreads = 8;
 struct PlanTask {
   int job, i0, i1;
   Box3 box;
@@ -553,15 +522,6 @@ int GrownBrick(const Brick3& b, const Box3& box, Brick3* after, int* grid_size) 
   return n > (int64_t{1} << 31) ? CSM_ERANGE : CSM_OK;
 }
 
-struct IntensPlan3 {
-  Box3 box;
-  Brick3 after{};
-  int grid_size = 0;
-  int paired = -1;  // the HybridGrid its jobs insert into
-  bool touched = false, grew = false;
-  DevBuf sum, count;
-};
-
 // The intensity jobs of one keys / sort / sums launch set.
 struct IntensSet3 {
   int round, first, num;
@@ -570,14 +530,65 @@ struct IntensSet3 {
   int end_bit = 0;  // of the key: 32 bits of cell, then the job and `none`
 };
 
-struct GridPlan3 {
-  Box3 box;          // the cells this call touches
-  Brick3 after{};    // the brick once the call is done
+// What a call does to one grid of either kind: a csm_hybrid_grid (a: values,
+// b: prob) or a csm_intensity_grid (a: sum, b: count).
+struct BrickPlan3 {
+  Box3 box;        // the cells this call touches
+  Brick3 after{};  // the brick once the call is done
   int grid_size = 0;
   bool touched = false, grew = false;
-  DevBuf values, prob, stats;  // a grown grid's new bricks; the first insert's counters
-  int rounds = 0;
+  DevBuf a, b;  // a grown grid's new bricks
+  int64_t cells() const { return static_cast<int64_t>(after.nx) * after.ny * after.nz; }
 };
+
+// The grid's brick and DynamicGrid size after the call, from p->box.
+template <typename Grid>
+int PlanBrick(const Grid* g, BrickPlan3* p) {
+  p->after = g->brick;
+  p->grid_size = g->grid_size;
+  p->touched = !p->box.empty();
+  if (!p->touched) return CSM_OK;
+  if (GrownBrick(g->brick, p->box, &p->after, &p->grid_size) != CSM_OK) return CSM_ERANGE;
+  p->grew = p->after.nx != g->brick.nx || p->after.ny != g->brick.ny || p->after.nz != g->brick.nz;
+  return CSM_OK;
+}
+
+// A grown grid's new bricks, and the event consumers on other streams wait on.
+int ReserveBrick(csm_context* ctx, BrickPlan3* p, size_t bytes_a, size_t bytes_b,
+                 hipEvent_t* ready) {
+  if (!*ready) CSM_HIP(hipEventCreateWithFlags(ready, hipEventDisableTiming));
+  if (!p->grew) return CSM_OK;
+  const int rc = ctx->pool.Take(bytes_a, &p->a);
+  return rc != CSM_OK ? rc : ctx->pool.Take(bytes_b, &p->b);
+}
+
+void GiveBackBricks(csm_context* ctx, std::vector<BrickPlan3>* plan) {
+  for (BrickPlan3& p : *plan) {
+    ctx->pool.Give(&p.a);
+    ctx->pool.Give(&p.b);
+  }
+}
+
+// Enqueues a touched grid's growth (the old cells at their offset, `unknown`
+// in b elsewhere), swaps the new bricks in and moves the grid's host state on.
+template <typename A, typename B, typename Grid>
+int CommitBrick(csm_context* ctx, Grid* g, DevBuf Grid::*a, DevBuf Grid::*b, B unknown,
+                BrickPlan3* p, std::deque<DevBuf>* retired) {
+  if (p->grew) {
+    hipLaunchKernelGGL(insert3d_grow, dim3(Blocks(p->cells(), 1024, 8192)), dim3(256), 0,
+                       ctx->stream, (g->*a).template as<A>(), (g->*b).template as<B>(), g->brick,
+                       p->a.as<A>(), p->b.as<B>(), p->after, unknown);
+    CSM_HIP(hipGetLastError());
+    retired->push_back(std::move(g->*a));
+    retired->push_back(std::move(g->*b));
+    g->*a = std::move(p->a);
+    g->*b = std::move(p->b);
+  }
+  g->brick = p->after;
+  g->grid_size = p->grid_size;
+  ++g->generation;
+  return CSM_OK;
+}
 
 int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_grids,
                  const csm_inserter3d_options* o, int32_t num_scans, const float* origins,
@@ -598,16 +609,8 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   for (int g = 0; g < num_grids; ++g)
     if (!grids[g]) return CSM_EINVAL;
   if (num_jobs == 0) return CSM_OK;
-  if (num_scans == 0) return CSM_EINVAL;
-  if (ret_off[0] != 0) return CSM_EINVAL;
-  for (int s = 0; s < num_scans; ++s) {
-    if (ret_off[s + 1] < ret_off[s] || ret_off[s + 1] - ret_off[s] > (1 << 24)) return CSM_EINVAL;
-    if (!Finite3(origins + 3 * s)) return CSM_EINVAL;
-  }
+  if (num_scans == 0 || !ValidScans(num_scans, origins, ret_off, returns)) return CSM_EINVAL;
   const int64_t total_ret = ret_off[num_scans];
-  if (total_ret > 0 && !returns) return CSM_EINVAL;
-  for (int64_t i = 0; i < total_ret; ++i)
-    if (!Finite3(returns + 3 * i)) return CSM_EINVAL;
   for (int64_t i = 0; i < int64_t{7} * num_transforms; ++i)
     if (!std::isfinite(transforms[i])) return CSM_EINVAL;
   for (int k = 0; k < num_jobs; ++k) {
@@ -642,18 +645,10 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   // The points are checked before any handle is read.
   if (ctx_of_grid) ctx = grids[0]->ctx;
   if (!ctx) return CSM_EINVAL;
-  for (int g = 0; g < num_grids; ++g) {
-    if (grids[g]->ctx != ctx) return CSM_EINVAL;
-    for (int h = 0; h < g; ++h)
-      if (grids[h] == grids[g]) return CSM_EINVAL;
-  }
-  for (int g = 0; in && g < in->num_grids; ++g) {
-    if (in->grids[g]->ctx != ctx) return CSM_EINVAL;
-    for (int h = 0; h < g; ++h)
-      if (in->grids[h] == in->grids[g]) return CSM_EINVAL;
-  }
+  if (!ValidHandles(ctx, grids, num_grids) || (in && !ValidHandles(ctx, in->grids, in->num_grids)))
+    return CSM_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);
-  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  if (EnsureDevice(ctx)) return CSM_EHIP;
 
   // Plan on the host, before any launch: every job's origin cell and the box
   // of the cells it touches. Per ray the first miss cell and the hit cell
@@ -662,13 +657,14 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   // is the old box united with the touched one.
   const int free_voxels = o->num_free_space_voxels;
   std::vector<Job3> jobs(num_jobs);
-  std::vector<GridPlan3> plan(num_grids);
+  std::vector<BrickPlan3> plan(num_grids), iplan(in ? in->num_grids : 0);
+  std::vector<DevBuf> stats(num_grids);  // the first insert's counters
+  std::vector<int> rounds(num_grids, 0);
   std::vector<int> round_of(num_jobs);
   std::vector<PlanTask> tasks;
   // The job's intensity grid, -1 where it has none or its scan carries no
   // intensities (:79), and that scan's intensities.
   std::vector<int> igrid_of(num_jobs, -1);
-  std::vector<IntensPlan3> iplan(in ? in->num_grids : 0);
   auto intensities_of = [&](int k) { return in->scan_intensities[scan_of_job[k]]; };
   for (int k = 0; in && in->grid_of_job && in->scan_intensities && k < num_jobs; ++k)
     if (in->grid_of_job[k] >= 0 && intensities_of(k)) igrid_of[k] = in->grid_of_job[k];
@@ -677,9 +673,8 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   for (int k = 0; k < num_jobs; ++k) {
     Job3& j = jobs[k];
     csm_hybrid_grid* g = grids[grid_of_job[k]];
-    GridPlan3& gp = plan[grid_of_job[k]];
-    round_of[k] = gp.rounds++;
-    num_rounds = std::max(num_rounds, gp.rounds);
+    round_of[k] = rounds[grid_of_job[k]]++;
+    num_rounds = std::max(num_rounds, round_of[k] + 1);
     const int s = scan_of_job[k];
     j.resolution = g->resolution;
     j.has_transform = transform_of_job && transform_of_job[k] >= 0;
@@ -708,101 +703,53 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
           PlanTask{k, i0, std::min(j.num_returns, i0 + kPlanChunk), Box3{}, CSM_OK, Box3{}});
     planned += j.num_returns;
   }
-  {
-    // Large scans are planned on a few threads, a chunk of returns at a time.
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-      for (size_t t; (t = next.fetch_add(1)) < tasks.size();) {
-        PlanTask& task = tasks[t];
-        // The boxes grow in locals and are stored once: neighbouring tasks
-        // share cache lines, and a store per return from every thread made
-        // the 55 000-return plan two to three times slower.
-        Box3 box, ibox;
-        int rc = PlanReturns(jobs[task.job], returns, task.i0, task.i1, free_voxels, &box);
-        const int ig = igrid_of[task.job];
-        if (rc == CSM_OK && ig >= 0)
-          rc = PlanIntensities(jobs[task.job], returns, intensities_of(task.job),
-                               in->grids[ig]->resolution, in->threshold, task.i0, task.i1, &ibox);
-        task.box = box;
-        task.ibox = ibox;
-        task.rc = rc;
-      }
-    };
-    const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-    const size_t nthreads =
-        planned >= kPlanThreaded ? std::min<size_t>({tasks.size(), hw, kPlanThreads}) : 1;
-    std::vector<std::thread> pool;
-    try {
-      for (size_t t = 1; t < nthreads; ++t) pool.emplace_back(work);
-    } catch (...) {  // no more threads: the ones there are share the chunks
-    }
-    work();
-    for (std::thread& t : pool) t.join();
-    for (const PlanTask& task : tasks) {
-      if (task.rc != CSM_OK) return task.rc;
-      if (!task.box.empty()) {
-        Box3& box = plan[grid_of_job[task.job]].box;
-        box.Add(task.box.lo[0], task.box.lo[1], task.box.lo[2]);
-        box.Add(task.box.hi[0], task.box.hi[1], task.box.hi[2]);
-      }
-      if (!task.ibox.empty()) {
-        Box3& box = iplan[igrid_of[task.job]].box;
-        box.Add(task.ibox.lo[0], task.ibox.lo[1], task.ibox.lo[2]);
-        box.Add(task.ibox.hi[0], task.ibox.hi[1], task.ibox.hi[2]);
-      }
-    }
+  // Large scans are planned on a few threads, a chunk of returns at a time.
+  RunPlanTasks(tasks.size(), planned, [&](size_t t) {
+    PlanTask& task = tasks[t];
+    // The boxes grow in locals and are stored once: neighbouring tasks
+    // share cache lines, and a store per return from every thread made
+    // the 55 000-return plan two to three times slower.
+    Box3 box, ibox;
+    int rc = PlanReturns(jobs[task.job], returns, task.i0, task.i1, free_voxels, &box);
+    const int ig = igrid_of[task.job];
+    if (rc == CSM_OK && ig >= 0)
+      rc = PlanIntensities(jobs[task.job], returns, intensities_of(task.job),
+                           in->grids[ig]->resolution, in->threshold, task.i0, task.i1, &ibox);
+    task.box = box;
+    task.ibox = ibox;
+    task.rc = rc;
+  });
+  for (const PlanTask& task : tasks) {
+    if (task.rc != CSM_OK) return task.rc;
+    plan[grid_of_job[task.job]].box.Add(task.box);
+    if (!task.ibox.empty()) iplan[igrid_of[task.job]].box.Add(task.ibox);
   }
-  for (size_t gi = 0; gi < iplan.size(); ++gi) {
-    IntensPlan3& ip = iplan[gi];
-    const csm_intensity_grid* g = in->grids[gi];
-    ip.after = g->brick;
-    ip.grid_size = g->grid_size;
-    ip.touched = !ip.box.empty();
-    if (!ip.touched) continue;
-    if (GrownBrick(g->brick, ip.box, &ip.after, &ip.grid_size) != CSM_OK) return CSM_ERANGE;
-    ip.grew = ip.after.nx != g->brick.nx || ip.after.ny != g->brick.ny ||
-              ip.after.nz != g->brick.nz;
-  }
+  for (size_t gi = 0; gi < iplan.size(); ++gi)
+    if (PlanBrick(in->grids[gi], &iplan[gi])) return CSM_ERANGE;
   for (int gi = 0; gi < num_grids; ++gi) {
-    GridPlan3& gp = plan[gi];
-    const csm_hybrid_grid* g = grids[gi];
-    gp.after = g->brick;
-    gp.grid_size = g->grid_size;
-    gp.touched = !gp.box.empty();
-    if (!gp.touched) continue;
-    const Brick3& b = g->brick;
-    const bool had = b.nx > 0;
-    if (GrownBrick(b, gp.box, &gp.after, &gp.grid_size) != CSM_OK) return CSM_ERANGE;
-    const int64_t n = static_cast<int64_t>(gp.after.nx) * gp.after.ny * gp.after.nz;
+    BrickPlan3& p = plan[gi];
+    if (PlanBrick(grids[gi], &p)) return CSM_ERANGE;
     // A brick csm_hybrid_grid_create sized to an odd cell count is moved once
     // so that its last cell has a whole word.
-    gp.grew = !had || gp.after.nx != b.nx || gp.after.ny != b.ny || gp.after.nz != b.nz ||
-              g->values.bytes < ValueBytes(n);
+    if (p.touched && grids[gi]->values.bytes < ValueBytes(p.cells())) p.grew = true;
   }
 
   // Allocate before anything is enqueued: a failure leaves the grids as they
   // were.
   int rc = EnsureTables3(ctx, o);
   auto give_back = [&] {
-    for (GridPlan3& gp : plan) {
-      if (gp.values.ptr) ctx->pool.Give(&gp.values);
-      if (gp.prob.ptr) ctx->pool.Give(&gp.prob);
-      if (gp.stats.ptr) ctx->pool.Give(&gp.stats);
-    }
-    for (IntensPlan3& ip : iplan) {
-      if (ip.sum.ptr) ctx->pool.Give(&ip.sum);
-      if (ip.count.ptr) ctx->pool.Give(&ip.count);
-    }
+    GiveBackBricks(ctx, &plan);
+    GiveBackBricks(ctx, &iplan);
+    for (DevBuf& b : stats) ctx->pool.Give(&b);
   };
   for (int gi = 0; gi < num_grids && rc == CSM_OK; ++gi) {
-    GridPlan3& gp = plan[gi];
-    if (!gp.touched) continue;
+    BrickPlan3& p = plan[gi];
+    if (!p.touched) continue;
     if (!grids[gi]->insert_stats.ptr)
-      rc = ctx->pool.Take(2 * sizeof(unsigned long long), &gp.stats);
-    if (rc != CSM_OK || !gp.grew) continue;
-    const int64_t n = static_cast<int64_t>(gp.after.nx) * gp.after.ny * gp.after.nz;
-    if ((rc = ctx->pool.Take(ValueBytes(n), &gp.values)) == CSM_OK)
-      rc = ctx->pool.Take(sizeof(float) * n, &gp.prob);
+      rc = ctx->pool.Take(2 * sizeof(unsigned long long), &stats[gi]);
+    if (rc == CSM_OK)
+      rc = ReserveBrick(ctx, &p, ValueBytes(p.cells()), sizeof(float) * p.cells(),
+                        &grids[gi]->ready);
   }
   // Jobs in round order (stable), then one upload: descriptors and returns.
   std::vector<int> order;
@@ -811,11 +758,10 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   std::stable_sort(order.begin(), order.end(),
                    [&](int a, int b) { return round_of[a] < round_of[b]; });
   const int live = static_cast<int>(order.size());
-  const size_t desc_bytes = (sizeof(Job3) * std::max(live, 1) + 255) & ~size_t(255);
+  const size_t desc_bytes = Align(sizeof(Job3) * std::max(live, 1));
   size_t bytes = desc_bytes + sizeof(float) * 3 * total_ret;
   // The intensity halves, in the same order: a launch set is the jobs of one
   // round (at most gridDim.y of them) whose intensity grid gains a return.
-  auto align = [](size_t n) { return (n + 255) & ~size_t(255); };
   std::vector<IJob3> ijobs;
   std::vector<IntensSet3> isets;
   for (int i = 0; i < live; ++i) {
@@ -836,8 +782,8 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   }
   size_t idesc_at = 0, ival_at = 0, sort_bytes = 0, pair_cap = 0, scratch_bytes = 256;
   if (!ijobs.empty()) {
-    idesc_at = align(bytes);
-    ival_at = idesc_at + align(sizeof(IJob3) * ijobs.size());
+    idesc_at = Align(bytes);
+    ival_at = idesc_at + Align(sizeof(IJob3) * ijobs.size());
     bytes = ival_at + sizeof(float) * total_ret;
     for (IntensSet3& set : isets) {
       if (set.pairs >= (int64_t{1} << 31)) rc = CSM_ERANGE;  // the sort counts in 32 bits
@@ -856,18 +802,13 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
       pair_cap = std::max(pair_cap, static_cast<size_t>(set.pairs));
     }
     // keys, sorted keys, indices, sorted indices, scratch.
-    sort_bytes = 2 * align(8 * pair_cap) + 2 * align(4 * pair_cap) + align(scratch_bytes);
+    sort_bytes = 2 * Align(8 * pair_cap) + 2 * Align(4 * pair_cap) + Align(scratch_bytes);
   }
   for (size_t gi = 0; gi < iplan.size() && rc == CSM_OK; ++gi) {
-    IntensPlan3& ip = iplan[gi];
-    csm_intensity_grid* g = in->grids[gi];
-    if (!ip.touched) continue;
-    if (!g->ready && hipEventCreateWithFlags(&g->ready, hipEventDisableTiming) != hipSuccess)
-      rc = CSM_EHIP;
-    if (rc != CSM_OK || !ip.grew) continue;
-    const int64_t n = static_cast<int64_t>(ip.after.nx) * ip.after.ny * ip.after.nz;
-    if ((rc = ctx->pool.Take(sizeof(float) * n, &ip.sum)) == CSM_OK)
-      rc = ctx->pool.Take(sizeof(int32_t) * n, &ip.count);
+    BrickPlan3& p = iplan[gi];
+    if (p.touched)
+      rc = ReserveBrick(ctx, &p, sizeof(float) * p.cells(), sizeof(int32_t) * p.cells(),
+                        &in->grids[gi]->ready);
   }
   if (rc == CSM_OK && ctx->ins3_sort.bytes < sort_bytes) {
     // As ins3_dev below: an earlier insert may still sort in it.
@@ -875,71 +816,31 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     else rc = ctx->ins3_sort.Reserve(sort_bytes + sort_bytes / 2);
   }
   StageRing::Slot* slot = nullptr;
-  if (rc == CSM_OK && live > 0) rc = ctx->ins3_stage.Take(bytes, &slot);
-  if (rc == CSM_OK && live > 0 && ctx->ins3_dev.bytes < bytes) {
-    // The buffer is replaced: earlier inserts on the stream may still read it.
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CSM_EHIP;
-    else rc = ctx->ins3_dev.Reserve(bytes + bytes / 2);
-  }
-  for (int gi = 0; gi < num_grids && rc == CSM_OK; ++gi) {
-    csm_hybrid_grid* g = grids[gi];
-    if (plan[gi].touched && !g->ready &&
-        hipEventCreateWithFlags(&g->ready, hipEventDisableTiming) != hipSuccess)
-      rc = CSM_EHIP;
-  }
+  if (rc == CSM_OK && live > 0)
+    rc = ReserveUpload(ctx, &ctx->ins3_stage, &ctx->ins3_dev, bytes, &slot);
   if (rc != CSM_OK) {
     give_back();
     return rc;
   }
   hipStream_t st = ctx->stream;
-  // From here on a failure is a HIP error: the stream's state is unknown.
+  // From here on a failure is a HIP error (insert_host.h).
   std::deque<DevBuf> retired;
   for (int gi = 0; gi < num_grids; ++gi) {
-    GridPlan3& gp = plan[gi];
     csm_hybrid_grid* g = grids[gi];
-    if (!gp.touched) continue;
-    if (gp.stats.ptr) {
-      CSM_HIP(hipMemsetAsync(gp.stats.ptr, 0, 2 * sizeof(unsigned long long), st));
-      MoveBuf(&gp.stats, &g->insert_stats);
+    if (!plan[gi].touched) continue;
+    if (stats[gi].ptr) {
+      CSM_HIP(hipMemsetAsync(stats[gi].ptr, 0, 2 * sizeof(unsigned long long), st));
+      g->insert_stats = std::move(stats[gi]);
     }
-    if (gp.grew) {
-      const int64_t n = static_cast<int64_t>(gp.after.nx) * gp.after.ny * gp.after.nz;
-      hipLaunchKernelGGL(insert3d_grow, dim3(Blocks(n, 1024, 8192)), dim3(256), 0, st,
-                         g->values.as<uint16_t>(), g->prob.as<float>(), g->brick,
-                         gp.values.as<uint16_t>(), gp.prob.as<float>(), gp.after, kMinP);
-      CSM_HIP(hipGetLastError());
-      retired.emplace_back();
-      MoveBuf(&g->values, &retired.back());
-      retired.emplace_back();
-      MoveBuf(&g->prob, &retired.back());
-      MoveBuf(&gp.values, &g->values);
-      MoveBuf(&gp.prob, &g->prob);
-    }
-    g->brick = gp.after;
-    g->grid_size = gp.grid_size;
-    ++g->generation;
+    if ((rc = CommitBrick<uint16_t>(ctx, g, &csm_hybrid_grid::values, &csm_hybrid_grid::prob,
+                                    kMinP, &plan[gi], &retired)))
+      return rc;
   }
-  for (size_t gi = 0; gi < iplan.size(); ++gi) {
-    IntensPlan3& ip = iplan[gi];
-    csm_intensity_grid* g = in->grids[gi];
-    if (!ip.touched) continue;
-    if (ip.grew) {
-      const int64_t n = static_cast<int64_t>(ip.after.nx) * ip.after.ny * ip.after.nz;
-      hipLaunchKernelGGL(insert3d_grow, dim3(Blocks(n, 1024, 8192)), dim3(256), 0, st,
-                         g->sum.as<float>(), g->count.as<int32_t>(), g->brick,
-                         ip.sum.as<float>(), ip.count.as<int32_t>(), ip.after, int32_t{0});
-      CSM_HIP(hipGetLastError());
-      retired.emplace_back();
-      MoveBuf(&g->sum, &retired.back());
-      retired.emplace_back();
-      MoveBuf(&g->count, &retired.back());
-      MoveBuf(&ip.sum, &g->sum);
-      MoveBuf(&ip.count, &g->count);
-    }
-    g->brick = ip.after;
-    g->grid_size = ip.grid_size;
-    ++g->generation;
-  }
+  for (size_t gi = 0; gi < iplan.size(); ++gi)
+    if (iplan[gi].touched &&
+        (rc = CommitBrick<float>(ctx, in->grids[gi], &csm_intensity_grid::sum,
+                                 &csm_intensity_grid::count, int32_t{0}, &iplan[gi], &retired)))
+      return rc;
   if (live > 0) {
     Job3* hd = slot->buf.as<Job3>();
     for (int i = 0; i < live; ++i) {
@@ -966,8 +867,7 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
       }
       std::memcpy(slot->buf.as<char>() + idesc_at, ijobs.data(), sizeof(IJob3) * ijobs.size());
     }
-    CSM_HIP(hipMemcpyAsync(ctx->ins3_dev.ptr, slot->buf.ptr, bytes, hipMemcpyHostToDevice, st));
-    CSM_HIP(hipEventRecord(slot->copied, st));
+    if ((rc = Upload(ctx, slot, &ctx->ins3_dev, bytes))) return rc;
     const Job3* dd = ctx->ins3_dev.as<Job3>();
     const float* dpts = reinterpret_cast<const float*>(ctx->ins3_dev.as<char>() + desc_bytes);
     const uint16_t* tabs = ctx->ins3_tabs.as<uint16_t>();
@@ -981,10 +881,10 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
     const float* dval = reinterpret_cast<const float*>(ctx->ins3_dev.as<char>() + ival_at);
     char* sort_at = ctx->ins3_sort.as<char>();
     uint64_t* keys = reinterpret_cast<uint64_t*>(sort_at);
-    uint64_t* sorted_keys = reinterpret_cast<uint64_t*>(sort_at + align(8 * pair_cap));
-    uint32_t* vals = reinterpret_cast<uint32_t*>(sort_at + 2 * align(8 * pair_cap));
-    uint32_t* sorted_vals = vals + align(4 * pair_cap) / sizeof(uint32_t);
-    void* scratch = sorted_vals + align(4 * pair_cap) / sizeof(uint32_t);
+    uint64_t* sorted_keys = reinterpret_cast<uint64_t*>(sort_at + Align(8 * pair_cap));
+    uint32_t* vals = reinterpret_cast<uint32_t*>(sort_at + 2 * Align(8 * pair_cap));
+    uint32_t* sorted_vals = vals + Align(4 * pair_cap) / sizeof(uint32_t);
+    void* scratch = sorted_vals + Align(4 * pair_cap) / sizeof(uint32_t);
     size_t next_set = 0;
     int i0 = 0;
     for (int r = 0; r < num_rounds && i0 < live; ++r) {
@@ -1034,8 +934,7 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
   for (size_t gi = 0; gi < iplan.size(); ++gi)
     if (iplan[gi].touched) CSM_HIP(hipEventRecord(in->grids[gi]->ready, st));
   // The old bricks of grown grids: reused by later takes on this stream.
-  for (DevBuf& b : retired)
-    if (b.ptr) ctx->pool.Give(&b);
+  for (DevBuf& b : retired) ctx->pool.Give(&b);
   return CSM_OK;
 }
 
@@ -1171,7 +1070,7 @@ int csm_intensity_grid_read(const csm_intensity_grid* g, float* sums_out, int32_
   const int64_t n = static_cast<int64_t>(g->brick.nx) * g->brick.ny * g->brick.nz;
   if (capacity < n || (n > 0 && (!sums_out || !counts_out))) return CSM_EINVAL;
   if (n == 0) return CSM_OK;  // nothing was ever enqueued for this grid
-  if (hipSetDevice(g->ctx->device) != hipSuccess) return CSM_EHIP;
+  if (EnsureDevice(g->ctx)) return CSM_EHIP;
   CSM_HIP(hipMemcpyAsync(sums_out, g->sum.ptr, n * sizeof(float), hipMemcpyDeviceToHost,
                          g->ctx->stream));
   CSM_HIP(hipMemcpyAsync(counts_out, g->count.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost,
@@ -1208,7 +1107,7 @@ int csm_hybrid_grid_read(const csm_hybrid_grid* g, uint16_t* out, int64_t capaci
   std::lock_guard<std::mutex> lock(g->ctx->mu);
   const int64_t n = static_cast<int64_t>(g->brick.nx) * g->brick.ny * g->brick.nz;
   if (capacity < n || (n > 0 && !out)) return CSM_EINVAL;
-  if (hipSetDevice(g->ctx->device) != hipSuccess) return CSM_EHIP;
+  if (EnsureDevice(g->ctx)) return CSM_EHIP;
   if (n > 0)
     CSM_HIP(hipMemcpyAsync(out, g->values.ptr, n * sizeof(uint16_t), hipMemcpyDeviceToHost,
                            g->ctx->stream));
@@ -1222,7 +1121,7 @@ int csm_hybrid_grid_insert_stats(const csm_hybrid_grid* g, int64_t* cells_visite
   std::lock_guard<std::mutex> lock(g->ctx->mu);
   unsigned long long s[2] = {0, 0};
   if (g->insert_stats.ptr) {
-    if (hipSetDevice(g->ctx->device) != hipSuccess) return CSM_EHIP;
+    if (EnsureDevice(g->ctx)) return CSM_EHIP;
     CSM_HIP(hipMemcpyAsync(s, g->insert_stats.ptr, sizeof(s), hipMemcpyDeviceToHost,
                            g->ctx->stream));
     CSM_HIP(hipStreamSynchronize(g->ctx->stream));

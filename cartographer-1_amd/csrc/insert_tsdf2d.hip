@@ -46,6 +46,9 @@
 // difference survives only on a float rounding boundary. f32 denormals are
 // kept (the compiler's default for gfx950): narrow bandwidths produce denormal
 // weights, and w == 0.f decides who claims a cell.
+//
+// The host steps of an insert call around the kernels are insert_host.h's;
+// growth, create and crop over the three planes are insert2d_common.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -56,7 +59,6 @@
 #include <limits>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "csm_internal.h"
@@ -66,8 +68,6 @@ namespace csm {
 namespace {
 
 constexpr uint32_t kNoRank = 0xffffffffu;
-constexpr int kPlanThreads = 8;            // most threads a batch is planned on
-constexpr int64_t kPlanThreaded = 32768;   // returns per call from which threads pay off
 
 // One ray of a scan, in the reference's iteration order.
 struct TsdfRay {
@@ -492,13 +492,81 @@ bool ValidOptions(const csm_tsdf_inserter_options* o) {
          std::isfinite(o->update_weight_distance_cell_to_hit_kernel_bandwidth);
 }
 
-struct GrowPlan {
-  int grid = 0, round = 0;
-  bool grew = false;
-  int off_x = 0, off_y = 0;
-  csm_map_limits before{}, after{};
-  DevBuf tsd, weight, rank;  // the grown grid's buffers
-};
+size_t CellBytes(size_t nx, size_t ny) { return nx * ny * sizeof(uint16_t); }
+size_t RankBytes(size_t nx, size_t ny) { return nx * ny * sizeof(uint32_t); }
+// The planes of a TSDF2D as growth sees them (insert2d_common.h).
+const Plane2<csm_tsdf_grid> kPlanes[] = {{&csm_tsdf_grid::tsd, CellBytes, 0, true},
+                                         {&csm_tsdf_grid::weight, CellBytes, 0, true},
+                                         {&csm_tsdf_grid::rank, RankBytes, 0xff, false}};
+
+// A scan's descriptor in limits `l`, without the planes.
+TsdfScanDev ScanDesc(const csm_tsdf_grid* g, const TsdfTables* tabs, const csm_map_limits& l,
+                     const float* origin, int num_rays, int64_t ray_begin) {
+  const Converter conv(g->truncation, g->max_weight);
+  TsdfScanDev d{};
+  d.to_float = tabs->to_float.as<float>();
+  d.nx = l.num_x_cells;
+  d.ny = l.num_y_cells;
+  d.max_x = l.max_x;
+  d.max_y = l.max_y;
+  d.resolution = l.resolution;
+  d.ox = origin[0];
+  d.oy = origin[1];
+  d.num_rays = num_rays;
+  d.ray_begin = ray_begin;
+  d.min_tsd = conv.min_tsd;
+  d.max_tsd = conv.max_tsd;
+  d.tsd_resolution = conv.tsd_resolution;
+  d.conv_max_weight = conv.max_weight;
+  d.weight_resolution = conv.weight_resolution;
+  return d;
+}
+
+// A scan's rays in the grown limits `l`. SuperscaleRay (:53-67): GetCellIndex
+// on the x1000 limits, in double.
+void SuperscaleRays(const csm_map_limits& l, const std::vector<RayPlan>& rays, TsdfRay* out) {
+  const double fine = l.resolution / kSubpixelScale;
+  const long fnx = static_cast<long>(l.num_x_cells) * kSubpixelScale;
+  const long fny = static_cast<long>(l.num_y_cells) * kSubpixelScale;
+  for (size_t k = 0; k < rays.size(); ++k) {
+    const RayPlan& r = rays[k];
+    TsdfRay& q = out[k];
+    q = TsdfRay{};
+    if (!r.cast) continue;
+    long bx, by, ex, ey;
+    CellIndex(l, fine, r.bx, r.by, &bx, &by);
+    CellIndex(l, fine, r.ex, r.ey, &ex, &ey);
+    // Outside the limits the reference CHECK-fails; such a ray is dropped.
+    if (bx < 0 || by < 0 || ex < 0 || ey < 0 || bx >= fnx || ex >= fnx || by >= fny ||
+        ey >= fny)
+      continue;
+    q.bx = static_cast<int>(bx);
+    q.by = static_cast<int>(by);
+    q.ex = static_cast<int>(ex);
+    q.ey = static_cast<int>(ey);
+    q.hx = r.hx;
+    q.hy = r.hy;
+    q.range = r.range;
+    q.cosn = r.cosn;
+    q.sinn = r.sinn;
+    q.w = r.w;
+    q.cast = 1;
+  }
+}
+
+TsdfOptsDev OptsDev(const csm_tsdf_inserter_options* o) {
+  TsdfOptsDev od{};
+  od.truncation = static_cast<float>(o->truncation_distance);
+  od.maximum_weight = static_cast<float>(o->maximum_weight);
+  od.project = o->project_sdf_distance_to_scan_normal != 0;
+  od.distance_kernel = o->update_weight_distance_cell_to_hit_kernel_bandwidth != 0.f;
+  if (od.distance_kernel) {
+    const float sigma = static_cast<float>(o->update_weight_distance_cell_to_hit_kernel_bandwidth);
+    od.dist_pre = 1.0 / (kSqrtTwoPi * sigma);
+    od.dist_sigma2 = sigma * sigma;
+  }
+  return od;
+}
 
 int InsertBatch(csm_context* ctx, csm_tsdf_grid* const* grids, int32_t num_grids,
                 const csm_tsdf_inserter_options* o, int32_t num_scans,
@@ -510,55 +578,28 @@ int InsertBatch(csm_context* ctx, csm_tsdf_grid* const* grids, int32_t num_grids
   for (int g = 0; g < num_grids; ++g)
     if (!grids[g]) return CSM_EINVAL;
   if (num_scans == 0) return CSM_OK;
-  const int64_t total_ret = ret_off[num_scans];
-  if (ret_off[0] != 0 || (total_ret > 0 && !returns)) return CSM_EINVAL;
-  for (int s = 0; s < num_scans; ++s) {
+  if (!ValidScans(num_scans, origins, ret_off, returns)) return CSM_EINVAL;
+  for (int s = 0; s < num_scans; ++s)
     if (grid_of_scan[s] < 0 || grid_of_scan[s] >= num_grids) return CSM_EINVAL;
-    if (ret_off[s + 1] < ret_off[s] || ret_off[s + 1] - ret_off[s] > (1 << 24)) return CSM_EINVAL;
-    if (!Finite3(origins + 3 * s)) return CSM_EINVAL;
-  }
-  for (int64_t i = 0; i < total_ret; ++i)
-    if (!Finite3(returns + 3 * i)) return CSM_EINVAL;
-
+  const int64_t total_ret = ret_off[num_scans];
   // The points are checked before any handle is read.
-  for (int g = 0; g < num_grids; ++g) {
-    if (grids[g]->ctx != ctx) return CSM_EINVAL;
-    for (int h = 0; h < g; ++h)
-      if (grids[h] == grids[g]) return CSM_EINVAL;
-  }
+  if (!ValidHandles(ctx, grids, num_grids)) return CSM_EINVAL;
 
   // The part of the plan that needs no grid, before the lock; batches of many
   // returns on a few threads, a scan at a time.
   std::vector<ScanPlanHost> host(num_scans);
-  {
-    std::atomic<int> next{0};
-    auto work = [&] {
-      for (int s; (s = next.fetch_add(1)) < num_scans;)
-        PlanScan(*o, origins + 3 * s, returns + 3 * ret_off[s],
-                 static_cast<int32_t>(ret_off[s + 1] - ret_off[s]), &host[s]);
-    };
-    const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-    const size_t nthreads =
-        total_ret >= kPlanThreaded
-            ? std::min<size_t>({static_cast<size_t>(num_scans), hw, size_t{kPlanThreads}})
-            : 1;
-    std::vector<std::thread> pool;
-    try {
-      for (size_t t = 1; t < nthreads; ++t) pool.emplace_back(work);
-    } catch (...) {  // no more threads: the ones there are share the scans
-    }
-    work();
-    for (std::thread& t : pool) t.join();
-  }
+  RunPlanTasks(num_scans, total_ret, [&](size_t s) {
+    PlanScan(*o, origins + 3 * s, returns + 3 * ret_off[s],
+             static_cast<int32_t>(ret_off[s + 1] - ret_off[s]), &host[s]);
+  });
 
   std::lock_guard<std::mutex> lock(ctx->mu);
   if (EnsureDevice(ctx)) return CSM_EHIP;
   for (int g = 0; g < num_grids; ++g)
     if (grids[g]->finished) return CSM_EINVAL;
 
-  // On the host's copy of the limits: each scan's growth, its round, and its
-  // rays' subpixel indices in the grown limits.
-  std::vector<GrowPlan> plan(num_scans);
+  // On the host's copy of the limits: each scan's growth and its round.
+  std::vector<GrowPlan2> plan(num_scans);
   std::vector<csm_map_limits> cur(num_grids);
   std::vector<int> rounds(num_grids, 0);
   std::vector<TsdfScanDev> descs(num_scans);
@@ -568,208 +609,67 @@ int InsertBatch(csm_context* ctx, csm_tsdf_grid* const* grids, int32_t num_grids
     cur[g] = grids[g]->limits;
     if ((rc = EnsureTables(ctx, grids[g]->truncation, grids[g]->max_weight, &tabs[g]))) return rc;
   }
-  int num_rounds = 0;
   for (int s = 0; s < num_scans; ++s) {
-    GrowPlan& p = plan[s];
     const ScanPlanHost& hp = host[s];
-    p.grid = grid_of_scan[s];
-    p.round = rounds[p.grid]++;
-    num_rounds = std::max(num_rounds, p.round + 1);
-    constexpr float kPadding = 1e-6f;
-    csm_map_limits& l = cur[p.grid];
-    p.before = l;
-    if (!GrowLimits(&l, hp.bmin_x - kPadding, hp.bmin_y - kPadding, &p.off_x, &p.off_y) ||
-        !GrowLimits(&l, hp.bmax_x + kPadding, hp.bmax_y + kPadding, &p.off_x, &p.off_y))
-      return CSM_ERANGE;
-    p.after = l;
-    p.grew = l.num_x_cells != p.before.num_x_cells;
-    const csm_tsdf_grid* g = grids[p.grid];
-    const Converter conv(g->truncation, g->max_weight);
-    TsdfScanDev& d = descs[s];
-    d.to_float = tabs[p.grid]->to_float.as<float>();
-    d.nx = l.num_x_cells;
-    d.ny = l.num_y_cells;
-    d.max_x = l.max_x;
-    d.max_y = l.max_y;
-    d.resolution = l.resolution;
-    d.ox = origins[3 * s];
-    d.oy = origins[3 * s + 1];
-    d.num_rays = static_cast<int>(hp.rays.size());
-    d.ray_begin = ret_off[s];
-    d.min_tsd = conv.min_tsd;
-    d.max_tsd = conv.max_tsd;
-    d.tsd_resolution = conv.tsd_resolution;
-    d.conv_max_weight = conv.max_weight;
-    d.weight_resolution = conv.weight_resolution;
+    const int g = grid_of_scan[s];
+    const float box[4] = {hp.bmin_x, hp.bmin_y, hp.bmax_x, hp.bmax_y};
+    if (!PlanGrowth2(g, box, &cur, &rounds, &plan[s])) return CSM_ERANGE;
+    descs[s] = ScanDesc(grids[g], tabs[g], plan[s].after, origins + 3 * s,
+                        static_cast<int>(hp.rays.size()), ret_off[s]);
   }
-
-  // Allocate every grown grid before anything is enqueued: a failure leaves
-  // the grids as they were.
-  auto give_back = [&] {
-    for (GrowPlan& p : plan)
-      for (DevBuf* b : {&p.tsd, &p.weight, &p.rank})
-        if (b->ptr) ctx->pool.Give(b);
-  };
-  rc = CSM_OK;
-  for (int s = 0; s < num_scans && rc == CSM_OK; ++s) {
-    GrowPlan& p = plan[s];
-    if (!p.grew) continue;
-    const size_t n = static_cast<size_t>(p.after.num_x_cells) * p.after.num_y_cells;
-    if ((rc = ctx->pool.Take(n * sizeof(uint16_t), &p.tsd)) == CSM_OK &&
-        (rc = ctx->pool.Take(n * sizeof(uint16_t), &p.weight)) == CSM_OK)
-      rc = ctx->pool.Take(n * sizeof(uint32_t), &p.rank);
-  }
-  // Scans in round order (stable), descriptors with the buffers each scan
-  // will see, then one upload: descriptors, rays.
+  // Scans in round order (stable).
   std::vector<int> order(num_scans);
   for (int s = 0; s < num_scans; ++s) order[s] = s;
   std::stable_sort(order.begin(), order.end(),
                    [&](int a, int b) { return plan[a].round < plan[b].round; });
-  const size_t desc_bytes = (sizeof(TsdfScanDev) * num_scans + 255) & ~size_t(255);
+
+  // Everything that can fail cleanly, before anything is enqueued: a failure
+  // leaves the grids as they were. One upload: descriptors, rays.
+  const size_t desc_bytes = Align(sizeof(TsdfScanDev) * num_scans);
   const size_t bytes = desc_bytes + sizeof(TsdfRay) * static_cast<size_t>(total_ret);
   StageRing::Slot* slot = nullptr;
-  if (rc == CSM_OK) rc = ctx->tsdf_stage.Take(bytes, &slot);
-  if (rc == CSM_OK && ctx->tsdf_dev.bytes < bytes) {
-    // The buffer is replaced: earlier inserts on the stream may still read it.
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CSM_EHIP;
-    else rc = ctx->tsdf_dev.Reserve(bytes + bytes / 2);
-  }
+  if ((rc = TakeGrown2(ctx, grids, num_grids, kPlanes, &plan)) == CSM_OK)
+    rc = ReserveUpload(ctx, &ctx->tsdf_stage, &ctx->tsdf_dev, bytes, &slot);
   if (rc != CSM_OK) {
-    give_back();
+    GiveBackGrown2(ctx, &plan);
     return rc;
   }
-  {
-    std::vector<uint16_t*> tsd(num_grids), weight(num_grids);
-    std::vector<uint32_t*> rank(num_grids);
-    for (int g = 0; g < num_grids; ++g) {
-      tsd[g] = grids[g]->tsd.as<uint16_t>();
-      weight[g] = grids[g]->weight.as<uint16_t>();
-      rank[g] = grids[g]->rank.as<uint32_t>();
-    }
-    TsdfScanDev* hd = slot->buf.as<TsdfScanDev>();
-    TsdfRay* hr = reinterpret_cast<TsdfRay*>(slot->buf.as<char>() + desc_bytes);
-    for (int i = 0; i < num_scans; ++i) {
-      const int s = order[i];
-      GrowPlan& p = plan[s];
-      if (p.grew) {
-        tsd[p.grid] = p.tsd.as<uint16_t>();
-        weight[p.grid] = p.weight.as<uint16_t>();
-        rank[p.grid] = p.rank.as<uint32_t>();
-      }
-      descs[s].tsd = tsd[p.grid];
-      descs[s].weight = weight[p.grid];
-      descs[s].rank = rank[p.grid];
-      hd[i] = descs[s];
-      // SuperscaleRay (:53-67): GetCellIndex on the x1000 limits, in double.
-      const csm_map_limits& l = p.after;
-      const double fine = l.resolution / kSubpixelScale;
-      const long fnx = static_cast<long>(l.num_x_cells) * kSubpixelScale;
-      const long fny = static_cast<long>(l.num_y_cells) * kSubpixelScale;
-      TsdfRay* out = hr + ret_off[s];
-      for (size_t k = 0; k < host[s].rays.size(); ++k) {
-        const RayPlan& r = host[s].rays[k];
-        TsdfRay& q = out[k];
-        q = TsdfRay{};
-        if (!r.cast) continue;
-        long bx, by, ex, ey;
-        CellIndex(l, fine, r.bx, r.by, &bx, &by);
-        CellIndex(l, fine, r.ex, r.ey, &ex, &ey);
-        // Outside the limits the reference CHECK-fails; such a ray is dropped.
-        if (bx < 0 || by < 0 || ex < 0 || ey < 0 || bx >= fnx || ex >= fnx || by >= fny ||
-            ey >= fny)
-          continue;
-        q.bx = static_cast<int>(bx);
-        q.by = static_cast<int>(by);
-        q.ex = static_cast<int>(ex);
-        q.ey = static_cast<int>(ey);
-        q.hx = r.hx;
-        q.hy = r.hy;
-        q.range = r.range;
-        q.cosn = r.cosn;
-        q.sinn = r.sinn;
-        q.w = r.w;
-        q.cast = 1;
-      }
-    }
+  TsdfScanDev* hd = slot->buf.as<TsdfScanDev>();
+  TsdfRay* hr = reinterpret_cast<TsdfRay*>(slot->buf.as<char>() + desc_bytes);
+  for (int i = 0; i < num_scans; ++i) {
+    const int s = order[i];
+    hd[i] = descs[s];
+    hd[i].tsd = static_cast<uint16_t*>(plan[s].seen[0]);
+    hd[i].weight = static_cast<uint16_t*>(plan[s].seen[1]);
+    hd[i].rank = static_cast<uint32_t*>(plan[s].seen[2]);
+    SuperscaleRays(plan[s].after, host[s].rays, hr + ret_off[s]);
   }
-  TsdfOptsDev od{};
-  od.truncation = static_cast<float>(o->truncation_distance);
-  od.maximum_weight = static_cast<float>(o->maximum_weight);
-  od.project = o->project_sdf_distance_to_scan_normal != 0;
-  od.distance_kernel = o->update_weight_distance_cell_to_hit_kernel_bandwidth != 0.f;
-  if (od.distance_kernel) {
-    const float sigma = static_cast<float>(o->update_weight_distance_cell_to_hit_kernel_bandwidth);
-    od.dist_pre = 1.0 / (kSqrtTwoPi * sigma);
-    od.dist_sigma2 = sigma * sigma;
-  }
+  const TsdfOptsDev od = OptsDev(o);
+  // From here on a failure is a HIP error (insert_host.h): the grids keep what
+  // they had when it struck.
+  if ((rc = Upload(ctx, slot, &ctx->tsdf_dev, bytes))) return rc;
   hipStream_t st = ctx->stream;
-  // From here on a failure is a HIP error: the stream's state is unknown and
-  // the grids keep their old buffers and limits.
-  if (hipMemcpyAsync(ctx->tsdf_dev.ptr, slot->buf.ptr, bytes, hipMemcpyHostToDevice, st) !=
-          hipSuccess ||
-      hipEventRecord(slot->copied, st) != hipSuccess) {
-    give_back();
-    return CSM_EHIP;
-  }
   const TsdfScanDev* dd = ctx->tsdf_dev.as<TsdfScanDev>();
   const TsdfRay* dr = reinterpret_cast<const TsdfRay*>(ctx->tsdf_dev.as<char>() + desc_bytes);
   std::deque<DevBuf> retired;
-  int i0 = 0;
-  for (int r = 0; r < num_rounds; ++r) {
-    int i1 = i0;
+  for (int i0 = 0, i1 = 0; i0 < num_scans; i0 = i1) {  // a round: [i0, i1)
     int64_t max_rays = 1;
-    for (; i1 < num_scans && plan[order[i1]].round == r; ++i1) {
+    for (; i1 < num_scans && plan[order[i1]].round == plan[order[i0]].round; ++i1) {
       const int s = order[i1];
-      GrowPlan& p = plan[s];
-      csm_tsdf_grid* g = grids[p.grid];
-      if (p.grew) {
-        const int nx = p.after.num_x_cells, ny = p.after.num_y_cells;
-        const size_t n = static_cast<size_t>(nx) * ny;
-        CSM_HIP(hipMemsetAsync(p.tsd.ptr, 0, n * sizeof(uint16_t), st));
-        CSM_HIP(hipMemsetAsync(p.weight.ptr, 0, n * sizeof(uint16_t), st));
-        CSM_HIP(hipMemsetAsync(p.rank.ptr, 0xff, n * sizeof(uint32_t), st));
-        const int ow = p.before.num_x_cells, oh = p.before.num_y_cells;
-        for (int plane = 0; plane < 2; ++plane) {
-          hipLaunchKernelGGL(insert2d_copy_rect, dim3(Blocks(int64_t{ow} * oh, 256, 4096)),
-                             dim3(256), 0, st,
-                             (plane ? g->weight : g->tsd).as<uint16_t>(), ow, 0, 0,
-                             (plane ? p.weight : p.tsd).as<uint16_t>(), nx, p.off_x, p.off_y, ow,
-                             oh);
-          CSM_HIP(hipGetLastError());
-        }
-        for (DevBuf* b : {&g->tsd, &g->weight, &g->rank}) {
-          retired.emplace_back();
-          MoveBuf(b, &retired.back());
-        }
-        MoveBuf(&p.tsd, &g->tsd);
-        MoveBuf(&p.weight, &g->weight);
-        MoveBuf(&p.rank, &g->rank);
-      }
-      g->limits = p.after;
-      ++g->generation;
+      if ((rc = CommitScan2(ctx, grids[plan[s].grid], kPlanes, &plan[s], &retired))) return rc;
       max_rays = std::max<int64_t>(max_rays, descs[s].num_rays);
     }
-    const unsigned ny = static_cast<unsigned>(i1 - i0);
-    // 65535 scans per launch (gridDim.y).
-    for (unsigned y0 = 0; y0 < ny; y0 += 65535) {
-      const unsigned nyy = std::min(65535u, ny - y0);
-      const dim3 blocks(Blocks(max_rays, 4, 1024), nyy);
-      hipLaunchKernelGGL(tsdf2d_claim, blocks, dim3(256), 0, st, dd + i0 + y0, dr, od);
+    for (int y0 = i0; y0 < i1; y0 += kMaxGridY) {
+      const dim3 blocks(Blocks(max_rays, 4, 1024), ChunkOf(y0, i1));
+      hipLaunchKernelGGL(tsdf2d_claim, blocks, dim3(256), 0, st, dd + y0, dr, od);
       CSM_HIP(hipGetLastError());
-      hipLaunchKernelGGL(tsdf2d_apply, blocks, dim3(256), 0, st, dd + i0 + y0, dr, od);
+      hipLaunchKernelGGL(tsdf2d_apply, blocks, dim3(256), 0, st, dd + y0, dr, od);
       CSM_HIP(hipGetLastError());
     }
-    i0 = i1;
   }
   // The old buffers of grown grids: reused by later takes on this stream.
-  for (DevBuf& b : retired)
-    if (b.ptr) ctx->pool.Give(&b);
+  for (DevBuf& b : retired) ctx->pool.Give(&b);
   return CSM_OK;
-}
-
-void GiveGrid(csm_tsdf_grid* g) {
-  for (DevBuf* b : {&g->tsd, &g->weight, &g->rank})
-    if (b->ptr) g->ctx->pool.Give(b);
 }
 
 }  // namespace
@@ -797,9 +697,8 @@ int csm_tsdf_plan_scan(const csm_tsdf_inserter_options* o, const float* origin,
                        float* ray_weight_out, uint8_t* cast_out) {
   if (!ValidOptions(o) || !origin || n < 0 || (n > 0 && !returns) || n > (1 << 24))
     return CSM_EINVAL;
-  if (!Finite3(origin)) return CSM_EINVAL;
-  for (int32_t i = 0; i < n; ++i)
-    if (!Finite3(returns + 3 * i)) return CSM_EINVAL;
+  const int64_t ro[2] = {0, n};
+  if (!ValidScans(1, origin, ro, returns)) return CSM_EINVAL;
   ScanPlanHost plan;
   PlanScan(*o, origin, returns, n, &plan);
   for (int32_t k = 0; k < n; ++k) {
@@ -819,14 +718,10 @@ int csm_tsdf_grid_create(csm_context* ctx, const csm_map_limits* limits, float t
   if (!(truncation_distance > 0.f) || !(max_weight > 0.f) || !std::isfinite(truncation_distance) ||
       !std::isfinite(max_weight))
     return CSM_EINVAL;
-  if (limits->num_x_cells < 1 || limits->num_y_cells < 1 || !(limits->resolution > 0.) ||
-      !std::isfinite(limits->resolution) || !std::isfinite(limits->max_x) ||
-      !std::isfinite(limits->max_y))
-    return CSM_EINVAL;
-  if (limits->num_x_cells > kMaxSide || limits->num_y_cells > kMaxSide) return CSM_ERANGE;
+  int rc;
+  if ((rc = CheckLimits2(limits))) return rc;
   std::lock_guard<std::mutex> lock(ctx->mu);
   if (EnsureDevice(ctx)) return CSM_EHIP;
-  int rc;
   TsdfTables* tabs;
   if ((rc = EnsureTables(ctx, truncation_distance, max_weight, &tabs))) return rc;
   auto g = std::make_unique<csm_tsdf_grid>();
@@ -835,31 +730,8 @@ int csm_tsdf_grid_create(csm_context* ctx, const csm_map_limits* limits, float t
   g->truncation = truncation_distance;
   g->max_weight = max_weight;
   g->id = g_next_grid_id.fetch_add(1);
-  const size_t n = static_cast<size_t>(limits->num_x_cells) * limits->num_y_cells;
-  if ((rc = ctx->pool.Take(n * sizeof(uint16_t), &g->tsd)) ||
-      (rc = ctx->pool.Take(n * sizeof(uint16_t), &g->weight)) ||
-      (rc = ctx->pool.Take(n * sizeof(uint32_t), &g->rank))) {
-    GiveGrid(g.get());
-    return rc;
-  }
-  hipStream_t st = ctx->stream;
-  bool ok = hipMemsetAsync(g->rank.ptr, 0xff, n * sizeof(uint32_t), st) == hipSuccess;
-  if (tsd_cells) {
-    // The caller's memory is read: finish before returning.
-    ok = ok &&
-         hipMemcpyAsync(g->tsd.ptr, tsd_cells, n * sizeof(uint16_t), hipMemcpyHostToDevice, st) ==
-             hipSuccess &&
-         hipMemcpyAsync(g->weight.ptr, weight_cells, n * sizeof(uint16_t), hipMemcpyHostToDevice,
-                        st) == hipSuccess &&
-         hipStreamSynchronize(st) == hipSuccess;
-  } else {
-    ok = ok && hipMemsetAsync(g->tsd.ptr, 0, n * sizeof(uint16_t), st) == hipSuccess &&
-         hipMemsetAsync(g->weight.ptr, 0, n * sizeof(uint16_t), st) == hipSuccess;
-  }
-  if (!ok) {
-    GiveGrid(g.get());
-    return CSM_EHIP;
-  }
+  const uint16_t* const host[] = {tsd_cells, weight_cells, nullptr};
+  if ((rc = NewPlanes2(g.get(), kPlanes, host))) return rc;
   *out = g.release();
   return CSM_OK;
 }
@@ -867,7 +739,7 @@ int csm_tsdf_grid_create(csm_context* ctx, const csm_map_limits* limits, float t
 void csm_tsdf_grid_destroy(csm_tsdf_grid* g) {
   if (!g) return;
   (void)hipSetDevice(g->ctx->device);
-  GiveGrid(g);
+  GivePlanes2(g, kPlanes);
   delete g;
 }
 
@@ -897,12 +769,10 @@ int csm_tsdf_grid_insert(csm_tsdf_grid* g, const csm_tsdf_inserter_options* o, c
                          const float* returns, int32_t num_returns) {
   if (!g || !o || !origin || num_returns < 0 || (num_returns > 0 && !returns)) return CSM_EINVAL;
   if (!ValidOptions(o)) return CSM_EINVAL;
-  // The points are checked before the handle is read.
-  if (!Finite3(origin)) return CSM_EINVAL;
-  for (int32_t i = 0; i < num_returns; ++i)
-    if (!Finite3(returns + 3 * i)) return CSM_EINVAL;
   const int32_t zero = 0;
   const int64_t ro[2] = {0, num_returns};
+  // The points are checked before the handle is read.
+  if (!ValidScans(1, origin, ro, returns)) return CSM_EINVAL;
   csm_tsdf_grid* const grids[1] = {g};
   return InsertBatch(g->ctx, grids, 1, o, 1, &zero, origin, returns, ro);
 }
@@ -923,26 +793,12 @@ int csm_tsdf_grid_finish(csm_tsdf_grid* g) {
   hipStream_t st = ctx->stream;
   int rc;
   TsdfTables* tabs;
-  if ((rc = EnsureTables(ctx, g->truncation, g->max_weight, &tabs)) ||
-      (rc = ctx->ins_box.Reserve(4 * sizeof(int))) ||
-      (rc = ctx->ins_box_host.Reserve(4 * sizeof(int))))
-    return rc;
-  int* hb = ctx->ins_box_host.as<int>();
-  hb[0] = hb[1] = INT_MAX;
-  hb[2] = hb[3] = -1;
+  Crop2 c;
   const int nx = g->limits.num_x_cells, ny = g->limits.num_y_cells;
-  CSM_HIP(hipMemcpyAsync(ctx->ins_box.ptr, hb, 4 * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(insert2d_box, dim3(Blocks(int64_t{nx} * ny, 1024, 1024)), dim3(256), 0, st,
-                     g->tsd.as<uint16_t>(), nx, ny, ctx->ins_box.as<int>());
-  CSM_HIP(hipGetLastError());
-  CSM_HIP(hipMemcpyAsync(hb, ctx->ins_box.ptr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  CSM_HIP(hipStreamSynchronize(st));
-  // Grid2D::ComputeCroppedLimits (grid_2d.cc:121-132) and the new max
-  // (tsdf_2d.cc:122-124).
-  const bool empty = hb[2] < 0;
-  const int ox = empty ? 0 : hb[0], oy = empty ? 0 : hb[1];
-  const int cnx = empty ? 1 : hb[2] - hb[0] + 1, cny = empty ? 1 : hb[3] - hb[1] + 1;
-  const size_t cn = static_cast<size_t>(cnx) * cny;
+  if ((rc = EnsureTables(ctx, g->truncation, g->max_weight, &tabs)) ||
+      (rc = CropBox2(ctx, g->tsd.as<uint16_t>(), nx, ny, &c)))
+    return rc;
+  const size_t cn = static_cast<size_t>(c.nx) * c.ny;
   DevBuf tsd, weight;
   if ((rc = ctx->pool.Take(cn * sizeof(uint16_t), &tsd)) ||
       (rc = ctx->pool.Take(cn * sizeof(uint16_t), &weight))) {
@@ -951,19 +807,14 @@ int csm_tsdf_grid_finish(csm_tsdf_grid* g) {
   }
   // An all-unknown grid's single cell is (0, 0) in the source as well.
   hipLaunchKernelGGL(tsdf2d_crop, dim3(Blocks(static_cast<int64_t>(cn), 256, 4096)), dim3(256), 0,
-                     st, g->tsd.as<uint16_t>(), g->weight.as<uint16_t>(), nx, ox, oy,
-                     tsd.as<uint16_t>(), weight.as<uint16_t>(), cnx, cny,
+                     st, g->tsd.as<uint16_t>(), g->weight.as<uint16_t>(), nx, c.ox, c.oy,
+                     tsd.as<uint16_t>(), weight.as<uint16_t>(), c.nx, c.ny,
                      tabs->round_trip.as<uint16_t>());
   CSM_HIP(hipGetLastError());
-  GiveGrid(g);  // reused by later takes on this stream
-  MoveBuf(&tsd, &g->tsd);
-  MoveBuf(&weight, &g->weight);
-  g->limits.max_x = g->limits.max_x - g->limits.resolution * static_cast<double>(oy);
-  g->limits.max_y = g->limits.max_y - g->limits.resolution * static_cast<double>(ox);
-  g->limits.num_x_cells = cnx;
-  g->limits.num_y_cells = cny;
-  g->finished = true;
-  ++g->generation;
+  GivePlanes2(g, kPlanes);  // reused by later takes on this stream
+  g->tsd = std::move(tsd);
+  g->weight = std::move(weight);
+  FinishCrop2(g, c);
   return CSM_OK;
 }
 

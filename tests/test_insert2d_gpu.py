@@ -245,6 +245,34 @@ def test_insert_errors(csm):
     assert np.array_equal(after.cells, before.cells)
 
 
+def test_batch_erange_in_the_second_grid_leaves_both_grids(csm):
+    """A batch over two grids of 8 x 8 cells: grid 0's scan is valid and would
+    double it, grid 1's needs more than 8192 cells a side. CSM_ERANGE, and both
+    grids keep their limits and cells: everything that can refuse a call comes
+    before the first enqueue for any of its grids. (The handles' generation
+    counters have no accessor; the limits stand in for them.)"""
+    limits = (0.05, 0.2, 0.2, 8, 8)
+    grids = [csm.DeviceProbabilityGrid(*limits) for _ in range(2)]
+    origin = np.zeros(3, np.float32)
+    near = np.array([[0.1, 0.0, 0], [0.0, 0.12, 0], [-0.1, -0.1, 0]], np.float32)
+    for g in grids:
+        g.insert(origin, near, hit_probability=HIT, miss_probability=MISS)
+    before = [g.to_host() for g in grids]
+    assert all((b.cells != 0).any() for b in before)
+    grows = np.array([[0.3, 0.0, 0], [0.0, 0.3, 0], [-0.3, -0.3, 0]], np.float32)
+    far = np.array([[0.1, 0.0, 0], [1000.0, 0.0, 0], [0.0, 0.1, 0]], np.float32)
+    with pytest.raises(csm.CsmError, match=r"\(-4\)"):
+        csm.DeviceProbabilityGrid.insert_batch(grids, [0, 1], [(origin, grows), (origin, far)],
+                                               HIT, MISS, True)
+    for g, b in zip(grids, before):
+        after = g.to_host()
+        assert sup.limits_tuple(after.limits()) == sup.limits_tuple(b.limits())
+        assert np.array_equal(after.cells, b.cells)
+    # The valid scan alone does grow its grid.
+    grids[0].insert(origin, grows, hit_probability=HIT, miss_probability=MISS)
+    assert grids[0].limits().num_x_cells == 16
+
+
 def test_finish(csm, oracle, inserted):
     """Finish crops to the oracle's ComputeCroppedGrid; a never-inserted grid
     finishes to 1 x 1; an insert after Finish is CSM_EINVAL."""

@@ -258,6 +258,28 @@ def test_errors_leave_the_grid_untouched(csm, oracle):
     sup.assert_same_grid(dev, ora)
 
 
+def test_batch_erange_in_the_second_grid_leaves_both_grids(csm):
+    """A batch over two grids of a few cells: grid 0's job is valid and would
+    grow its brick, grid 1's has a coordinate past 1e9 cells. CSM_ERANGE, and
+    both grids keep their bricks: everything that can refuse a call comes
+    before the first enqueue for any of its grids. (The handles' generation
+    counters have no accessor; the brick and DynamicGrid size stand in.)"""
+    grids = [empty_grid(csm, RES) for _ in range(2)]
+    origin = np.zeros(3, np.float32)
+    near = np.array([[0.3, 0.0, 0.0], [0.0, 0.3, 0.1], [-0.2, -0.2, 0.0]], np.float32)
+    for g in grids:
+        g.insert(origin, near)
+    before = [(g.info(), g.values().tobytes()) for g in grids]
+    grows = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.5], [-1.0, -1.0, 0.0]], np.float32)
+    far = np.array([[0.3, 0.0, 0.0], [2.0e8, 0.0, 0.0], [0.0, 0.3, 0.0]], np.float32)
+    with pytest.raises(csm.CsmError, match=r"\(-4\)"):
+        csm.HybridGrid.insert_batch(grids, [(origin, grows), (origin, far)], [(0, 0), (1, 1)])
+    assert [(g.info(), g.values().tobytes()) for g in grids] == before
+    # The valid job alone does grow its grid.
+    grids[0].insert(origin, grows)
+    assert grids[0].info()[1] != before[0][0][1]
+
+
 # ---- 7. touched-cell scaling --------------------------------------------------
 def test_apply_pass_visits_touched_cells_only(csm, oracle):
     """64 short rays into a brick of 200^3 cells: the FinishUpdate pass looks at

@@ -226,6 +226,38 @@ def test_growth_past_8192_is_erange_and_leaves_the_grid(csm, oracle):
     dev.close()
 
 
+def test_batch_erange_in_the_second_grid_leaves_both_grids(csm):
+    """A batch over two small grids: grid 0's scan is valid and would grow it,
+    grid 1's needs more than 8192 cells a side. CSM_ERANGE, and both grids keep
+    their limits and planes: everything that can refuse a call comes before the
+    first enqueue for any of its grids. (The handles' generation counters have
+    no accessor; the limits stand in for them.)"""
+    options = sup.OPTION_SETS["A"]
+    grids = [sup.new_device_grid(csm, (0.05, 0.2, 0.2, 8, 8)) for _ in range(2)]
+    origin = np.zeros(3, np.float32)
+    # Past the truncation distance (0.3 m): nearer returns cast no ray.
+    near = np.array([[0.5, 0.0, 0], [0.0, 0.45, 0], [-0.4, -0.4, 0]], np.float32)
+    for g in grids:
+        g.insert(origin, near, options)
+    before = [g.to_host() for g in grids]
+    side = before[0].num_x_cells
+    assert side <= 64 and all((b.weight_cells != 0).any() for b in before)
+    grows = np.array([[2.0, 0.0, 0], [0.0, 2.0, 0], [-2.0, -2.0, 0]], np.float32)
+    far = np.array([[0.1, 0.0, 0], [300.0, 0.0, 0], [0.0, 0.1, 0]], np.float32)
+    with pytest.raises(csm.CsmError, match=r"\(-4\)"):
+        csm.DeviceTSDF2D.insert_batch(grids, [0, 1], [(origin, grows), (origin, far)], options)
+    for g, b in zip(grids, before):
+        after = g.to_host()
+        assert (after.resolution, after.max_x, after.max_y) == (b.resolution, b.max_x, b.max_y)
+        assert np.array_equal(after.tsd_cells, b.tsd_cells)
+        assert np.array_equal(after.weight_cells, b.weight_cells)
+    # The valid scan alone does grow its grid.
+    grids[0].insert(origin, grows, options)
+    assert grids[0].limits().num_x_cells > side
+    for g in grids:
+        g.close()
+
+
 def test_match_on_device_planes(csm, oracle):
     """csm_rt2d_match_tsdf_grid after each of room's inserts: the score and
     pose of csm_rt2d_match_tsdf on the read-back planes, and the oracle's
