@@ -120,17 +120,56 @@ struct WorkQueues {
   int32_t rot_chunk;              // rotations per chunk
 };
 
-// v2 work queues: chunks of `rot_chunk` rotations of a pair; a chunk id
-// decodes to its pair in O(1) through a per-64-chunk block table.
+// v4/v5 work queues: interleaved (csm_schedule.h BuildSchedule, DESIGN.md §5
+// "Rotation chunks"). A queue is a run of slots, claimed front to back with
+// one atomicAdd each. Its pairs are grouped into blocks of pairs of one
+// submap, longest first, and a block is cut into rectangles: rectangle
+// (first, width, pos0) holds positions pos0, pos0 + 1, ... of entries
+// [first, first + width), position-major, so two consecutive positions of a
+// pair are `width` claims apart. A slot whose position is past its pair's
+// chunk count is empty (the host bounds their share). Position j of a pair
+// is its chunk j * stride mod chunks, stride coprime to chunks.
+struct SchedEntry {
+  int32_t pair;
+  int32_t chunks;  // rotation chunks of the pair, >= 1
+  int32_t stride;  // in [1, chunks), coprime to chunks (1 if chunks == 1)
+  int32_t pad;
+};
+struct SchedRect {
+  int64_t slot_begin, slot_end;  // within its queue; fewer than 2^31 slots
+  int32_t first;                 // into the entries
+  int32_t width;                 // pairs, >= 1
+  int32_t pos0;                  // position of the rectangle's first row
+  int32_t pad;
+};
 struct WorkQueues2 {
-  const int32_t* pair_order;    // pairs, grouped by queue
-  const int64_t* chunk_prefix;  // size |pair_order|+1, cumulative chunks
-  const int32_t* block_first;   // per queue block of 64 chunks: pair_order index
-  int32_t block_offset[kNumXcd];
-  int32_t queue_begin[kNumXcd + 1];
-  int64_t queue_chunks[kNumXcd];
+  const SchedEntry* entries;
+  const SchedRect* rects;  // queue after queue, each in slot order
+  const int32_t* hint;     // per queue and 2^hint_shift slots: the rectangle of the first one
+  int32_t hint_offset[kNumXcd];
+  int64_t queue_slots[kNumXcd];
+  int32_t hint_shift;
   int32_t rot_chunk;
 };
+
+// Slot `slot` (< queue_slots[q]) of queue q -> (pair, chunk); false: an empty
+// slot. Three dependent loads when the hint is exact (hint, rectangle,
+// entry); the kernel's claim and the host's checks both call this.
+CSM_HD inline bool DecodeSlot(const WorkQueues2& w, int q, int64_t slot, int* pair, int* chunk) {
+  int r = w.hint[w.hint_offset[q] + static_cast<int>(slot >> w.hint_shift)];
+  SchedRect rect = w.rects[r];
+  while (slot >= rect.slot_end) rect = w.rects[++r];
+  const uint32_t rel = static_cast<uint32_t>(slot - rect.slot_begin);
+  const uint32_t width = static_cast<uint32_t>(rect.width);
+  const uint32_t row = rel / width;
+  const SchedEntry e = w.entries[rect.first + static_cast<int>(rel - row * width)];
+  const uint32_t pos = static_cast<uint32_t>(rect.pos0) + row;
+  if (pos >= static_cast<uint32_t>(e.chunks)) return false;
+  *pair = e.pair;
+  // pos, stride < chunks <= kMaxRotations: the product fits 32 bits.
+  *chunk = static_cast<int>(pos * static_cast<uint32_t>(e.stride) % static_cast<uint32_t>(e.chunks));
+  return true;
+}
 
 // Rotations per v4/v5 search item at most (per-rotation LDS tables are sized
 // for it; the host clamps CSM_ROT_CHUNK to it).

@@ -30,6 +30,7 @@
 #include "csm_device.h"
 #include "csm_internal.h"
 #include "csm_launch.h"
+#include "csm_schedule.h"
 #include "parallel_sort.h"
 #include "search_window.h"
 
@@ -221,70 +222,53 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
                  std::vector<uint2>* ties = nullptr, std::vector<int32_t>* tie_counts = nullptr) {
   const int np = static_cast<int>(pdesc.size());
   const int rc = plan.rc;
-  // Per-XCD queues: submap s -> queue s % 8 so a submap's pyramid stays in
-  // one XCD's L2; pairs within a queue in submap order. A batch of fewer
-  // than 8 submaps (the C3 chunks hold 4) spreads each submap's pairs over
-  // 8 / S queues, so every XCD starts on a submap of its own instead of the
-  // empty queues' workgroups all stealing from the first one: C3 chunk
-  // launch 591 -> 570 ms (profiles/r4o/; CSM_QUEUE_SPREAD=0 for the A/B).
+  // Per-XCD queues (csm_schedule.h AssignQueues; CSM_QUEUE_SPREAD=0 for the
+  // A/B of the spreading).
   static const bool spread_on = [] {
     const char* e = std::getenv("CSM_QUEUE_SPREAD");
     return !(e && std::atoi(e) == 0);
   }();
-  int nsub = 0;
-  for (int i = 0; i < np; ++i) nsub = std::max(nsub, pdesc[i].submap + 1);
-  const int reps = spread_on && nsub > 0 && nsub < kNumXcd ? kNumXcd / nsub : 1;
-  std::vector<int32_t> seen(reps > 1 ? nsub : 0, 0);
-  std::vector<std::vector<int32_t>> q(kNumXcd);
+  std::vector<int32_t> pair_submap(np), pair_chunks(np);
   for (int i = 0; i < np; ++i) {
-    const int sm = pdesc[i].submap;
-    const int qi = reps > 1 ? sm + nsub * (seen[sm]++ % reps) : sm % kNumXcd;
-    q[qi].push_back(i);
+    pair_submap[i] = pdesc[i].submap;
+    pair_chunks[i] = (pdesc[i].num_scans + rc - 1) / rc;
   }
+  const std::vector<std::vector<int32_t>> q = AssignQueues(pair_submap, spread_on);
+  // v1 kernel: pair-major, a pair's chunks in rotation order.
   std::vector<int32_t> order;
   std::vector<int64_t> prefix;
   WorkQueues wq{};
   wq.rot_chunk = rc;
-  int64_t running = 0;
-  for (int x = 0; x < kNumXcd; ++x) {
-    std::stable_sort(q[x].begin(), q[x].end(),
-                     [&](int a, int b) { return pdesc[a].submap < pdesc[b].submap; });
-    wq.queue_begin[x] = static_cast<int32_t>(order.size());
-    const int64_t qstart = running;
-    for (int pi : q[x]) {
-      order.push_back(pi);
-      prefix.push_back(running);
-      running += (pdesc[pi].num_scans + rc - 1) / rc;
-    }
-    wq.queue_chunks[x] = running - qstart;
-  }
-  wq.queue_begin[kNumXcd] = static_cast<int32_t>(order.size());
-  prefix.push_back(running);
-
-  // Block table (v2 kernel): for every 64 chunks of a queue, the first
-  // pair_order entry.
-  std::vector<int32_t> blocks;
-  WorkQueues2 wq2{};
+  // v4/v5 kernel: a block of pairs at a time, position-major (csm_schedule.h).
+  Schedule sched;
+  int64_t total_chunks = 0;
+  double sched_ms = 0.0;
   if (plan.use_v2) {
-    wq2.rot_chunk = rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    sched = BuildSchedule(q, pair_submap, pair_chunks, rc);
+    sched_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    total_chunks = sched.items;
+  } else {
+    int64_t running = 0;
     for (int x = 0; x < kNumXcd; ++x) {
-      wq2.queue_begin[x] = wq.queue_begin[x];
-      wq2.queue_chunks[x] = wq.queue_chunks[x];
-      wq2.block_offset[x] = static_cast<int32_t>(blocks.size());
-      const int64_t qstart = prefix[wq.queue_begin[x]];
-      int e = wq.queue_begin[x];
-      for (int64_t c = 0; c < wq.queue_chunks[x]; c += 64) {
-        while (prefix[e + 1] - qstart <= c) ++e;
-        blocks.push_back(e);
+      wq.queue_begin[x] = static_cast<int32_t>(order.size());
+      const int64_t qstart = running;
+      for (int pi : q[x]) {
+        order.push_back(pi);
+        prefix.push_back(running);
+        running += (pdesc[pi].num_scans + rc - 1) / rc;
       }
+      wq.queue_chunks[x] = running - qstart;
     }
-    wq2.queue_begin[kNumXcd] = wq.queue_begin[kNumXcd];
+    wq.queue_begin[kNumXcd] = static_cast<int32_t>(order.size());
+    prefix.push_back(running);
+    total_chunks = running;
   }
 
   // One device arena per launch (csm_context::arena): the inputs, uploaded
   // with one copy from pinned staging, then the outputs, zeroed with one
   // memset and read back with one copy into pinned memory:
-  //   pair_desc | pair_order | chunk_prefix | blocks || best | best_hi |
+  //   pair_desc | queue tables (three regions) || best | best_hi |
   //   status | tie_count | counters | stats
   // (init_best, when given, is uploaded into `best` with the inputs.)
   auto align = [](size_t v) { return (v + 255) & ~size_t{255}; };
@@ -294,9 +278,13 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
     at = align(at + std::max<size_t>(bytes, 1));
     return o;
   };
-  const size_t o_pd = region(sizeof(PairDesc) * np), o_order = region(sizeof(int32_t) * order.size()),
-               o_prefix = region(sizeof(int64_t) * prefix.size()),
-               o_blocks = region(sizeof(int32_t) * blocks.size());
+  // v1: pair_order | chunk_prefix; v4/v5: entries | rectangles | hints.
+  const size_t o_pd = region(sizeof(PairDesc) * np);
+  const size_t o_order = region(plan.use_v2 ? sizeof(SchedEntry) * sched.entries.size()
+                                            : sizeof(int32_t) * order.size()),
+               o_prefix = region(plan.use_v2 ? sizeof(SchedRect) * sched.rects.size()
+                                             : sizeof(int64_t) * prefix.size()),
+               o_blocks = region(sizeof(int32_t) * sched.hint.size());
   const size_t o_best = region(sizeof(uint64_t) * np), o_hi = region(sizeof(uint64_t) * np),
                o_status = region(sizeof(int32_t) * np), o_tcount = region(sizeof(int32_t) * np),
                o_counters = region(sizeof(unsigned long long) * kNumXcd);
@@ -312,9 +300,14 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
     return rcode;
   char* hin = ctx->arena_in.as<char>();
   std::memcpy(hin + o_pd, pdesc.data(), sizeof(PairDesc) * np);
-  std::memcpy(hin + o_order, order.data(), sizeof(int32_t) * order.size());
-  std::memcpy(hin + o_prefix, prefix.data(), sizeof(int64_t) * prefix.size());
-  if (!blocks.empty()) std::memcpy(hin + o_blocks, blocks.data(), sizeof(int32_t) * blocks.size());
+  if (plan.use_v2) {
+    std::memcpy(hin + o_order, sched.entries.data(), sizeof(SchedEntry) * sched.entries.size());
+    std::memcpy(hin + o_prefix, sched.rects.data(), sizeof(SchedRect) * sched.rects.size());
+    std::memcpy(hin + o_blocks, sched.hint.data(), sizeof(int32_t) * sched.hint.size());
+  } else {
+    std::memcpy(hin + o_order, order.data(), sizeof(int32_t) * order.size());
+    std::memcpy(hin + o_prefix, prefix.data(), sizeof(int64_t) * prefix.size());
+  }
   if (init_best) std::memcpy(hin + o_best, init_best->data(), sizeof(uint64_t) * np);
   char* dev = ctx->arena.as<char>();
   hipStream_t st = ctx->stream;
@@ -332,13 +325,13 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
   wq.chunk_prefix = reinterpret_cast<int64_t*>(dev + o_prefix);
 
   // ---- launch: persistent workgroups ----------------------------------------
-  const int64_t total_chunks = running;
   const int max_npad = plan.max_npad;
   if (timed) CSM_HIP(hipEventRecord(ctx->ev0, st));
   if (plan.use_v2) {
-    wq2.pair_order = wq.pair_order;
-    wq2.chunk_prefix = wq.chunk_prefix;
-    wq2.block_first = reinterpret_cast<int32_t*>(dev + o_blocks);
+    WorkQueues2 wq2 = sched.wq;
+    wq2.entries = reinterpret_cast<SchedEntry*>(dev + o_order);
+    wq2.rects = reinterpret_cast<SchedRect*>(dev + o_prefix);
+    wq2.hint = reinterpret_cast<int32_t*>(dev + o_blocks);
     // Per rotation: npad raw cells and capc cluster-list entries. capc =
     // 3/4 npad holds the three cluster lists of a typical scan (0.55 npad on
     // C2); a list that does not fit falls back to a finer one in the kernel.
@@ -355,8 +348,12 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
     int per_cu = std::max(1, std::min(8, Fast2dSearchV2BlocksPerCu(plan.hex, plan.fifo, dyn_lds)));
     if (const char* w = std::getenv("CSM_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(w)));
     if (std::getenv("CSM_PROFILE2D") && !init_best)
-      std::fprintf(stderr, "fast2d launch: %s %s, %d rotations per item, %zu B dynamic LDS (capc %d), %d workgroups per CU\n",
-                   plan.hex ? "v5" : "v4", plan.fifo ? "fifo" : "lifo", rc, dyn_lds, capc, per_cu);
+      std::fprintf(stderr, "fast2d launch: %s %s, %d rotations per item, %zu B dynamic LDS (capc %d), %d workgroups per CU; "
+                   "%lld items, %lld empty slots (%.3f %%), %zu rectangles, %zu hints, built in %.3f ms\n",
+                   plan.hex ? "v5" : "v4", plan.fifo ? "fifo" : "lifo", rc, dyn_lds, capc, per_cu,
+                   static_cast<long long>(sched.items), static_cast<long long>(sched.empty_slots),
+                   100.0 * sched.empty_slots / std::max<int64_t>(sched.items, 1), sched.rects.size(),
+                   sched.hint.size(), sched_ms);
     // Concurrent single calls (call contexts, csm_internal.h) each take a
     // share of the chip, so their persistent grids tile it instead of
     // queueing behind one another (at least one workgroup per CU each).

@@ -1122,12 +1122,9 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
       int q = sh.queue, pair = -1, chunk = 0;
       while (tries < kNumXcd) {
         const int64_t item = static_cast<int64_t>(atomicAdd(&counters[q], 1ull));
-        if (item < queues.queue_chunks[q]) {
-          const int64_t gch = queues.chunk_prefix[queues.queue_begin[q]] + item;
-          int e = queues.block_first[queues.block_offset[q] + static_cast<int>(item >> 6)];
-          while (queues.chunk_prefix[e + 1] <= gch) ++e;
-          pair = queues.pair_order[e];
-          chunk = static_cast<int>(gch - queues.chunk_prefix[e]);
+        if (item < queues.queue_slots[q]) {
+          // An empty slot (a position past its pair's chunks): claim again.
+          if (!DecodeSlot(queues, q, item, &pair, &chunk)) continue;
           break;
         }
         q = (q + 1) % kNumXcd;

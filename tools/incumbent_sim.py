@@ -8,6 +8,21 @@ rotation chunk starts from) and at bound < S, S = the pair's final best sum
 (a perfect incumbent from the start). Matched and unmatched pairs apart.
 
     python tools/incumbent_sim.py [--pairs 24] [--rots 16]
+
+--replay prices the order of a pair's rotation chunks instead (matched pairs
+only; an unmatched pair never has an incumbent above s_min). A chunk is
+--rot-chunk rotations; it starts from the best leaf of the chunks whose
+position in the order is at least L earlier (its own leaves and the refresh
+during an item are left out, as above). Three schedules: the pair-major one
+(chunks in rotation order, L = the 192 workgroups of a queue, all on one
+pair), the interleaved one in rotation order (L = 1: a pair's next position
+is claimed a block of pairs later) and the interleaved one in the
+golden-section order of csm_schedule.h. The gathers are summed over --rots
+evenly spaced rotations plus every rotation within --dense of the best one
+(so the peak's width is resolved), each weighted by the rotations it stands
+for; the best leaf of the rotations in between is interpolated.
+
+    python tools/incumbent_sim.py --replay [--pairs 16] [--rots 24] [--dense 12]
 """
 import argparse
 import math
@@ -21,6 +36,25 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def golden_stride(chunks):
+    """csm_schedule.h GoldenStrideSearch."""
+    if chunks <= 2:
+        return 1
+    s0 = int(chunks * 0.6180339887498949 + 0.5)
+    best, best_q = 1, chunks + 1
+    for d in range(9):
+        for s in (s0 + d, s0 - d):
+            if s < 1 or s >= chunks:
+                continue
+            a, b, q = chunks, s, 0
+            while b > 0:
+                q = max(q, a // b)
+                a, b = b, a % b
+            if a == 1 and q < best_q:
+                best, best_q = s, q
+    return best
+
+
 def main():
     from scipy.ndimage import maximum_filter
     ap = argparse.ArgumentParser()
@@ -31,6 +65,11 @@ def main():
     ap.add_argument("--min-score", type=float, default=0.55)
     ap.add_argument("--dive", type=int, default=0,
                     help="greedy dive incumbent from every n-th rotation (0: off)")
+    ap.add_argument("--replay", action="store_true",
+                    help="price the chunk orders (module docstring)")
+    ap.add_argument("--dense", type=int, default=12,
+                    help="--replay: every rotation within this many of the best one")
+    ap.add_argument("--rot-chunk", type=int, default=2)
     args = ap.parse_args()
     ks = [int(v) for v in args.k.split(",")]
     import __graft_entry__ as ge
@@ -45,6 +84,7 @@ def main():
     pairs = [(s, int(world.submap_nodes[s])) for s in rng.choice(50, half, replace=False)]
     pairs += list(zip(rng.randint(0, 50, args.pairs - half), rng.randint(0, 500, args.pairs - half)))
     tot = {"matched": [0, 0, 0, 0], "unmatched": [0, 0, 0, 0]}  # gathers at s_min, at S, pairs, at dive
+    replay_tot = {}
     for pi, (s, nd) in enumerate(pairs):
         g = world.grid(int(s))
         cells = g.cells
@@ -52,7 +92,7 @@ def main():
         om = o.fast2d(limits, cells, 7.0, math.radians(30.0), D)
         cloud = world.cloud(int(nd))
         n = len(cloud)
-        ok, score, _, _ = om.match_full_submap(cloud, args.min_score)
+        ok, score, pose, _ = om.match_full_submap(cloud, args.min_score)
         G0 = om.level(0).astype(np.int64)
         PAD = 600
         Gp = np.zeros((G0.shape[0] + 2 * PAD, G0.shape[1] + 2 * PAD), np.int64)
@@ -99,6 +139,74 @@ def main():
                 cnt = np.diff(np.append(idx, n))
                 ent.append((qx[idx], qy[idx], cnt.astype(np.int64), (1 << c) + k - 1))
             return ent
+
+        def search(r, thr):
+            """Gathers of rotation r's search with nodes kept at bound > thr,
+            and its best leaf sum above thr (0: none)."""
+            ent = entries(r)
+            bx0, bx1, by0, by1 = bounds[r]
+            st = 1 << (D - 1)
+            fx, fy = [a.ravel() for a in np.meshgrid(np.arange(bx0, bx1 + 1, st),
+                                                     np.arange(by0, by1 + 1, st), indexing="ij")]
+            gathers = ((len(fx) + 3) // 4) * len(ent[D - 1][0])
+            d = D - 1
+            while len(fx):
+                sc = score_e(ent[d], fx, fy)
+                keep = sc > thr
+                fx, fy, sc = fx[keep], fy[keep], sc[keep]
+                if d == 0:
+                    return gathers, int(sc.max()) if len(sc) else 0
+                hh = 1 << (d - 1)
+                cx_ = np.concatenate([fx + a * hh for a in range(2) for b in range(2)])
+                cy_ = np.concatenate([fy + b * hh for a in range(2) for b in range(2)])
+                gathers += len(fx) * len(ent[d - 1][0])
+                okc = (cx_ <= bx1) & (cy_ <= by1)
+                fx, fy = cx_[okc], cy_[okc]
+                d -= 1
+            return gathers, 0
+
+        if args.replay:
+            if not ok:
+                continue
+            r_best = int(np.argmin([abs((k - (ns - 1) // 2) * step - pose[2]) for k in range(ns)]))
+            rs = sorted(set(np.linspace(0, ns - 1, args.rots).astype(int).tolist())
+                        | set(range(max(0, r_best - args.dense), min(ns, r_best + args.dense + 1))))
+            base = {r: search(r, s_min) for r in rs}  # (gathers, best leaf) at s_min
+            rs_a = np.array(rs)
+            leaf_rot = np.interp(np.arange(ns), rs_a, [max(base[r][1], s_min) for r in rs])
+            rc = args.rot_chunk
+            nch = (ns + rc - 1) // rc
+            leaf_chunk = np.array([leaf_rot[c * rc:(c + 1) * rc].max() for c in range(nch)])
+            # Each sampled rotation stands for the rotations nearer to it than to another.
+            edges = np.concatenate([[0], (rs_a[1:] + rs_a[:-1] + 1) // 2, [ns]])
+            weight = np.diff(edges)
+            stride = golden_stride(nch)
+            orders = {"pair-major, L=192": (np.arange(nch), 192),
+                      "interleaved, rotation order, L=1": (np.arange(nch), 1),
+                      "interleaved, golden order, L=1": (np.arange(nch) * stride % nch, 1)}
+            g0 = sum(base[r][0] * w for r, w in zip(rs, weight))
+            line = [f"pair {pi} ({s},{nd}) rotations {ns} best {r_best} S {S} s_min {s_min}"]
+            for name, (order, lag) in orders.items():
+                pos = np.empty(nch, np.int64)
+                pos[order] = np.arange(nch)
+                seen = np.maximum.accumulate(leaf_chunk[order])  # best leaf of positions <= j
+                total = 0
+                for r, w in zip(rs, weight):
+                    j = pos[r // rc] - lag
+                    thr = max(s_min, int(seen[j]) - 1) if j >= 0 else s_min
+                    total += (base[r][0] if thr == s_min else search(r, thr)[0]) * w
+                acc = replay_tot.setdefault(name, [0.0, 0.0])
+                acc[0] += total
+                acc[1] += g0
+                line.append(f"{name}: {total / g0:.3f}")
+            # The ceiling: the final best from the start.
+            total = sum(search(r, S - 1)[0] * w for r, w in zip(rs, weight))
+            acc = replay_tot.setdefault("final best from the start", [0.0, 0.0])
+            acc[0] += total
+            acc[1] += g0
+            line.append(f"ceiling: {total / g0:.3f}")
+            print("; ".join(line), flush=True)
+            continue
 
         # Greedy dive per rotation: from the best top-level node, the best
         # child at every level down to a leaf (exact leaf sum).
@@ -167,6 +275,11 @@ def main():
         tot[kind][2] += 1
         print(f"pair {pi} ({s},{nd}) {kind} score {score:.3f} rotations {ns} S {S} dive {S_dive} "
               f"s_min {s_min}", flush=True)
+    if args.replay:
+        print("gathers of matched pairs relative to pruning at s_min only:")
+        for name, (a, b) in replay_tot.items():
+            print(f"  {name}: {a / b:.3f}")
+        return
     for kind, (a, b, npairs, dv) in tot.items():
         if npairs:
             print(f"{kind}: {npairs} pairs, gathers/pair at s_min {a / npairs:.3g}"
