@@ -127,9 +127,12 @@ def test_tsdf_c1_shaped_synthetic(csm, oracle):
 
 @pytest.mark.parametrize("lin,ang_deg", [(0.5, 10.0), (3.5, 2.0)])
 def test_wide_windows(csm, oracle, lin, ang_deg):
-    """Windows whose candidates' gathered values do not fit one LDS stage
-    (+-0.5 m: 21 x offsets x 1080 points, staged in segments) or span several
-    64-offset chunks (+-3.5 m: 141 x offsets)."""
+    """Windows of one partly filled chunk of x offsets (+-0.5 m: 21 of a
+    workgroup's 64 lanes valid) and of several 64-offset chunks (+-3.5 m: 141
+    x offsets, three workgroups per (rotation, y offset), the last with 13
+    valid lanes), over a 1080-point cloud: 33 full pipeline batches of 32, an
+    odd count, so the loop leaves a full batch to the first tail and the
+    remaining 24 points to the second."""
     world = csm.SyntheticWorld2D(num_nodes=6, num_submaps=6, submap_cells=200, seed=13)
     opts = (lin, math.radians(ang_deg), 0.1, 0.1)
     m = csm.RealTimeCorrelativeScanMatcher2D(csm.RealTimeCorrelativeScanMatcherOptions(*opts))
@@ -149,11 +152,13 @@ def test_wide_windows(csm, oracle, lin, ang_deg):
 
 
 def test_tsdf_wide_window(csm, oracle):
-    """TSDF2D with a window past one LDS stage (+-0.6 m: 25 x offsets of
-    8-byte terms) and a cloud past the staged point indices."""
+    """TSDF2D (8-byte gathers of term and weight) over many pipeline batches:
+    5005 points are 156 full batches of 32, an even count, so the loop consumes
+    them all, the first tail sums the last 13 points and the second tail's
+    count is negative. +-0.6 m: 25 x offsets in one chunk."""
     limits, tsd, wgt = _seven_point_tsdf(oracle)
     g = csm.TSDF2D(*limits, tsd, wgt, 0.3, 1.0)
-    # 5005 points: the point indices are read from global memory (> 4096).
+    # 5005 points: 157 batches of indices per rotation, read with scalar loads.
     cloud = np.repeat(SEVEN, 715, axis=0) + np.float32(1e-5) * np.arange(5005, dtype=np.float32)[:, None]
     cloud[:, 2] = 0
     opts = (0.6, 0.05, 0.1, 0.1)
