@@ -220,6 +220,23 @@ class AdaptiveVoxelFilterOptions(C.Structure):
         return AdaptiveVoxelFilterOptions(max_length, min_num_points, max_range)
 
 
+class RangeData2DOptions(C.Structure):
+    """csm_range_data2d_options: the fields of
+    proto::LocalTrajectoryBuilderOptions2D that the range-data front end reads
+    (all floats); defaults are trajectory_builder_2d.lua:17-29's."""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float),
+                ("missing_data_ray_length", C.c_float), ("min_z", C.c_float),
+                ("max_z", C.c_float), ("voxel_filter_size", C.c_float),
+                ("adaptive_voxel_filter", AdaptiveVoxelFilterOptions)]
+
+    @staticmethod
+    def make(min_range=0.0, max_range=30.0, missing_data_ray_length=5.0, min_z=-0.8, max_z=2.0,
+             voxel_filter_size=0.025, adaptive_voxel_filter=None) -> "RangeData2DOptions":
+        return RangeData2DOptions(min_range, max_range, missing_data_ray_length, min_z, max_z,
+                                  voxel_filter_size,
+                                  adaptive_voxel_filter or AdaptiveVoxelFilterOptions.make())
+
+
 class LinearBounds(C.Structure):
     """SearchParameters::LinearBounds (correlative_scan_matcher_2d.h:37-42)."""
     _fields_ = [("min_x", C.c_int32), ("max_x", C.c_int32), ("min_y", C.c_int32),
@@ -365,6 +382,18 @@ _SIGNATURES = {
                                                    C.c_int32, C.c_int32,
                                                    C.POINTER(AdaptiveVoxelFilterOptions),
                                                    C.c_void_p, C.c_void_p]),
+    "csm_range_data2d_prepare": (C.c_int, [C.c_void_p, C.POINTER(RangeData2DOptions),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float),
+                                           C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int32)]),
+    "csm_range_data_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float),
+                                           C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float)]),
     "csm_ceres2d_refine_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
                                            C.c_void_p, C.POINTER(Refine2D), C.c_int64,
                                            C.POINTER(CeresOptions2D), C.POINTER(Pose2D),
@@ -1706,6 +1735,54 @@ def AdaptiveVoxelFilter(point_cloud, options: AdaptiveVoxelFilterOptions, intens
     if intensities is None:
         return pts[keep]
     return pts[keep], np.asarray(intensities, np.float32)[keep[:len(intensities)]]
+
+
+def range_data2d_prepare(options: RangeData2DOptions, hits, origin_index, poses, origins,
+                         gravity_from_local, local_origin, context: Optional[Context] = None):
+    """csm_range_data2d_prepare: AddRangeData's range loop
+    (local_trajectory_builder_2d.cc:163-185), TransformToGravityAlignedFrameAndFilter
+    (:51-63) and AdaptiveVoxelFilter (:228-231) on the device. ``hits`` (n, 3),
+    ``origin_index`` (n,), ``poses`` (n, 7) as (t xyz, q wxyz), ``origins``
+    (num_origins, 3); ``gravity_from_local`` (7,) and ``local_origin`` (3,).
+    Returns (origin (3,), returns, misses, filtered), the gravity-aligned range
+    data and the matchers' cloud, each (k, 3) float32 in input order."""
+    ctx = context or default_context()
+    h = _f32_points(hits)
+    n = len(h)
+    idx = np.ascontiguousarray(np.asarray(origin_index, np.int32).reshape(-1))
+    p = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 7))
+    o = _f32_points(origins)
+    if len(idx) != n or len(p) != n:
+        raise ValueError("hits, origin_index and poses differ in length")
+    g = np.ascontiguousarray(np.asarray(gravity_from_local, np.float32).reshape(7))
+    lo = np.ascontiguousarray(np.asarray(local_origin, np.float32).reshape(3))
+    origin = np.zeros(3, np.float32)
+    outs = [np.zeros((max(n, 1), 3), np.float32) for _ in range(3)]
+    counts = [C.c_int32(0) for _ in range(3)]
+    F = C.c_float
+    _check(ctx._lib.csm_range_data2d_prepare(
+        ctx.handle, C.byref(options), _ptr(h, F), _ptr(idx, C.c_int32), _ptr(p, F), n, _ptr(o, F),
+        len(o), _ptr(g, F), _ptr(lo, F), _ptr(origin, F), _ptr(outs[0], F), C.byref(counts[0]),
+        _ptr(outs[1], F), C.byref(counts[1]), _ptr(outs[2], F), C.byref(counts[2])),
+        "csm_range_data2d_prepare")
+    return (origin,) + tuple(a[:c.value].copy() for a, c in zip(outs, counts))
+
+
+def range_data_transform(transform, origin, returns, misses=None,
+                         context: Optional[Context] = None):
+    """csm_range_data_transform: sensor::TransformRangeData (range_data.cc:25-32)
+    by the Rigid3f ``transform`` (t xyz, q wxyz) -> (origin, returns, misses)."""
+    ctx = context or default_context()
+    t = np.ascontiguousarray(np.asarray(transform, np.float32).reshape(7))
+    o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+    r = _f32_points(returns)
+    m = _f32_points(misses if misses is not None else np.zeros((0, 3), np.float32))
+    o_out, r_out, m_out = np.zeros(3, np.float32), np.zeros_like(r), np.zeros_like(m)
+    F = C.c_float
+    _check(ctx._lib.csm_range_data_transform(
+        ctx.handle, _ptr(t, F), _ptr(o, F), _ptr(r, F), len(r), _ptr(m, F), len(m), _ptr(o_out, F),
+        _ptr(r_out, F), _ptr(m_out, F)), "csm_range_data_transform")
+    return o_out, r_out, m_out
 
 
 # --------------------------------------------------------------------------

@@ -317,6 +317,11 @@ struct csm_context {
   csm::DevBuf f3_jobs;
   // Voxel filter scratch (voxel_filter.hip).
   csm::DevBuf vf_points, vf_offsets, vf_keep, vf_counts;
+  // Range-data front end (range_data2d.hip): one call's upload, its working
+  // clouds and masks, its packed outputs, and the pinned staging of the one
+  // copy each way.
+  csm::DevBuf rd_in, rd_work, rd_out;
+  csm::PinnedBuf rd_stage_in, rd_stage_out;
   // CeresScanMatcher2D refinement scratch (ceres2d.hip).
   csm::DevBuf cr_items, cr_out, cr3_items, cr3_points, cr3_out;
   // The cloud of a single csm_ceres2d_match_*grid call, and the value tables

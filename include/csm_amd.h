@@ -1077,6 +1077,58 @@ int csm_adaptive_voxel_filter_device(csm_context* ctx, const float* d_xyz,
                                      const csm_adaptive_voxel_filter_options* options,
                                      uint8_t* d_keep, int32_t* d_counts);
 
+/* ---- range data: the front end of LocalTrajectoryBuilder2D ------------------
+ * From one accumulated sweep of rangefinder points to what the inserters and
+ * the scan matchers take (mapping/internal/2d/local_trajectory_builder_2d.cc).
+ * Rigid3f arguments are (t x y z, q w x y z). All arithmetic is float, not
+ * contracted, in Eigen's order, so every output float is the reference's bit
+ * for bit, and every output cloud is in input order. */
+typedef struct csm_range_data2d_options {
+  /* proto::LocalTrajectoryBuilderOptions2D
+   * (mapping/proto/local_trajectory_builder_options_2d.proto): all floats. */
+  float min_range;
+  float max_range;
+  float missing_data_ray_length;
+  float min_z;
+  float max_z;
+  float voxel_filter_size;
+  csm_adaptive_voxel_filter_options adaptive_voxel_filter;
+} csm_range_data2d_options;
+
+/* AddRangeData's range loop (local_trajectory_builder_2d.cc:163-185),
+ * TransformToGravityAlignedFrameAndFilter (:51-63) and the AdaptiveVoxelFilter
+ * of AddAccumulatedRangeData (:228-231), in one upload, one chain of launches
+ * and one download. Point i is hits_xyz[3 i ..] measured from
+ * origins_xyz[3 origin_index[i] ..], both moved by poses_tq[7 i ..]
+ * (range_data_poses[i]): dropped below min_range (or with a NaN range), a
+ * return up to max_range, else a miss at missing_data_ray_length along the
+ * ray. Returns and misses are moved by gravity_from_local_tq
+ * (transform_to_gravity_aligned_frame), cropped to min_z <= z <= max_z
+ * (sensor/point_cloud.cc:76-81) and voxel-filtered: returns_out / misses_out
+ * with num_returns / num_misses points; origin_out is local_origin_xyz
+ * (range_data_poses.back().translation()) moved likewise. filtered_out /
+ * num_filtered is AdaptiveVoxelFilter(returns_out). Each output cloud needs
+ * room for n points. n up to 8192 (larger: CSM_ERANGE); n == 0 gives zero
+ * counts. CSM_EINVAL: a null pointer with n > 0, an origin_index outside
+ * [0, num_origins), voxel_filter_size <= 0 or a non-positive adaptive
+ * max_length. */
+int csm_range_data2d_prepare(csm_context* ctx, const csm_range_data2d_options* options,
+                             const float* hits_xyz, const int32_t* origin_index,
+                             const float* poses_tq, int32_t n, const float* origins_xyz,
+                             int32_t num_origins, const float gravity_from_local_tq[7],
+                             const float local_origin_xyz[3], float origin_out[3],
+                             float* returns_out, int32_t* num_returns, float* misses_out,
+                             int32_t* num_misses, float* filtered_out, int32_t* num_filtered);
+
+/* sensor::TransformRangeData (sensor/range_data.cc:25-32) by a Rigid3f: the
+ * origin, the returns and the misses (local_trajectory_builder_2d.cc:246-248
+ * moves the gravity-aligned range data by Embed3D(pose_estimate_2d) before the
+ * insert). The outputs may not alias the inputs. */
+int csm_range_data_transform(csm_context* ctx, const float transform_tq[7],
+                             const float origin_xyz[3], const float* returns_xyz,
+                             int32_t num_returns, const float* misses_xyz, int32_t num_misses,
+                             float origin_out[3], float* returns_out, float* misses_out);
+
 /* ---- pbstream ingest --------------------------------------------------------
  * Reads a serialized state file (io/proto_stream.cc:26-86: magic, then per
  * message an 8-byte size and a gzip member; SerializationHeader then
