@@ -237,6 +237,25 @@ class RangeData2DOptions(C.Structure):
                                   adaptive_voxel_filter or AdaptiveVoxelFilterOptions.make())
 
 
+class RangeData3DOptions(C.Structure):
+    """csm_range_data3d_options: the fields of
+    proto::LocalTrajectoryBuilderOptions3D that the 3D range-data front end
+    reads; defaults are trajectory_builder_3d.lua:19-34's."""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float),
+                ("voxel_filter_size", C.c_float),
+                ("high_resolution_adaptive_voxel_filter", AdaptiveVoxelFilterOptions),
+                ("low_resolution_adaptive_voxel_filter", AdaptiveVoxelFilterOptions)]
+
+    @staticmethod
+    def make(min_range=1.0, max_range=60.0, voxel_filter_size=0.15,
+             high_resolution_adaptive_voxel_filter=None,
+             low_resolution_adaptive_voxel_filter=None) -> "RangeData3DOptions":
+        return RangeData3DOptions(
+            min_range, max_range, voxel_filter_size,
+            high_resolution_adaptive_voxel_filter or AdaptiveVoxelFilterOptions.make(2.0, 150, 15.0),
+            low_resolution_adaptive_voxel_filter or AdaptiveVoxelFilterOptions.make(4.0, 200, 60.0))
+
+
 class LinearBounds(C.Structure):
     """SearchParameters::LinearBounds (correlative_scan_matcher_2d.h:37-42)."""
     _fields_ = [("min_x", C.c_int32), ("max_x", C.c_int32), ("min_y", C.c_int32),
@@ -382,6 +401,22 @@ _SIGNATURES = {
                                                    C.c_int32, C.c_int32,
                                                    C.POINTER(AdaptiveVoxelFilterOptions),
                                                    C.c_void_p, C.c_void_p]),
+    "csm_voxel_filter_large": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_float,
+                                         C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
+    "csm_adaptive_voxel_filter_large": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int64,
+                                                  C.POINTER(AdaptiveVoxelFilterOptions),
+                                                  C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
+    "csm_range_data3d_prepare": (C.c_int, [C.c_void_p, C.POINTER(RangeData3DOptions),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32,
+                                           C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int32)]),
     "csm_range_data2d_prepare": (C.c_int, [C.c_void_p, C.POINTER(RangeData2DOptions),
                                            C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float),
@@ -510,6 +545,8 @@ _SIGNATURES = {
     "csm_hybrid_grid_insert_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int64)]),
     "csm_inserter3d_lookup_table": (C.c_int, [C.c_float, C.POINTER(C.c_uint16)]),
+    "csm_compute_histogram": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.c_int32,
+                                        C.POINTER(C.c_float)]),
     "csm_rotate_histogram": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_float,
                                        C.POINTER(C.c_float)]),
     "csm_pbstream_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
@@ -1671,7 +1708,7 @@ from .matching3d import (FastCorrelativeScanMatcher3D, FastCorrelativeScanMatche
                          HybridGrid, IntensityHybridGrid, NodeData3D, NodeSet3D, PAIR3_DTYPE,
                          RESULT3_DTYPE,
                          RealTimeCorrelativeScanMatcher3D, SyntheticWorld3D,
-                         ceres_intensity_evaluate_3d, ceres_refine_batch_3d,
+                         ceres_intensity_evaluate_3d, ceres_refine_batch_3d, compute_histogram,
                          inserter3d_lookup_table, make_pairs_3d, match_batch_3d, rotate_histogram)
 
 
@@ -1735,6 +1772,94 @@ def AdaptiveVoxelFilter(point_cloud, options: AdaptiveVoxelFilterOptions, intens
     if intensities is None:
         return pts[keep]
     return pts[keep], np.asarray(intensities, np.float32)[keep[:len(intensities)]]
+
+
+def voxel_filter_large_mask(point_cloud, resolution: float, context: Optional[Context] = None):
+    """csm_voxel_filter_large: sensor::VoxelFilter (voxel_filter.cc:212-232) of
+    one cloud of up to 2^20 points -> (keep mask, count)."""
+    ctx = context or default_context()
+    pts = _f32_points(point_cloud)
+    keep = np.zeros(max(len(pts), 1), np.uint8)
+    count = C.c_int64(0)
+    _check(ctx._lib.csm_voxel_filter_large(ctx.handle, _ptr(pts, C.c_float), len(pts),
+                                           float(resolution), _ptr(keep, C.c_uint8),
+                                           C.byref(count)), "csm_voxel_filter_large")
+    return keep[:len(pts)].astype(bool), int(count.value)
+
+
+def adaptive_voxel_filter_large_mask(point_cloud, options: AdaptiveVoxelFilterOptions,
+                                     context: Optional[Context] = None):
+    """csm_adaptive_voxel_filter_large: sensor::AdaptiveVoxelFilter
+    (voxel_filter.cc:263-268) of one cloud of up to 2^20 points -> (keep mask, count)."""
+    ctx = context or default_context()
+    pts = _f32_points(point_cloud)
+    keep = np.zeros(max(len(pts), 1), np.uint8)
+    count = C.c_int64(0)
+    _check(ctx._lib.csm_adaptive_voxel_filter_large(ctx.handle, _ptr(pts, C.c_float), len(pts),
+                                                    C.byref(options), _ptr(keep, C.c_uint8),
+                                                    C.byref(count)),
+           "csm_adaptive_voxel_filter_large")
+    return keep[:len(pts)].astype(bool), int(count.value)
+
+
+def VoxelFilterLarge(point_cloud, resolution: float, intensities=None,
+                     context: Optional[Context] = None):
+    """VoxelFilter for clouds of any size up to 2^20 points: the surviving
+    points in input order (and their intensities, if given)."""
+    pts = _f32_points(point_cloud)
+    keep, _ = voxel_filter_large_mask(pts, resolution, context)
+    if intensities is None:
+        return pts[keep]
+    return pts[keep], np.asarray(intensities, np.float32)[keep]
+
+
+def range_data3d_prepare(options: RangeData3DOptions, hits, origin_index, poses, origins,
+                         tracking_from_local, local_origin, intensities=None,
+                         context: Optional[Context] = None):
+    """csm_range_data3d_prepare: AddRangeData's range loop
+    (local_trajectory_builder_3d.cc:636-669), both VoxelFilter calls (:680-683),
+    TransformRangeData by ``tracking_from_local`` (:696-698) and both
+    AdaptiveVoxelFilter calls (:734-745) on the device. ``hits`` (n, 3),
+    ``origin_index`` (n,), ``poses`` (n, 7) as (t xyz, q wxyz), ``origins``
+    (num_origins, 3), ``intensities`` (n,) or None. Returns a dict: ``origin``
+    (3,), ``returns``, ``misses``, ``high``, ``low`` as (k, 3) float32 in input
+    order and ``returns_intensities``, ``high_intensities``,
+    ``low_intensities`` (None without intensities)."""
+    ctx = context or default_context()
+    h = _f32_points(hits)
+    n = len(h)
+    idx = np.ascontiguousarray(np.asarray(origin_index, np.int32).reshape(-1))
+    p = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 7))
+    o = _f32_points(origins)
+    if len(idx) != n or len(p) != n:
+        raise ValueError("hits, origin_index and poses differ in length")
+    inten = None
+    if intensities is not None:
+        inten = np.ascontiguousarray(np.asarray(intensities, np.float32).reshape(-1))
+        if len(inten) != n:
+            raise ValueError("hits and intensities differ in length")
+    g = np.ascontiguousarray(np.asarray(tracking_from_local, np.float32).reshape(7))
+    lo = np.ascontiguousarray(np.asarray(local_origin, np.float32).reshape(3))
+    origin = np.zeros(3, np.float32)
+    clouds = [np.zeros((max(n, 1), 3), np.float32) for _ in range(4)]  # returns, misses, high, low
+    ints = [np.zeros(max(n, 1), np.float32) for _ in range(3)]  # of returns, high, low
+    counts = [C.c_int32(0) for _ in range(4)]
+    F = C.c_float
+    ip = (lambda a: _ptr(a, F)) if inten is not None else (lambda a: None)
+    _check(ctx._lib.csm_range_data3d_prepare(
+        ctx.handle, C.byref(options), _ptr(h, F), ip(inten), _ptr(idx, C.c_int32), _ptr(p, F), n,
+        _ptr(o, F), len(o), _ptr(g, F), _ptr(lo, F), _ptr(origin, F),
+        _ptr(clouds[0], F), ip(ints[0]), C.byref(counts[0]),
+        _ptr(clouds[1], F), C.byref(counts[1]),
+        _ptr(clouds[2], F), ip(ints[1]), C.byref(counts[2]),
+        _ptr(clouds[3], F), ip(ints[2]), C.byref(counts[3])), "csm_range_data3d_prepare")
+    nr, nm, nh, nl = (c.value for c in counts)
+    with_i = inten is not None
+    return {"origin": origin, "returns": clouds[0][:nr].copy(), "misses": clouds[1][:nm].copy(),
+            "high": clouds[2][:nh].copy(), "low": clouds[3][:nl].copy(),
+            "returns_intensities": ints[0][:nr].copy() if with_i else None,
+            "high_intensities": ints[1][:nh].copy() if with_i else None,
+            "low_intensities": ints[2][:nl].copy() if with_i else None}
 
 
 def range_data2d_prepare(options: RangeData2DOptions, hits, origin_index, poses, origins,

@@ -317,6 +317,13 @@ struct csm_context {
   csm::DevBuf f3_jobs;
   // Voxel filter scratch (voxel_filter.hip).
   csm::DevBuf vf_points, vf_offsets, vf_keep, vf_counts;
+  // Voxel filters for large clouds (voxel_filter_large.hip): the working set of
+  // one cloud (keys, sorted pairs, ranks, masks, the range-filtered copy), the
+  // radix sort's scratch, and the pinned words a pass reports through. Sized
+  // for the largest cloud seen so far.
+  csm::DevBuf vfl_work, vfl_sort, vfl_cloud;
+  csm::PinnedBuf vfl_rb;
+  int64_t vfl_capacity = 0;
   // Range-data front end (range_data2d.hip): one call's upload, its working
   // clouds and masks, its packed outputs, and the pinned staging of the one
   // copy each way.
@@ -435,6 +442,24 @@ int EnsureValueTable(csm_context* ctx, float unknown, float lower, float upper, 
 int Rt2dMatchGrid(csm_context* ctx, const csm_rt_options* o, const csm_probability_grid* grid,
                   const csm_pose2d* initial, const float* xyz, int32_t n, double* score,
                   csm_pose2d* pose);
+
+// Voxel filters for clouds of up to kVflMaxPoints points (voxel_filter_large.hip)
+// on a packed device cloud, for callers that hold ctx->mu. Each enqueues on
+// ctx->stream and waits for it (the host steers the draw passes and the
+// adaptive search by small read-backs): *count is final on return, d_keep is
+// written in stream order. VflCompact only enqueues: the points with d_sel[i] == want, in
+// order, to out_xyz (and out_intensities when intensities is given);
+// d_index_out (optional) receives their indices and d_count their number.
+constexpr int64_t kVflMaxPoints = int64_t{1} << 20;
+int VflReserve(csm_context* ctx, int64_t n);
+int VflVoxelFilter(csm_context* ctx, const float* d_xyz, int32_t n, float resolution,
+                   uint8_t* d_keep, int32_t* count);
+int VflAdaptiveVoxelFilter(csm_context* ctx, const float* d_xyz, int32_t n,
+                           const csm_adaptive_voxel_filter_options* options, uint8_t* d_keep,
+                           int32_t* count);
+int VflCompact(csm_context* ctx, const uint8_t* d_sel, uint8_t want, int32_t n,
+               const float* d_xyz, const float* d_intensities, float* d_out_xyz,
+               float* d_out_intensities, uint32_t* d_index_out, int32_t* d_count);
 
 // Call contexts (csm_context::call_free): taken for one single Match call,
 // returned with its timing added to the owner's.

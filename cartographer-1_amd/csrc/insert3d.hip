@@ -57,6 +57,7 @@
 #include <cmath>
 #include <cstring>
 #include <deque>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -943,6 +944,90 @@ int InsertBatch3(csm_context* ctx, csm_hybrid_grid* const* grids, int32_t num_gr
 
 using namespace csm;
 
+// RotationalScanMatcher::ComputeHistogram's host steps
+// (rotational_scan_matcher.cc:34-117), float arithmetic in the reference's order.
+namespace csm {
+namespace {
+
+constexpr float kHistMinDistance = 0.2f, kHistMaxDistance = 0.9f, kHistSliceHeight = 0.2f;
+
+struct HistPoint {
+  float x, y, z;
+};
+using HistSlice = std::vector<HistPoint>;
+
+int HistRoundToInt(float v) { return static_cast<int>(std::lround(v)); }
+float HistNorm2(float x, float y) { return std::sqrt(x * x + y * y); }
+
+// AddValueToHistogram (:34-49).
+void HistAddValue(float angle, float value, int size, float* histogram) {
+  const float pi = static_cast<float>(M_PI);
+  while (angle > pi) angle -= pi;
+  while (angle < 0.f) angle += pi;
+  const float zero_to_one = angle / pi;
+  const int bucket = std::min(
+      std::max(HistRoundToInt(static_cast<float>(size) * zero_to_one - 0.5f), 0), size - 1);
+  histogram[bucket] += value;
+}
+
+// ComputeCentroid (:51-58): the sum in point order, then one division each.
+HistPoint HistCentroid(const HistSlice& slice) {
+  HistPoint sum{0.f, 0.f, 0.f};
+  for (const HistPoint& p : slice) {
+    sum.x += p.x;
+    sum.y += p.y;
+    sum.z += p.z;
+  }
+  const float n = static_cast<float>(slice.size());
+  return HistPoint{sum.x / n, sum.y / n, sum.z / n};
+}
+
+// SortSlice (:92-117): by the angle about the centroid, points near it dropped.
+HistSlice HistSortSlice(const HistSlice& slice) {
+  struct ByAngle {
+    bool operator<(const ByAngle& other) const { return angle < other.angle; }
+    float angle;
+    HistPoint point;
+  };
+  const HistPoint centroid = HistCentroid(slice);
+  std::vector<ByAngle> by_angle;
+  by_angle.reserve(slice.size());
+  for (const HistPoint& p : slice) {
+    const float dx = p.x - centroid.x, dy = p.y - centroid.y;
+    if (HistNorm2(dx, dy) < kHistMinDistance) continue;
+    by_angle.push_back(ByAngle{std::atan2(dy, dx), p});
+  }
+  std::sort(by_angle.begin(), by_angle.end());
+  HistSlice sorted;
+  sorted.reserve(by_angle.size());
+  for (const ByAngle& e : by_angle) sorted.push_back(e.point);
+  return sorted;
+}
+
+// AddPointCloudSliceToHistogram (:60-88).
+void HistAddSlice(const HistSlice& slice, int size, float* histogram) {
+  if (slice.empty()) return;
+  const HistPoint centroid = HistCentroid(slice);
+  HistPoint last = slice.front();
+  for (const HistPoint& p : slice) {
+    const float dx = p.x - last.x, dy = p.y - last.y;
+    const float cx = p.x - centroid.x, cy = p.y - centroid.y;
+    const float distance = HistNorm2(dx, dy);
+    if (distance < kHistMinDistance || HistNorm2(cx, cy) < kHistMinDistance) continue;
+    if (distance > kHistMaxDistance) {
+      last = p;
+      continue;
+    }
+    const float angle = std::atan2(dy, dx);
+    const float dn = HistNorm2(dx, dy), cn = HistNorm2(cx, cy);
+    const float dot = (dx / dn) * (cx / cn) + (dy / dn) * (cy / cn);
+    HistAddValue(angle, std::max(0.f, 1.f - std::abs(dot)), size, histogram);
+  }
+}
+
+}  // namespace
+}  // namespace csm
+
 extern "C" {
 
 int csm_inserter3d_lookup_table(float probability, uint16_t* out) {
@@ -967,6 +1052,19 @@ int csm_rotate_histogram(const float* histogram, int32_t size, float angle, floa
     const float r1 = in[(i + 1 + full_buckets) % size];
     out[i] = fraction * r1 + (1.f - fraction) * r0;
   }
+  return CSM_OK;
+}
+
+int csm_compute_histogram(const float* points_xyz, int64_t n, int32_t histogram_size, float* out) {
+  if (n < 0 || histogram_size <= 0 || !out || (n > 0 && !points_xyz)) return CSM_EINVAL;
+  std::fill(out, out + histogram_size, 0.f);
+  std::map<int, csm::HistSlice> slices;  // :160-171
+  for (int64_t i = 0; i < n; ++i) {
+    const csm::HistPoint p{points_xyz[3 * i], points_xyz[3 * i + 1], points_xyz[3 * i + 2]};
+    slices[csm::HistRoundToInt(p.z / csm::kHistSliceHeight)].push_back(p);
+  }
+  for (const auto& slice : slices)
+    csm::HistAddSlice(csm::HistSortSlice(slice.second), histogram_size, out);
   return CSM_OK;
 }
 

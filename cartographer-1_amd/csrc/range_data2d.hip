@@ -32,6 +32,7 @@
 #include <cstring>
 
 #include "csm_internal.h"
+#include "rigid3_dev.h"
 
 namespace csm {
 namespace {
@@ -41,13 +42,6 @@ constexpr int kRdWaves = kRdThreads / 64;
 constexpr int kRdTiles = 8;
 constexpr int kRdMaxPoints = kRdThreads * kRdTiles;  // 8192, the voxel filters' limit
 constexpr int kRdSlots = kRdWaves * kRdTiles;        // per-wave counts of a cloud: 128
-
-struct RdVec3 {
-  float x, y, z;
-};
-struct RdRigid3 {
-  float tx, ty, tz, qw, qx, qy, qz;
-};
 
 // What range_data2d_classify takes by value.
 struct RdParams {
@@ -62,27 +56,6 @@ struct RdHeader {
   float origin[3];
   float pad1;
 };
-
-// Eigen MatrixBase::cross, coefficient order kept.
-__host__ __device__ __forceinline__ RdVec3 RdCross(float ax, float ay, float az, const RdVec3& b) {
-  return RdVec3{ay * b.z - az * b.y, az * b.x - ax * b.z, ax * b.y - ay * b.x};
-}
-
-// rigid_transform.h:190-196 with Eigen QuaternionBase::_transformVector:
-// uv = 2 (q.vec x v); v + q.w uv + q.vec x uv; then the translation.
-__host__ __device__ __forceinline__ RdVec3 RdApply(const RdRigid3& r, const RdVec3& v) {
-  RdVec3 uv = RdCross(r.qx, r.qy, r.qz, v);
-  uv.x += uv.x;
-  uv.y += uv.y;
-  uv.z += uv.z;
-  const RdVec3 c = RdCross(r.qx, r.qy, r.qz, uv);
-  const RdVec3 w{(v.x + r.qw * uv.x) + c.x, (v.y + r.qw * uv.y) + c.y, (v.z + r.qw * uv.z) + c.z};
-  return RdVec3{w.x + r.tx, w.y + r.ty, w.z + r.tz};
-}
-
-__device__ __forceinline__ RdRigid3 RdLoadRigid(const float* __restrict__ p) {
-  return RdRigid3{p[0], p[1], p[2], p[3], p[4], p[5], p[6]};
-}
 
 // Bit t of `sel` says whether this thread's point of tile t (point
 // t * 1024 + threadIdx.x) is selected. Leaves in cnt[t * 16 + wave] the number

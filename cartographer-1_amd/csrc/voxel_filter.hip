@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "csm_internal.h"
+#include "voxel_filter_dev.h"
 
 namespace csm {
 namespace {
@@ -41,50 +42,6 @@ namespace {
 constexpr int kVfThreads = 256;
 constexpr int kVfMaxPoints = 8192;  // LDS: 14 B per slot, 112 KiB at 8192
 constexpr uint16_t kPad = 0xffff;
-constexpr uint32_t kMinstdM = 2147483647u;  // std::minstd_rand0: x <- 16807 x mod (2^31 - 1)
-constexpr uint32_t kMinstdA = 16807u;
-// uniform_int_distribution's __urngrange = max() - min() for minstd_rand0.
-constexpr uint32_t kUrngRange = 2147483645u;
-
-__device__ __forceinline__ uint32_t MulMod(uint32_t a, uint32_t b) {
-  const uint64_t p = static_cast<uint64_t>(a) * b;  // < 2^62
-  uint64_t r = (p & kMinstdM) + (p >> 31);          // < 2^32
-  r = (r & kMinstdM) + (r >> 31);                   // <= 2^31
-  return static_cast<uint32_t>(r >= kMinstdM ? r - kMinstdM : r);
-}
-
-// State of a seed-1 minstd_rand0 after e draws.
-__device__ uint32_t MinstdJump(uint32_t e) {
-  uint32_t result = 1u, base = kMinstdA;
-  while (e) {
-    if (e & 1u) result = MulMod(result, base);
-    base = MulMod(base, base);
-    e >>= 1;
-  }
-  return result;
-}
-
-// One uniform_int_distribution<>(1, k) draw from output x (no rejection):
-// returns 1 when the draw equals k, 0 otherwise, 2 when x is rejected.
-__device__ __forceinline__ int Draw(uint32_t x, uint32_t k) {
-  const uint32_t scaling = kUrngRange / k;
-  const uint32_t past = k * scaling;
-  const uint32_t ret = x - 1u;  // __urng() - __urngmin
-  if (ret >= past) return 2;
-  return (ret / scaling + 1u == k) ? 1 : 0;
-}
-
-// GetVoxelCellIndex (voxel_filter.cc:79-86).
-__device__ __forceinline__ uint64_t VoxelKeyCoord(float v, float resolution) {
-  const float q = __fdiv_rn(v, resolution);
-  // common::RoundToInt = std::lround narrowed to int, then widened to uint64_t.
-  const int i = static_cast<int>(static_cast<long long>(roundf(q)));
-  return static_cast<uint64_t>(static_cast<int64_t>(i));
-}
-__device__ __forceinline__ uint64_t VoxelKey(float x, float y, float z, float resolution) {
-  return (VoxelKeyCoord(x, resolution) << 42) + (VoxelKeyCoord(y, resolution) << 21) +
-         VoxelKeyCoord(z, resolution);
-}
 
 struct VfLds {
   uint64_t* key;   // [M] sort keys; after sorting, overlaid by seg / rank / aux
@@ -318,8 +275,7 @@ voxel_filter_batch(const float* __restrict__ points, const int64_t* __restrict__
       const int i = i0 + e;
       if (i < n) {
         const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        const float norm = sqrtf(__fadd_rn(__fmul_rn(x, x), __fadd_rn(__fmul_rn(y, y), __fmul_rn(z, z))));
-        if (norm <= p2) pass |= 1u << e;
+        if (VfWithinRange(x, y, z, p2)) pass |= 1u << e;
       }
     }
     int total = 0;
@@ -341,30 +297,14 @@ voxel_filter_batch(const float* __restrict__ points, const int64_t* __restrict__
     __syncthreads();
     kept = m;
   } else {
-    // AdaptivelyVoxelFiltered (voxel_filter.cc:38-76), float arithmetic as written.
-    const float max_length = p0, min_num_points = p1;
-    kept = VoxelFilterPass(xyz, L, m, max_length, tmp, &flag);
-    CopyMask(L, m);
-    if (!(static_cast<float>(kept) >= min_num_points)) {
-      for (float high_length = max_length; high_length > __fmul_rn(1e-2f, max_length);
-           high_length = __fdiv_rn(high_length, 2.f)) {
-        float low_length = __fdiv_rn(high_length, 2.f);
-        kept = VoxelFilterPass(xyz, L, m, low_length, tmp, &flag);
+    // AdaptivelyVoxelFiltered (voxel_filter.cc:38-76): VfLengthSearch walks its lengths.
+    kept = m;
+    VfLengthSearch search(p0, p1);
+    while (!search.Done()) {
+      const int cand = VoxelFilterPass(xyz, L, m, search.Length(), tmp, &flag);
+      if (search.Step(cand)) {
+        kept = cand;
         CopyMask(L, m);
-        if (static_cast<float>(kept) >= min_num_points) {
-          while (__fdiv_rn(__fsub_rn(high_length, low_length), low_length) > 1e-1f) {
-            const float mid_length = __fdiv_rn(__fadd_rn(low_length, high_length), 2.f);
-            const int cand = VoxelFilterPass(xyz, L, m, mid_length, tmp, &flag);
-            if (static_cast<float>(cand) >= min_num_points) {
-              low_length = mid_length;
-              kept = cand;
-              CopyMask(L, m);
-            } else {
-              high_length = mid_length;
-            }
-          }
-          break;
-        }
       }
     }
   }

@@ -314,6 +314,17 @@ def rotate_histogram(histogram, angle: float) -> np.ndarray:
     return out
 
 
+def compute_histogram(point_cloud, histogram_size: int) -> np.ndarray:
+    """RotationalScanMatcher::ComputeHistogram (rotational_scan_matcher.cc:160-171)
+    on the host: the histogram of a node's gravity-aligned returns."""
+    pts = np.ascontiguousarray(np.asarray(point_cloud, np.float32).reshape(-1, 3))
+    out = np.zeros(int(histogram_size), np.float32)
+    _check(load_library().csm_compute_histogram(_ptr(pts, C.c_float), len(pts),
+                                                int(histogram_size), _ptr(out, C.c_float)),
+           "csm_compute_histogram")
+    return out
+
+
 def _pose(p) -> Pose3D:
     if isinstance(p, Pose3D):
         return p

@@ -1040,6 +1040,19 @@ int csm_inserter3d_lookup_table(float probability, uint16_t* out /* [32768] */);
  * Host-only. */
 int csm_rotate_histogram(const float* histogram, int32_t size, float angle, float* out);
 
+/* RotationalScanMatcher::ComputeHistogram(point_cloud, histogram_size)
+ * (rotational_scan_matcher.cc:160-171 with AddValueToHistogram :34-49,
+ * ComputeCentroid :51-58, AddPointCloudSliceToHistogram :60-88 and
+ * SortSlice :92-117): the histogram LocalTrajectoryBuilder3D::InsertIntoSubmap
+ * makes of a node's gravity-aligned returns (local_trajectory_builder_3d.cc:
+ * 898-903). points_xyz holds n points (x, y, z); out receives histogram_size
+ * floats. The same slices (a map keyed by RoundToInt(z / 0.2)), the same
+ * std::sort by the angle about the slice's centroid, the same float order, so
+ * the result is the reference's bit for bit on a host whose atan2f is the
+ * reference's. Host-only on purpose (it takes no context): its atan2f is the
+ * C library's. CSM_EINVAL: n < 0, histogram_size <= 0, a null pointer. */
+int csm_compute_histogram(const float* points_xyz, int64_t n, int32_t histogram_size, float* out);
+
 /* ---- node clouds: voxel filters -------------------------------------------
  * sensor::VoxelFilter and sensor::AdaptiveVoxelFilter
  * (sensor/internal/voxel_filter.h, voxel_filter.cc:212-232 and :263-268), the
@@ -1076,6 +1089,25 @@ int csm_adaptive_voxel_filter_device(csm_context* ctx, const float* d_xyz,
                                      int32_t max_points,
                                      const csm_adaptive_voxel_filter_options* options,
                                      uint8_t* d_keep, int32_t* d_counts);
+
+/* The same two filters for one cloud of up to 2^20 points (larger: CSM_ERANGE,
+ * checked before the device is touched), the size of a 3D sweep
+ * (local_trajectory_builder_3d.cc:680-683 filters the accumulated returns,
+ * :734-745 the returns in the tracking frame; the reference's own
+ * LocalTrajectoryBuilderTest feeds 16 000 points per scan). The kept set is
+ * RandomizedVoxelFilterIndices' (voxel_filter.cc:136-162) exactly, and the
+ * adaptive filter is FilterByMaxRange (:31-36), AdaptivelyVoxelFiltered
+ * (:38-76) and AdaptiveVoxelFilter (:263-268) exactly, whatever the size: the
+ * cloud lives in global memory, sorted by voxel key with a device radix sort.
+ * keep[i] = 1 for a surviving point; *count = survivors. n == 0: CSM_OK and a
+ * zero count. CSM_EINVAL: a null pointer with n > 0, a null count,
+ * resolution <= 0, max_length <= 0. Working memory is kept with the context
+ * and grows on demand. */
+int csm_voxel_filter_large(csm_context* ctx, const float* xyz, int64_t n, float resolution,
+                           uint8_t* keep, int64_t* count);
+int csm_adaptive_voxel_filter_large(csm_context* ctx, const float* xyz, int64_t n,
+                                    const csm_adaptive_voxel_filter_options* options,
+                                    uint8_t* keep, int64_t* count);
 
 /* ---- range data: the front end of LocalTrajectoryBuilder2D ------------------
  * From one accumulated sweep of rangefinder points to what the inserters and
@@ -1119,6 +1151,47 @@ int csm_range_data2d_prepare(csm_context* ctx, const csm_range_data2d_options* o
                              const float local_origin_xyz[3], float origin_out[3],
                              float* returns_out, int32_t* num_returns, float* misses_out,
                              int32_t* num_misses, float* filtered_out, int32_t* num_filtered);
+
+/* ---- range data: the front end of LocalTrajectoryBuilder3D ------------------ */
+typedef struct csm_range_data3d_options {
+  /* proto::LocalTrajectoryBuilderOptions3D
+   * (mapping/proto/local_trajectory_builder_options_3d.proto). */
+  float min_range;
+  float max_range;
+  float voxel_filter_size;
+  csm_adaptive_voxel_filter_options high_resolution_adaptive_voxel_filter;
+  csm_adaptive_voxel_filter_options low_resolution_adaptive_voxel_filter;
+} csm_range_data3d_options;
+
+/* AddRangeData's range loop (local_trajectory_builder_3d.cc:636-669), the two
+ * VoxelFilter calls (:680-683), TransformRangeData by tracking_from_local
+ * (:696-698) and the two AdaptiveVoxelFilter calls of AddAccumulatedRangeData
+ * on the transformed returns (:734-745), in one upload, one chain of launches
+ * and one download. Point i is hits_xyz[3 i ..] measured from
+ * origins_xyz[3 origin_index[i] ..], both moved by poses_tq[7 i ..]: dropped
+ * below min_range (or with a NaN range), a return up to max_range carrying
+ * intensities[i], else a miss at origin + (max_range / range) * delta (the 3D
+ * builder crops the ray to max_range). Returns and misses are voxel-filtered
+ * at voxel_filter_size and moved by tracking_from_local_tq
+ * (current_pose.inverse().cast<float>()): returns_out / misses_out;
+ * origin_out is local_origin_xyz (current_pose.translation().cast<float>())
+ * moved likewise. high_out / low_out are AdaptiveVoxelFilter(returns_out) with
+ * the two option sets. Intensities follow their points through every filter;
+ * intensities == NULL: none, and the intensity outputs are not written (they
+ * may be NULL). Every output cloud is in input order and needs room for n
+ * points. n up to 2^20 (larger: CSM_ERANGE); n == 0 gives zero counts.
+ * CSM_EINVAL: a null pointer with n > 0, an origin_index outside
+ * [0, num_origins), voxel_filter_size <= 0 or a non-positive max_length. */
+int csm_range_data3d_prepare(csm_context* ctx, const csm_range_data3d_options* options,
+                             const float* hits_xyz, const float* intensities,
+                             const int32_t* origin_index, const float* poses_tq, int32_t n,
+                             const float* origins_xyz, int32_t num_origins,
+                             const float tracking_from_local_tq[7],
+                             const float local_origin_xyz[3], float origin_out[3],
+                             float* returns_out, float* returns_intensities_out,
+                             int32_t* num_returns, float* misses_out, int32_t* num_misses,
+                             float* high_out, float* high_intensities_out, int32_t* num_high,
+                             float* low_out, float* low_intensities_out, int32_t* num_low);
 
 /* sensor::TransformRangeData (sensor/range_data.cc:25-32) by a Rigid3f: the
  * origin, the returns and the misses (local_trajectory_builder_2d.cc:246-248
