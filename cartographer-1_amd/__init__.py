@@ -281,6 +281,28 @@ class Pair3D(C.Structure):
                 ("min_score", C.c_float), ("node_pose", Pose3D), ("submap_pose", Pose3D)]
 
 
+class PoseGraph2DEdge(C.Structure):
+    """csm_pose_graph2d_edge: `end` observed from `start` as zbar (x, y, angle)."""
+    _fields_ = [("start", C.c_int32), ("end", C.c_int32), ("zbar", C.c_double * 3),
+                ("translation_weight", C.c_double), ("rotation_weight", C.c_double),
+                ("loss", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseGraph2DOptions(C.Structure):
+    """csm_pose_graph2d_options (pose_graph.lua's optimization_problem)."""
+    _fields_ = [("huber_scale", C.c_double), ("max_num_iterations", C.c_int32),
+                ("use_nonmonotonic_steps", C.c_int32), ("max_cg_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("cg_relative_tolerance", C.c_double)]
+
+
+class PoseGraph2DSummary(C.Structure):
+    """csm_pose_graph2d_summary."""
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("num_iterations", C.c_int32), ("num_successful_steps", C.c_int32),
+                ("num_cg_iterations", C.c_int32), ("num_cg_capped_steps", C.c_int32),
+                ("termination", C.c_int32), ("reserved", C.c_int32)]
+
+
 # Exported symbols and their signatures (include/csm_amd.h).
 _SIGNATURES = {
     "csm_context_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
@@ -589,6 +611,17 @@ _SIGNATURES = {
     "csm_comm_barrier": (C.c_int, [C.c_void_p]),
     "csm_comm_claim_open": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "csm_comm_fetch_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "csm_pose_graph2d_default_options": (None, [C.POINTER(PoseGraph2DOptions)]),
+    "csm_pose_graph2d_evaluate": (C.c_int, [C.c_void_p, C.POINTER(PoseGraph2DOptions),
+                                            C.POINTER(C.c_double), C.c_int32,
+                                            C.POINTER(PoseGraph2DEdge), C.c_int64,
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double)]),
+    "csm_pose_graph2d_solve": (C.c_int, [C.c_void_p, C.POINTER(PoseGraph2DOptions),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int32,
+                                         C.POINTER(PoseGraph2DEdge), C.c_int64,
+                                         C.POINTER(PoseGraph2DSummary)]),
+    "csm_pose_graph2d_last_phase_seconds": (None, [C.c_void_p, C.POINTER(C.c_double)]),
     "csm_strerror": (C.c_char_p, [C.c_int]),
 }
 
@@ -2068,3 +2101,6 @@ from .submap_3d import (ActiveSubmaps3D, CeresScanMatcher3D,  # noqa: E402,F401
                         CeresScanMatcherOptions3D, IntensityCostFunctionOptions,
                         RangeDataInserter3D, RangeDataInserterOptions3D, Submap3D,
                         SubmapsOptions3D)
+from .optimization_problem_2d import (OptimizationProblem2D, OptimizationProblemOptions,  # noqa: E402,F401
+                                      pose_graph2d_edges, pose_graph2d_evaluate,
+                                      pose_graph2d_solve)

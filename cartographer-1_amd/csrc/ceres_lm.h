@@ -4,6 +4,8 @@
 // quality of a step is judged against the current cost and a reference cost,
 // so that with ceres_solver_options.use_nonmonotonic_steps up to
 // max_consecutive_nonmonotonic_steps (5) accepted steps may raise the cost.
+// The pose-graph solve (pose_graph2d.hip) drives its outer loop on the host
+// with the same two structs, hence __host__ __device__.
 #ifndef CSM_CERES_LM_H_
 #define CSM_CERES_LM_H_
 
@@ -15,16 +17,16 @@ struct StepEvaluator {
   double reference_cost, minimum_cost, current_cost, candidate_cost;
   double acc_reference_model, acc_candidate_model;
   int num_nonmonotonic, max_nonmonotonic;
-  __device__ StepEvaluator(double cost, bool nonmonotonic)
+  __host__ __device__ StepEvaluator(double cost, bool nonmonotonic)
       : reference_cost(cost), minimum_cost(cost), current_cost(cost), candidate_cost(cost),
         acc_reference_model(0.), acc_candidate_model(0.), num_nonmonotonic(0),
         max_nonmonotonic(nonmonotonic ? 5 : 0) {}
-  __device__ double Quality(double cost, double model) const {
+  __host__ __device__ double Quality(double cost, double model) const {
     const double relative = (current_cost - cost) / model;
     const double historical = (reference_cost - cost) / (acc_reference_model + model);
     return fmax(relative, historical);
   }
-  __device__ void Accepted(double cost, double model) {
+  __host__ __device__ void Accepted(double cost, double model) {
     current_cost = cost;
     acc_candidate_model += model;
     acc_reference_model += model;
@@ -50,12 +52,12 @@ struct StepEvaluator {
 // LevenbergMarquardtStrategy radius updates (levenberg_marquardt_strategy.cc).
 struct LmRadius {
   double radius = 1e4, decrease = 2.;
-  __device__ void Accepted(double quality) {
+  __host__ __device__ void Accepted(double quality) {
     const double tf = 2. * quality - 1.;
     radius = fmin(1e16, radius / fmax(1. / 3., 1. - tf * tf * tf));
     decrease = 2.;
   }
-  __device__ void Rejected() {
+  __host__ __device__ void Rejected() {
     radius /= decrease;
     decrease *= 2.;
   }

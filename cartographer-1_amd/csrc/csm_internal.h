@@ -368,6 +368,12 @@ struct csm_context {
   std::map<std::pair<float, float>, csm::TsdfTables> tsdf_tabs;
   csm::DevBuf tsdf_dev;
   csm::StageRing tsdf_stage;
+  // Pose-graph solve (pose_graph2d.hip): one call's device arena, the pinned
+  // words its read-backs land in, and the last solve's host seconds by phase
+  // (set-up, linearise, linear solves, candidate evaluation).
+  csm::DevBuf pg2_dev;
+  csm::PinnedBuf pg2_host;
+  double pg2_phase_seconds[4] = {0., 0., 0., 0.};
   ~csm_context() {
     for (csm_context* c : call_all) csm_context_destroy(c);
   }

@@ -1296,6 +1296,96 @@ int csm_comm_barrier(csm_comm* comm);
 int csm_comm_claim_open(csm_comm* comm, const char* root_host, int32_t port);
 int csm_comm_fetch_add(csm_comm* comm, int64_t key, int64_t delta, int64_t* old_value);
 
+/* ---- OptimizationProblem2D: the sparse pose-graph solve ----------------------
+ * The part of OptimizationProblem2D::Solve
+ * (mapping/internal/optimization/optimization_problem_2d.cc:240-409) built from
+ * submaps, nodes and constraints, as a flat problem: V vertices of (x, y,
+ * angle) and E edges, each the SPA cost of one observed relative pose
+ * (ComputeUnscaledError and ScaleError, cost_functions/cost_helpers_impl.h:28-56,
+ * the angle through NormalizeAngleDifference, common/math.h). Landmarks,
+ * fixed-frame poses, IMU and the time interpolation of odometry are not part
+ * of it; an odometry term is one more edge. */
+#define CSM_POSE_GRAPH2D_LOSS_NONE 0  /* nullptr loss (INTRA_SUBMAP, :337-347) */
+#define CSM_POSE_GRAPH2D_LOSS_HUBER 1 /* ceres::HuberLoss(huber_scale) (INTER_SUBMAP, :289-298) */
+#define CSM_POSE_GRAPH2D_MAX_VERTICES (1 << 22)
+#define CSM_POSE_GRAPH2D_MAX_EDGES (1 << 26)
+#define CSM_POSE_GRAPH2D_MAX_CG_ITERATIONS (1 << 16)
+#define CSM_POSE_GRAPH2D_MAX_LM_ITERATIONS (1 << 16)
+
+/* One residual block of :289-298 / :337-347: `end` observed from `start` as
+ * zbar (x, y, angle), Constraint::Pose's weights, and the loss. */
+typedef struct csm_pose_graph2d_edge {
+  int32_t start, end; /* vertex indices */
+  double zbar[3];
+  double translation_weight, rotation_weight;
+  int32_t loss; /* CSM_POSE_GRAPH2D_LOSS_* */
+  int32_t reserved;
+} csm_pose_graph2d_edge;
+
+/* optimization_problem_options (huber_scale) and its ceres_solver_options
+ * (configuration_files/pose_graph.lua: 10, 50 iterations, monotonic steps).
+ * The linear solve is a preconditioned conjugate-gradient iteration:
+ * max_cg_iterations is Ceres's max_linear_solver_iterations (500), and an
+ * iteration stops at |r| <= cg_relative_tolerance |r0|. */
+typedef struct csm_pose_graph2d_options {
+  double huber_scale;
+  int32_t max_num_iterations;
+  int32_t use_nonmonotonic_steps;
+  int32_t max_cg_iterations;
+  int32_t reserved;
+  double cg_relative_tolerance;
+} csm_pose_graph2d_options;
+/* 10, 50, 0, 500, 1e-8. */
+void csm_pose_graph2d_default_options(csm_pose_graph2d_options* out);
+
+/* ceres::Solver::Summary's termination, split by the tolerance that fired. */
+#define CSM_POSE_GRAPH2D_CONVERGENCE_GRADIENT 0
+#define CSM_POSE_GRAPH2D_CONVERGENCE_PARAMETER 1
+#define CSM_POSE_GRAPH2D_CONVERGENCE_FUNCTION 2
+#define CSM_POSE_GRAPH2D_NO_CONVERGENCE 3
+#define CSM_POSE_GRAPH2D_FAILURE 4
+typedef struct csm_pose_graph2d_summary {
+  double initial_cost, final_cost;
+  int32_t num_iterations;       /* Levenberg-Marquardt iterations after the first evaluation */
+  int32_t num_successful_steps; /* those whose step was accepted */
+  int32_t num_cg_iterations;    /* over all steps */
+  int32_t num_cg_capped_steps;  /* steps whose linear solve ran into max_cg_iterations */
+  int32_t termination;          /* CSM_POSE_GRAPH2D_* above */
+  int32_t reserved;
+} csm_pose_graph2d_summary;
+
+/* The cost 1/2 sum rho(|r|^2) at `poses` (V x 3), and on request every edge's
+ * residual as the SPA cost function returns it (E x 3, before the loss) and
+ * the cost's gradient (V x 3, every vertex taken as variable). No solve. */
+int csm_pose_graph2d_evaluate(csm_context* ctx, const csm_pose_graph2d_options* options,
+                              const double* poses, int32_t num_vertices,
+                              const csm_pose_graph2d_edge* edges, int64_t num_edges, double* cost,
+                              double* residuals, double* gradient);
+
+/* ceres::Solve of :403-407 on the flat problem, with Ceres 1.13's trust-region
+ * minimizer and Levenberg-Marquardt strategy restated on the device and its
+ * defaults for everything `options` does not name. constant[v] != 0 is
+ * SetParameterBlockConstant (:272-277, :284-286); NULL: none. poses_inout
+ * receives the solution; constant vertices keep their bits. An edge between
+ * two constant vertices is no part of the minimisation; its cost is added to
+ * both reported costs (Ceres's fixed_cost). Two calls on the same input return
+ * the same bits.
+ * Before anything is enqueued: CSM_EINVAL for a null pointer, a non-finite
+ * pose, observation or weight, a vertex index outside [0, V), start == end, an
+ * unknown loss, a non-positive huber_scale, cg tolerance or iteration limit;
+ * CSM_ERANGE past CSM_POSE_GRAPH2D_MAX_*. num_edges == 0 and a problem whose
+ * vertices are all constant are successes that launch nothing: the poses stay,
+ * the summary reports CONVERGENCE_GRADIENT after 0 iterations and, since
+ * nothing was evaluated, costs of 0. */
+int csm_pose_graph2d_solve(csm_context* ctx, const csm_pose_graph2d_options* options,
+                           double* poses_inout, const uint8_t* constant, int32_t num_vertices,
+                           const csm_pose_graph2d_edge* edges, int64_t num_edges,
+                           csm_pose_graph2d_summary* summary);
+/* Host seconds of the context's last solve that reached the device, by phase:
+ * set-up (adjacency and upload), linearisations, linear solves, candidate
+ * evaluations. Each phase ends in a read-back, so the clock sees the device. */
+void csm_pose_graph2d_last_phase_seconds(csm_context* ctx, double out[4]);
+
 /* Human-readable text for a return code. */
 const char* csm_strerror(int code);
 
