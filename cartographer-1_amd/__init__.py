@@ -529,7 +529,21 @@ _SIGNATURES = {
                                             C.c_int32, C.c_double, C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(C.c_int32)]),
-    "csm_tsdf_plan_scan": (C.c_int, [C.POINTER(TSDFInserterOptions), C.POINTER(C.c_float),
+    "csm_ceres2d_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CeresOptions2D),
+                                       C.POINTER(C.c_double), C.c_double, C.POINTER(Pose2D),
+                                       C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "csm_ceres2d_evaluate_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CeresOptions2D),
+                                            C.POINTER(C.c_double), C.c_double, C.POINTER(Pose2D),
+                                            C.POINTER(C.c_float), C.c_int32,
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double)]),
+    "csm_ceres3d_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Node3D),
+                                       C.POINTER(CeresOptions3D), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(Pose3D),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double)]),
+    "csm_tsdf_plan_scan":(C.c_int, [C.POINTER(TSDFInserterOptions), C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.POINTER(C.c_uint8)]),
@@ -1675,6 +1689,30 @@ def ceres_tsdf_evaluate(matcher: FastCorrelativeScanMatcher2D, point_cloud,
     return bool(valid.value), res[:n], jac[:n]
 
 
+def ceres_evaluate(grid_or_matcher, point_cloud, options: "CeresOptions2D", target, pose,
+                   context: Optional[Context] = None):
+    """csm_ceres2d_evaluate / csm_ceres2d_evaluate_grid (visible for testing):
+    the refinement's whole cost at ``pose`` on a probability matcher's handle
+    or on a DeviceProbabilityGrid, with the delta rows to ``target`` (x, y,
+    theta) -> (residuals (n + 3,), jacobian (n + 3, 3), sums (10,): sum r^2,
+    upper J^T J, J^T r as the solver's pass reduces them)."""
+    on_grid = isinstance(grid_or_matcher, DeviceProbabilityGrid)
+    ctx = context or grid_or_matcher.context
+    pts = _f32_points(point_cloud)
+    n = len(pts)
+    res = np.zeros(n + 3, np.float64)
+    jac = np.zeros((n + 3, 3), np.float64)
+    sums = np.zeros(10, np.float64)
+    txy = (C.c_double * 2)(float(target[0]), float(target[1]))
+    p = Pose2D(*[float(v) for v in pose])
+    name = "csm_ceres2d_evaluate_grid" if on_grid else "csm_ceres2d_evaluate"
+    _check(getattr(ctx._lib, name)(ctx.handle, grid_or_matcher.handle, C.byref(options), txy,
+                                   float(target[2]), C.byref(p), _ptr(pts, C.c_float), n,
+                                   _ptr(res, C.c_double), _ptr(jac, C.c_double),
+                                   _ptr(sums, C.c_double)), name)
+    return res, jac, sums
+
+
 # --------------------------------------------------------------------------
 # Synthetic world (bench / test inputs; not the matching path).
 
@@ -1741,7 +1779,8 @@ from .matching3d import (FastCorrelativeScanMatcher3D, FastCorrelativeScanMatche
                          HybridGrid, IntensityHybridGrid, NodeData3D, NodeSet3D, PAIR3_DTYPE,
                          RESULT3_DTYPE,
                          RealTimeCorrelativeScanMatcher3D, SyntheticWorld3D,
-                         ceres_intensity_evaluate_3d, ceres_refine_batch_3d, compute_histogram,
+                         ceres_evaluate_3d, ceres_intensity_evaluate_3d, ceres_refine_batch_3d,
+                         compute_histogram,
                          inserter3d_lookup_table, make_pairs_3d, match_batch_3d, rotate_histogram)
 
 

@@ -93,9 +93,12 @@ __device__ void Row(const RefineDesc& d, const float* pts, double scale, const d
 
 // Pass over the N occupied-space rows plus the 3 delta rows at pose x:
 // out[0] = sum r^2, and with jac, out[1..6] = Ju^T Ju (upper), out[7..9] = Ju^T r.
-template <bool kU16, bool kJac>
+// kRows (csm_ceres2d_evaluate only): also writes residual i to rows_r[i] and
+// its Jacobian row to rows_j[3 * i], n + 3 rows.
+template <bool kU16, bool kJac, bool kRows = false>
 __device__ void Pass(const RefineDesc& d, const float* pts, double scale, const RefineOpts& o,
-                     const double* x, double* out, double (*red)[10]) {
+                     const double* x, double* out, double (*red)[10], double* rows_r = nullptr,
+                     double* rows_j = nullptr) {
   const double s = sin(x[2]), c = cos(x[2]);
   double acc[10] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
   for (int i = threadIdx.x; i < d.n + 3; i += kRefineThreads) {
@@ -111,6 +114,10 @@ __device__ void Pass(const RefineDesc& d, const float* pts, double scale, const 
     } else {
       r = o.wr * (x[2] - d.initial[2]);
       J[2] = o.wr;
+    }
+    if (kRows) {
+      rows_r[i] = r;
+      for (int a = 0; a < 3; ++a) rows_j[3 * i + a] = J[a];
     }
     acc[0] += r * r;
     if (kJac) {
@@ -223,6 +230,24 @@ ceres2d_refine(const RefineDesc* __restrict__ items, const int32_t* __restrict__
   }
 }
 
+// csm_ceres2d_evaluate / _evaluate_grid: one Pass<kU16, true> at pose x, the
+// solver's own, which also writes its n + 3 rows; sums receives the 10
+// block-reduced sums as the solver reads them. d.initial[2] is the target
+// angle of the rotation delta row.
+template <bool kU16>
+__global__ void __launch_bounds__(kRefineThreads)
+ceres2d_evaluate(RefineDesc d, const float* __restrict__ pts, RefineOpts o, double x0, double x1,
+                 double x2, double* __restrict__ residuals, double* __restrict__ jacobian,
+                 double* __restrict__ sums) {
+  __shared__ double red[kRefineThreads / 64][10];
+  const double scale = o.occupied / sqrt(static_cast<double>(d.n));
+  const double x[3] = {x0, x1, x2};
+  double S[10];
+  Pass<kU16, true, true>(d, pts, scale, o, x, S, red, residuals, jacobian);
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 10; ++k) sums[k] = S[k];
+}
+
 // Uploads the items, runs each through its grid kind's kernel and reads the
 // results back in item order. u16: the items read device grids' uint16 cells.
 // The caller holds ctx->mu.
@@ -311,6 +336,43 @@ void FillSingleItem(const csm_map_limits& limits, const double target_xy[2],
   d->initial[2] = initial->theta;
   d->target[0] = target_xy[0];
   d->target[1] = target_xy[1];
+}
+
+// The evaluate entries' launch and read-back; the cloud is in ctx->cr_points
+// and the caller holds ctx->mu.
+int RunEvaluate2d(csm_context* ctx, const RefineDesc& d, bool u16,
+                  const csm_ceres2d_options* options, const csm_pose2d* pose, double* residuals,
+                  double* jacobian, double* sums) {
+  const size_t rows = static_cast<size_t>(d.n) + 3;
+  int rc;
+  if ((rc = ctx->cr_out.Reserve(sizeof(double) * (4 * rows + 10)))) return rc;
+  const RefineOpts o{options->occupied_space_weight, options->translation_weight,
+                     options->rotation_weight, options->max_num_iterations,
+                     options->use_nonmonotonic_steps ? 1 : 0};
+  hipStream_t st = ctx->stream;
+  double* dres = ctx->cr_out.as<double>();
+  double* djac = dres + rows;
+  double* dsums = djac + 3 * rows;
+  if (u16)
+    hipLaunchKernelGGL(ceres2d_evaluate<true>, dim3(1), dim3(kRefineThreads), 0, st, d,
+                       ctx->cr_points.as<float>(), o, pose->x, pose->y, pose->theta, dres, djac,
+                       dsums);
+  else
+    hipLaunchKernelGGL(ceres2d_evaluate<false>, dim3(1), dim3(kRefineThreads), 0, st, d,
+                       ctx->cr_points.as<float>(), o, pose->x, pose->y, pose->theta, dres, djac,
+                       dsums);
+  CSM_HIP(hipGetLastError());
+  CSM_HIP(hipMemcpyAsync(residuals, dres, sizeof(double) * rows, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipMemcpyAsync(jacobian, djac, sizeof(double) * 3 * rows, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipMemcpyAsync(sums, dsums, sizeof(double) * 10, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  return CSM_OK;
+}
+
+bool FinitePose2d(const double target_xy[2], double target_theta, const csm_pose2d* pose) {
+  return std::isfinite(target_xy[0]) && std::isfinite(target_xy[1]) &&
+         std::isfinite(target_theta) && std::isfinite(pose->x) && std::isfinite(pose->y) &&
+         std::isfinite(pose->theta);
 }
 
 }  // namespace
@@ -412,6 +474,53 @@ int csm_ceres2d_match_tsdf_grid(csm_context* ctx, const csm_ceres2d_options* opt
   desc[0].wtable = wtable;
   return RunRefine2d(ctx, desc, {1}, true, ctx->cr_points.as<float>(), options, pose_out,
                      iterations_out);
+}
+
+int csm_ceres2d_evaluate(csm_context* ctx, const csm_fast2d* m, const csm_ceres2d_options* options,
+                         const double target_xy[2], double target_theta, const csm_pose2d* pose,
+                         const float* points_xyz, int32_t n, double* residuals, double* jacobian,
+                         double* sums) {
+  using namespace csm;
+  if (!ctx || !m || !options || !target_xy || !pose || !residuals || !jacobian || !sums)
+    return CSM_EINVAL;
+  if (m->ctx != ctx || m->tsdf || !m->cost.ptr || CheckCeres2dOptions(options)) return CSM_EINVAL;
+  if (!FinitePose2d(target_xy, target_theta, pose)) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  int rc;
+  if ((rc = UploadSingleCloud(ctx, points_xyz, n))) return rc;
+  RefineDesc d{};
+  const csm_pose2d target{target_xy[0], target_xy[1], target_theta};
+  FillSingleItem(m->limits, target_xy, &target, n, &d);
+  d.cost = m->cost.as<float>();
+  d.max_cost = static_cast<double>(m->max_cc);
+  return RunEvaluate2d(ctx, d, false, options, pose, residuals, jacobian, sums);
+}
+
+int csm_ceres2d_evaluate_grid(csm_context* ctx, const csm_probability_grid* grid,
+                              const csm_ceres2d_options* options, const double target_xy[2],
+                              double target_theta, const csm_pose2d* pose, const float* points_xyz,
+                              int32_t n, double* residuals, double* jacobian, double* sums) {
+  using namespace csm;
+  if (!ctx || !grid || !options || !target_xy || !pose || !residuals || !jacobian || !sums)
+    return CSM_EINVAL;
+  if (grid->ctx != ctx || !grid->cells.ptr || CheckCeres2dOptions(options)) return CSM_EINVAL;
+  if (!FinitePose2d(target_xy, target_theta, pose)) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  int rc;
+  if ((rc = UploadSingleCloud(ctx, points_xyz, n))) return rc;
+  // The bounds and table of csm_ceres2d_match_grid.
+  const float min_cc = 1.f - (1.f - 0.1f), max_cc = 1.f - 0.1f;
+  const float* table;
+  if ((rc = EnsureValueTable(ctx, max_cc, min_cc, max_cc, &table))) return rc;
+  RefineDesc d{};
+  const csm_pose2d target{target_xy[0], target_xy[1], target_theta};
+  FillSingleItem(grid->limits, target_xy, &target, n, &d);
+  d.max_cost = static_cast<double>(max_cc);
+  d.cells16 = grid->cells.as<uint16_t>();
+  d.table = table;
+  return RunEvaluate2d(ctx, d, true, options, pose, residuals, jacobian, sums);
 }
 
 }  // extern "C"

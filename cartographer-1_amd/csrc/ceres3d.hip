@@ -247,11 +247,14 @@ __device__ __forceinline__ void Huber(double a, double s, double* rho, double* r
   }
 }
 
-template <bool kJac, bool kIntens>
+// kRows (csm_ceres3d_evaluate only): also writes residual i to rows_r[i] and
+// its tangent Jacobian row to rows_j[6 * i], n[0] + n[1] + 6 rows.
+template <bool kJac, bool kIntens, bool kRows = false>
 __device__ void Pass3(const Refine3Desc& d, const float* pts, const double* scale,
                       const Refine3Opts& o, const double* t, const double* q,
                       const double* target_inv, double* out, double (*red)[kSums],
-                      const IntensBlock3* ib, const float* values) {
+                      const IntensBlock3* ib, const float* values, double* rows_r = nullptr,
+                      double* rows_j = nullptr) {
   double acc[kSums], acc2[kIntens ? kSums : 1];
   for (int k = 0; k < kSums; ++k) acc[k] = 0.;
   if (kIntens)
@@ -305,6 +308,10 @@ __device__ void Pass3(const Refine3Desc& d, const float* pts, const double* scal
         for (int m = 0; m < 4; ++m) s += o.wr * M[a][m] * L[3 * m + c];
         j[3 + c] = s;
       }
+    }
+    if (kRows) {
+      rows_r[i] = r;
+      for (int a = 0; a < 6; ++a) rows_j[6 * i + a] = j[a];
     }
     Accumulate(acc, r, j, kJac);
   }
@@ -460,6 +467,28 @@ ceres3d_refine(const Refine3Desc* __restrict__ items, const float* __restrict__ 
     for (int a = 0; a < 4; ++a) out[7 * blockIdx.x + 3 + a] = best_q[a];
     if (out_iters) out_iters[blockIdx.x] = iter;
   }
+}
+
+// csm_ceres3d_evaluate: one Pass3<true, false> at the pose (d.t, d.q), the
+// plain solver's own, which also writes its rows; sums receives the kSums
+// block-reduced sums as the solver reads them. The rotation delta is taken to
+// target_q, which the solver sets to its initial rotation.
+struct Quat3 {
+  double v[4];
+};
+__global__ void __launch_bounds__(kR3Threads)
+ceres3d_evaluate(Refine3Desc d, const float* __restrict__ points, Refine3Opts o, Quat3 target_q,
+                 double* __restrict__ residuals, double* __restrict__ jacobian,
+                 double* __restrict__ sums) {
+  __shared__ double red[kR3Threads / 64][kSums];
+  const double scale[2] = {o.w0 / sqrt(static_cast<double>(d.n[0])),
+                           o.w1 / sqrt(static_cast<double>(d.n[1]))};
+  const double target_inv[4] = {target_q.v[0], -target_q.v[1], -target_q.v[2], -target_q.v[3]};
+  double S[kSums];
+  Pass3<true, false, true>(d, points, scale, o, d.t, d.q, target_inv, S, red, nullptr, nullptr,
+                           residuals, jacobian);
+  if (threadIdx.x == 0)
+    for (int k = 0; k < kSums; ++k) sums[k] = S[k];
 }
 
 // Test-visible lookups on a device grid (csm_hybrid_grid_get_probability /
@@ -743,6 +772,77 @@ int csm_ceres3d_intensity_evaluate(const csm_intensity_grid* grid, const float* 
   CSM_HIP(hipMemcpyAsync(residuals, dout.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
   CSM_HIP(hipMemcpyAsync(jacobian, dout.as<double>() + n, sizeof(double) * 6 * n,
                          hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  return CSM_OK;
+}
+
+int csm_ceres3d_evaluate(csm_context* ctx, const csm_hybrid_grid* high, const csm_hybrid_grid* low,
+                         const csm_node3d* node, const csm_ceres3d_options* options,
+                         const double target_translation[3], const double target_rotation[4],
+                         const csm_pose3d* pose, double* residuals, double* jacobian,
+                         double* sums) {
+  using namespace csm;
+  if (!ctx || !high || !low || !node || !options || !target_translation || !target_rotation ||
+      !pose || !residuals || !jacobian || !sums)
+    return CSM_EINVAL;
+  if (!(options->occupied_space_weight_0 > 0.) || !(options->occupied_space_weight_1 > 0.) ||
+      !(options->translation_weight > 0.) || !(options->rotation_weight > 0.))
+    return CSM_EINVAL;
+  const int32_t n0 = node->num_high_resolution, n1 = node->num_low_resolution;
+  if (n0 <= 0 || n1 <= 0 || !node->high_resolution_xyz || !node->low_resolution_xyz)
+    return CSM_EINVAL;
+  const csm_hybrid_grid* g[2] = {high, low};
+  Refine3Desc d{};
+  for (int k = 0; k < 2; ++k) {
+    if (!g[k]->ctx || g[k]->ctx->device != ctx->device || !g[k]->prob.ptr) return CSM_EINVAL;
+    d.grid[k] = GridView3{g[k]->prob.as<float>(), g[k]->brick, g[k]->resolution};
+  }
+  d.offset[0] = 0;
+  d.offset[1] = n0;
+  d.n[0] = n0;
+  d.n[1] = n1;
+  Quat3 tq;
+  for (int a = 0; a < 3; ++a) {
+    d.t[a] = pose->t[a];
+    d.target[a] = target_translation[a];
+    if (!std::isfinite(d.t[a]) || !std::isfinite(d.target[a])) return CSM_EINVAL;
+  }
+  for (int a = 0; a < 4; ++a) {
+    d.q[a] = pose->q[a];
+    tq.v[a] = target_rotation[a];
+    if (!std::isfinite(d.q[a]) || !std::isfinite(tq.v[a])) return CSM_EINVAL;
+  }
+  const size_t total = static_cast<size_t>(n0) + static_cast<size_t>(n1);
+  std::vector<float> pts(3 * total);
+  std::memcpy(pts.data(), node->high_resolution_xyz, sizeof(float) * 3 * n0);
+  std::memcpy(pts.data() + 3 * static_cast<size_t>(n0), node->low_resolution_xyz,
+              sizeof(float) * 3 * n1);
+  for (float v : pts)
+    if (!std::isfinite(v)) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return CSM_EHIP;
+  int rc;
+  const size_t rows = total + 6;
+  if ((rc = ctx->cr3_points.Reserve(sizeof(float) * pts.size())) ||
+      (rc = ctx->cr3_out.Reserve(sizeof(double) * (7 * rows + kSums))))
+    return rc;
+  hipStream_t st = ctx->stream;
+  for (int k = 0; k < 2; ++k)
+    if ((rc = WaitBuilt(g[k]->ready, g[k]->ctx->stream, st))) return rc;
+  CSM_HIP(hipMemcpyAsync(ctx->cr3_points.ptr, pts.data(), sizeof(float) * pts.size(),
+                         hipMemcpyHostToDevice, st));
+  const Refine3Opts o{options->occupied_space_weight_0, options->occupied_space_weight_1,
+                      options->translation_weight, options->rotation_weight,
+                      options->max_num_iterations, options->use_nonmonotonic_steps ? 1 : 0};
+  double* dres = ctx->cr3_out.as<double>();
+  double* djac = dres + rows;
+  double* dsums = djac + 6 * rows;
+  hipLaunchKernelGGL(ceres3d_evaluate, dim3(1), dim3(kR3Threads), 0, st, d,
+                     ctx->cr3_points.as<float>(), o, tq, dres, djac, dsums);
+  CSM_HIP(hipGetLastError());
+  CSM_HIP(hipMemcpyAsync(residuals, dres, sizeof(double) * rows, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipMemcpyAsync(jacobian, djac, sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipMemcpyAsync(sums, dsums, sizeof(double) * kSums, hipMemcpyDeviceToHost, st));
   CSM_HIP(hipStreamSynchronize(st));
   return CSM_OK;
 }

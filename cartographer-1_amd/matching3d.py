@@ -693,6 +693,29 @@ def ceres_intensity_evaluate_3d(grid: IntensityHybridGrid, points, intensities, 
     return r, jac
 
 
+def ceres_evaluate_3d(high: HybridGrid, low: HybridGrid, node: NodeData3D, options, target,
+                      pose, context: Optional[Context] = None):
+    """csm_ceres3d_evaluate (visible for testing): the refinement's whole cost
+    at ``pose`` ((t), (w, x, y, z)) with the delta rows to ``target`` ((t),
+    (w, x, y, z)) -> (residuals (N,), Jacobian (N, 6) in the tangent space,
+    sums (28,): sum r^2, upper J^T J, J^T r as the solver's pass reduces them),
+    N = high + low points + 6."""
+    ctx = context or high.context
+    cnode = node.to_c()
+    rows = cnode.num_high_resolution + cnode.num_low_resolution + 6
+    r = np.zeros(rows, np.float64)
+    jac = np.zeros((rows, 6), np.float64)
+    sums = np.zeros(28, np.float64)
+    tt = (C.c_double * 3)(*[float(v) for v in target[0]])
+    tq = (C.c_double * 4)(*[float(v) for v in target[1]])
+    p = _pose(pose)
+    _check(ctx._lib.csm_ceres3d_evaluate(ctx.handle, high.handle, low.handle, C.byref(cnode),
+                                         C.byref(options), tt, tq, C.byref(p),
+                                         _ptr(r, C.c_double), _ptr(jac, C.c_double),
+                                         _ptr(sums, C.c_double)), "csm_ceres3d_evaluate")
+    return r, jac, sums
+
+
 # --------------------------------------------------------------------------
 # Synthetic 3D world (bench / test inputs; not the matching path).
 

@@ -560,6 +560,21 @@ int csm_ceres2d_tsdf_evaluate(csm_context* ctx, const csm_fast2d* tsdf_handle,
                               const double pose[3], double* residuals, double* jacobian,
                               int32_t* valid);
 
+/* Test-visible: the whole cost of one probability item at `pose`, through the
+ * pass over the rows that the refinement kernel runs each iteration (the same
+ * device function, which here also writes its rows). The n occupied-space
+ * rows of OccupiedSpaceCostFunction2D with weight occupied_space_weight /
+ * sqrt(n), then the two translation delta rows to target_xy and the rotation
+ * delta row to target_theta (the refinement's initial angle): residuals[n + 3]
+ * and the row-major (n + 3) x 3 Jacobian by (x, y, theta). sums[10] are the
+ * pass's block-reduced sums as the solver reads them: sum r^2, the upper
+ * triangle of J^T J by rows (6), J^T r (3). n >= 1 finite points; the
+ * iteration fields of options are not used. A TSDF handle: CSM_EINVAL. */
+int csm_ceres2d_evaluate(csm_context* ctx, const csm_fast2d* probability_handle,
+                         const csm_ceres2d_options* options, const double target_xy[2],
+                         double target_theta, const csm_pose2d* pose, const float* points_xyz,
+                         int32_t n, double* residuals, double* jacobian, double* sums);
+
 /* CeresScanMatcher3D refinement (ConstraintBuilder3D::ComputeConstraint,
  * constraint_builder_3d.cc:264-275; ceres_scan_matcher_3d.cc:84-160): the
  * match pose is refined against the submap's high- and low-resolution
@@ -637,6 +652,24 @@ int csm_ceres3d_intensity_evaluate(const csm_intensity_grid* grid, const float* 
                                    const float* intensities, int32_t n, const double pose[7],
                                    double scaling_factor, float intensity_threshold,
                                    double* residuals, double* jacobian);
+
+/* Test-visible, like csm_ceres2d_evaluate: the whole cost of one
+ * csm_ceres3d_refine_batch item at `pose`, through the pass over the rows that
+ * the kernel without an intensity block runs each iteration. The node's
+ * high-resolution rows in `high`, its low-resolution rows in `low`, three
+ * translation delta rows to target_translation and three rotation delta rows
+ * vec(target_rotation^-1 * q) (the refinement takes its initial rotation as
+ * target_rotation): with N = num_high_resolution + num_low_resolution + 6,
+ * residuals[N] and the row-major N x 6 Jacobian in the tangent space
+ * (translation, then the rotation increment of
+ * ceres::QuaternionParameterization). sums[28]: sum r^2, the upper triangle of
+ * J^T J by rows (21), J^T r (6). Both clouds hold at least one finite point;
+ * the iteration fields of options are not used. */
+int csm_ceres3d_evaluate(csm_context* ctx, const csm_hybrid_grid* high, const csm_hybrid_grid* low,
+                         const csm_node3d* node, const csm_ceres3d_options* options,
+                         const double target_translation[3], const double target_rotation[4],
+                         const csm_pose3d* pose, double* residuals, double* jacobian,
+                         double* sums);
 
 /* ---- submap grid formats ---------------------------------------------------
  * Submap2D::Finish (submap_2d.cc:146-150) crops a finished submap's grid to
@@ -863,6 +896,14 @@ int csm_ceres2d_match_tsdf_grid(csm_context* ctx, const csm_ceres2d_options* opt
                                 const csm_tsdf_grid* grid, const double target_xy[2],
                                 const csm_pose2d* initial, const float* points_xyz, int32_t n,
                                 csm_pose2d* pose_out, int32_t* iterations_out);
+
+/* Test-visible: csm_ceres2d_evaluate on a device-resident grid of ctx, through
+ * the instantiation csm_ceres2d_match_grid runs (uint16 cells through the
+ * value table). */
+int csm_ceres2d_evaluate_grid(csm_context* ctx, const csm_probability_grid* grid,
+                              const csm_ceres2d_options* options, const double target_xy[2],
+                              double target_theta, const csm_pose2d* pose, const float* points_xyz,
+                              int32_t n, double* residuals, double* jacobian, double* sums);
 
 /* Test-visible and host-only, like csm_inserter2d_lookup_table: the per-ray
  * plan of one Insert that the device consumes. order[k] is the index of the

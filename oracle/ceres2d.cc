@@ -314,4 +314,31 @@ int32_t oracle_ceres2d_match(double res, double max_x, double max_y, int32_t nx,
   return CeresMatch2D(l, c, min_cc, max_cc, o, target, initial, pts, out, nullptr);
 }
 
+// The rows of Evaluate above, which CeresMatch2D minimises: residuals[n + 3]
+// and the row-major (n + 3) x 3 Jacobian at `pose`. weights: occupied,
+// translation, rotation. target: (x, y, theta). Returns the cost.
+double oracle_ceres2d_evaluate(double res, double max_x, double max_y, int32_t nx, int32_t ny,
+                               const uint16_t* cells, float min_cc, float max_cc,
+                               const double* weights, const double* target, const double* pose,
+                               const float* xyz, int32_t n, double* residuals, double* jacobian) {
+  MapLimits l;
+  l.resolution = res;
+  l.max_x = max_x;
+  l.max_y = max_y;
+  l.cells = CellLimits{nx, ny};
+  const std::vector<uint16_t> c(cells, cells + static_cast<size_t>(nx) * ny);
+  std::vector<Vec2d> pts(static_cast<size_t>(n));
+  for (int32_t i = 0; i < n; ++i)
+    pts[i] = Vec2d{static_cast<double>(xyz[3 * i]), static_cast<double>(xyz[3 * i + 1])};
+  const std::vector<float> table = MakeConversionTable(max_cc, min_cc, max_cc);
+  const CostGrid grid{l, &table, &c, static_cast<double>(max_cc)};
+  const Problem p{&grid, &pts, weights[0] / std::sqrt(static_cast<double>(n)),
+                  weights[1], weights[2], target[0], target[1], target[2]};
+  std::vector<double> r, J;
+  const double cost = Evaluate(p, pose, &r, &J);
+  std::copy(r.begin(), r.end(), residuals);
+  std::copy(J.begin(), J.end(), jacobian);
+  return cost;
+}
+
 }  // extern "C"

@@ -367,4 +367,34 @@ int32_t oracle_ceres3d_match(void* high, void* low, const float* high_xyz, int32
                       target, initial, initial + 3, out, out + 3, nullptr);
 }
 
+// The rows of Evaluate3 above, which CeresMatch3D minimises: residuals[N] and
+// the row-major N x 6 tangent-space Jacobian, N = nh + nl + 6, at pose (t[3],
+// q[4]). weights: w0, w1, wt, wr. target: t[3], then the rotation q[4] the
+// rotation delta is taken to. Returns the cost.
+double oracle_ceres3d_evaluate(void* high, void* low, const float* high_xyz, int32_t nh,
+                               const float* low_xyz, int32_t nl, const double* weights,
+                               const double* target, const double* pose, double* residuals,
+                               double* jacobian) {
+  std::vector<Vec3f> hc(static_cast<size_t>(nh)), lc(static_cast<size_t>(nl));
+  for (int32_t i = 0; i < nh; ++i) hc[i] = Vec3f{high_xyz[3 * i], high_xyz[3 * i + 1], high_xyz[3 * i + 2]};
+  for (int32_t i = 0; i < nl; ++i) lc[i] = Vec3f{low_xyz[3 * i], low_xyz[3 * i + 1], low_xyz[3 * i + 2]};
+  Problem3 p;
+  p.grid[0] = static_cast<HybridGrid*>(high);
+  p.grid[1] = static_cast<HybridGrid*>(low);
+  p.cloud[0] = &hc;
+  p.cloud[1] = &lc;
+  p.scale[0] = weights[0] / std::sqrt(static_cast<double>(nh));
+  p.scale[1] = weights[1] / std::sqrt(static_cast<double>(nl));
+  p.wt = weights[2];
+  p.wr = weights[3];
+  for (int a = 0; a < 3; ++a) p.target[a] = target[a];
+  p.target_inv[0] = target[3];
+  for (int a = 1; a < 4; ++a) p.target_inv[a] = -target[3 + a];
+  std::vector<double> r, J;
+  const double cost = Evaluate3(p, pose, pose + 3, &r, &J);
+  std::copy(r.begin(), r.end(), residuals);
+  std::copy(J.begin(), J.end(), jacobian);
+  return cost;
+}
+
 }  // extern "C"

@@ -543,6 +543,65 @@ def _o_ceres3d_match(self, high, low, high_cloud, low_cloud, options, target, in
 Oracle.ceres3d_match = _o_ceres3d_match
 
 
+def _rows_export(self, name, argtypes):
+    """The evaluate exports were added after the match entries; ensure_built
+    only builds a missing liboracle.so, so an older one may still be loaded."""
+    try:
+        f = getattr(self.lib, name)
+    except AttributeError:
+        raise RuntimeError(f"{ORACLE_PATH} has no {name}: it predates the row exports; rebuild "
+                           "the oracle (make -C oracle)") from None
+    f.restype, f.argtypes = D, argtypes
+    return f
+
+
+def _o_ceres2d_evaluate(self, limits, cells, weights, target, pose, cloud):
+    """The rows of oracle/ceres2d.cc's Evaluate at `pose`: (residuals (n + 3,),
+    Jacobian (n + 3, 3), cost). weights: (occupied, translation, rotation);
+    target: (x, y, theta)."""
+    f = _rows_export(self, "oracle_ceres2d_evaluate",
+                     [D, D, D, I32, I32, P(C.c_uint16), F, F, P(D), P(D), P(D), P(F), I32, P(D),
+                      P(D)])
+    f32 = np.float32
+    min_cc, max_cc = f32(1.0) - (f32(1.0) - f32(0.1)), f32(1.0) - f32(0.1)
+    cells = np.ascontiguousarray(cells, np.uint16)
+    pts = np.ascontiguousarray(cloud, np.float32).reshape(-1, 3)
+    w = np.asarray(weights, np.float64)[:3].copy()
+    t = np.asarray(target, np.float64).copy()
+    x = np.asarray(pose, np.float64).copy()
+    assert t.shape == (3,) and x.shape == (3,)
+    r = np.zeros(len(pts) + 3)
+    jac = np.zeros((len(pts) + 3, 3))
+    cost = f(limits[0], limits[1], limits[2], cells.shape[1], cells.shape[0],
+             _p(cells, C.c_uint16), float(min_cc), float(max_cc), _p(w, D), _p(t, D), _p(x, D),
+             _p(pts, F), len(pts), _p(r, D), _p(jac, D))
+    return r, jac, float(cost)
+
+
+def _o_ceres3d_evaluate(self, high, low, high_cloud, low_cloud, weights, target, pose):
+    """The rows of oracle/ceres3d.cc's Evaluate3 at `pose` ((t), (w, x, y, z)):
+    (residuals (N,), tangent-space Jacobian (N, 6), cost), N = points + 6.
+    weights: (w0, w1, translation, rotation); target: ((t), (w, x, y, z))."""
+    _o3_hgrid(self, 1.0)  # binds the 3D signatures
+    f = _rows_export(self, "oracle_ceres3d_evaluate",
+                     [VP, VP, P(F), I32, P(F), I32, P(D), P(D), P(D), P(D), P(D)])
+    hc = np.ascontiguousarray(high_cloud, np.float32).reshape(-1, 3)
+    lc = np.ascontiguousarray(low_cloud, np.float32).reshape(-1, 3)
+    w = np.asarray(weights, np.float64)[:4].copy()
+    t = _pose7(*target)
+    x = _pose7(*pose)
+    rows = len(hc) + len(lc) + 6
+    r = np.zeros(rows)
+    jac = np.zeros((rows, 6))
+    cost = f(high.h, low.h, _p(hc, F), len(hc), _p(lc, F), len(lc), _p(w, D), _p(t, D), _p(x, D),
+             _p(r, D), _p(jac, D))
+    return r, jac, float(cost)
+
+
+Oracle.ceres2d_evaluate = _o_ceres2d_evaluate
+Oracle.ceres3d_evaluate = _o_ceres3d_evaluate
+
+
 def _o_search_parameters(self, lin, ang, cloud, res):
     """SearchParameters(lin, ang, cloud, res) restated: (num_angular, step,
     num_scans, first scan's bounds)."""

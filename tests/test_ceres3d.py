@@ -5,7 +5,8 @@ Ceres is absent from this image: the oracle (oracle/ceres3d.cc) restates the
 cost (two OccupiedSpaceCostFunction3D blocks over InterpolatedGrid, the
 translation and rotation delta functors), the quaternion parameterization and
 Ceres 1.13's LM. Its analytic Jacobians are checked against finite
-differences of the same cost, and the restatement is pinned by the reference's
+differences of an independent long-double restatement of the same cost
+(test_ceres_rows_host.py), and the restatement is pinned by the reference's
 rotation_delta_cost_functor_3d_test.cc and the upstream
 ceres_scan_matcher_3d_test.cc (the fork's .bak copy; restated in
 oracle/ref_tests_3d.cc without its intensity block, which ConstraintBuilder3D
