@@ -281,6 +281,19 @@ class Pair3D(C.Structure):
                 ("min_score", C.c_float), ("node_pose", Pose3D), ("submap_pose", Pose3D)]
 
 
+class RotPair3D(C.Structure):
+    """csm_rot_pair3d: one record of csm_rotational_scores_batch."""
+    _fields_ = [("node_histogram", C.c_int32), ("submap_histogram", C.c_int32),
+                ("size", C.c_int32), ("window", C.c_int32), ("step", C.c_float),
+                ("yaw0", C.c_float), ("min_score", C.c_double)]
+
+
+class DiscreteScan3D(C.Structure):
+    """csm_discrete_scan3d: one kept yaw of csm_fast3d_discrete_scans."""
+    _fields_ = [("k", C.c_int32), ("rotational_score", C.c_float), ("q", C.c_float * 4),
+                ("n", C.c_float * 4), ("t", C.c_float * 3)]
+
+
 class PoseGraph2DEdge(C.Structure):
     """csm_pose_graph2d_edge: `end` observed from `start` as zbar (x, y, angle)."""
     _fields_ = [("start", C.c_int32), ("end", C.c_int32), ("zbar", C.c_double * 3),
@@ -410,7 +423,17 @@ _SIGNATURES = {
     "csm_fast3d_match_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
                                          C.POINTER(Node3D), C.c_int32, C.POINTER(Pair3D),
                                          C.c_int64, C.POINTER(Result3D)]),
-    "csm_voxel_filter": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64),
+    "csm_rotational_scores_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int64,
+                                              C.POINTER(RotPair3D), C.c_int32,
+                                              C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                              C.POINTER(C.c_int64)]),
+    "csm_fast3d_discrete_scans": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Node3D),
+                                            C.POINTER(Pair3D), C.POINTER(DiscreteScan3D),
+                                            C.c_int32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "csm_voxel_filter":(C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64),
                                    C.c_int32, C.c_float, C.POINTER(C.c_uint8),
                                    C.POINTER(C.c_int32)]),
     "csm_adaptive_voxel_filter": (C.c_int, [C.c_void_p, C.POINTER(C.c_float),
@@ -1779,9 +1802,11 @@ from .matching3d import (FastCorrelativeScanMatcher3D, FastCorrelativeScanMatche
                          HybridGrid, IntensityHybridGrid, NodeData3D, NodeSet3D, PAIR3_DTYPE,
                          RESULT3_DTYPE,
                          RealTimeCorrelativeScanMatcher3D, SyntheticWorld3D,
+                         DISCRETE_SCAN3_DTYPE, ROT_PAIR3_DTYPE,
                          ceres_evaluate_3d, ceres_intensity_evaluate_3d, ceres_refine_batch_3d,
-                         compute_histogram,
-                         inserter3d_lookup_table, make_pairs_3d, match_batch_3d, rotate_histogram)
+                         compute_histogram, discrete_scans_3d,
+                         inserter3d_lookup_table, make_pairs_3d, match_batch_3d, rotate_histogram,
+                         rotational_scores_batch)
 
 
 # --------------------------------------------------------------------------

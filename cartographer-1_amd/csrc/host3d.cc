@@ -1139,6 +1139,11 @@ float MaxNorm(const csm_node3d& node) {
 
 void PreparePair(const csm_fast3d* m, const csm_node3d& node, const csm_pair3d& p, float max_norm,
                  PairPrep* out) {
+  if (node.histogram_size != static_cast<int32_t>(m->histogram.size()) ||
+      node.histogram_size > kMaxHistogram || (node.histogram_size > 0 && !node.histogram)) {
+    out->status = CSM_EINVAL;
+    return;
+  }
   const csm_fast3d_options& o = m->options;
   const float res = m->resolution;
   const int n = node.num_high_resolution;
@@ -1749,6 +1754,224 @@ namespace {
 // with the check before the search.
 constexpr int kRetryWithYawFlags = 0x7fff0001;
 
+// Whether a pass that deferred its flag check runs again with the check
+// before the search; CSM_YAW_FORCE_RETRY (tests) takes the retry path on
+// every deferred pass.
+bool RetryWithYawFlags(unsigned nflag, bool defer_flags) {
+  return nflag != 0 || (defer_flags && std::getenv("CSM_YAW_FORCE_RETRY"));
+}
+
+// What the rotational stage leaves behind: per record its {offset, count} in
+// the compacted lists, and where the device keeps every score (at each
+// record's `out`) and the passing (k, score) lists (ctx->f3_scores).
+struct RotRun {
+  std::vector<int2> range;
+  unsigned kept = 0;
+  const float* scores = nullptr;
+  const int32_t* k = nullptr;
+  const float* s = nullptr;
+};
+
+// rot_scores then yaw_compact over `rp` on ctx->stream; `total` scores in
+// all, the longest record `max_yaws`. Waits for the ranges and the count.
+int RunRotScores(csm_context* ctx, const std::vector<RotPair3Host>& rp, const std::vector<float>& hists,
+                 int64_t total, int max_yaws, RotRun* run) {
+  run->range.assign(rp.size(), int2{0, 0});
+  if (rp.empty()) return CSM_OK;
+  int rc;
+  hipStream_t st = ctx->stream;
+  if ((rc = ctx->f3_items.Reserve(sizeof(RotPair3Host) * rp.size() +
+                                  sizeof(float) * std::max<size_t>(hists.size(), 1))))
+    return rc;
+  // [scores | passing k | passing scores | ranges | cursor]
+  if ((rc = ctx->f3_scores.Reserve(12 * total + sizeof(int2) * rp.size() + 16))) return rc;
+  float* dscores = ctx->f3_scores.as<float>();
+  int32_t* dk = reinterpret_cast<int32_t*>(dscores + total);
+  float* ds = reinterpret_cast<float*>(dk + total);
+  int2* drange = reinterpret_cast<int2*>(ds + total + (total & 1));
+  unsigned* dcursor = reinterpret_cast<unsigned*>(drange + rp.size());
+  RotPair3Host* drp = ctx->f3_items.as<RotPair3Host>();
+  float* dh = reinterpret_cast<float*>(drp + rp.size());
+  // Pinned staging both ways, one copy each: the pair records and
+  // histograms up (contiguous on the device), the ranges and the cursor
+  // (adjacent) back. Pageable copies cost ~25 us each, which dominated
+  // a single call's latency (profiles/r6h/).
+  const size_t up_bytes = sizeof(RotPair3Host) * rp.size() + sizeof(float) * hists.size();
+  const size_t rb_bytes = sizeof(int2) * rp.size() + sizeof(unsigned);
+  if ((rc = ctx->f3_up.Reserve(up_bytes)) || (rc = ctx->f3_rb.Reserve(rb_bytes))) return rc;
+  std::memcpy(ctx->f3_up.ptr, rp.data(), sizeof(RotPair3Host) * rp.size());
+  if (!hists.empty())
+    std::memcpy(ctx->f3_up.as<char>() + sizeof(RotPair3Host) * rp.size(), hists.data(),
+                sizeof(float) * hists.size());
+  CSM_HIP(hipMemcpyAsync(drp, ctx->f3_up.ptr, up_bytes, hipMemcpyHostToDevice, st));
+  CSM_HIP(hipMemsetAsync(dcursor, 0, sizeof(unsigned), st));
+  CSM_HIP(LaunchRotScores(drp, static_cast<int>(rp.size()), max_yaws, dh, dscores, st));
+  CSM_HIP(LaunchYawCompact(drp, static_cast<int>(rp.size()), dscores, dcursor, drange, dk, ds, st));
+  CSM_HIP(hipMemcpyAsync(ctx->f3_rb.ptr, drange, rb_bytes, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  std::memcpy(run->range.data(), ctx->f3_rb.ptr, sizeof(int2) * rp.size());
+  std::memcpy(&run->kept, ctx->f3_rb.as<char>() + sizeof(int2) * rp.size(), sizeof(unsigned));
+  // The passing (k, score) lists stay on the device (f3_scores) for the
+  // yaw_build kernel; the host reads them back with the results.
+  run->scores = dscores;
+  run->k = dk;
+  run->s = ds;
+  return CSM_OK;
+}
+
+// Phase 2 (device): rotational scores of every (pair, yaw) of the pairs that
+// phase 1 prepared; the passing yaws (k, score) per pair stay compacted on the
+// device. rp_pair[j]: the input pair of record j.
+int RotationalPhase(csm_context* ctx, csm_fast3d* const* submaps, int32_t num_submaps,
+                    const csm_node3d* nodes, int32_t num_nodes, const csm_pair3d* pairs,
+                    int64_t num_pairs, const csm_result3d* results, const std::vector<PairPrep>& prep,
+                    std::vector<int64_t>* rp_pair, RotRun* run) {
+  std::vector<float> hists;
+  std::vector<int64_t> node_hist(num_nodes, -1), sub_hist(num_submaps, -1);
+  std::vector<RotPair3Host> rp;
+  int64_t total = 0;
+  int max_yaws = 0;
+  for (int64_t i = 0; i < num_pairs; ++i) {
+    if (results[i].status != CSM_NO_MATCH || prep[i].status != CSM_OK) continue;
+    const csm_pair3d& p = pairs[i];
+    if (node_hist[p.node] < 0) {
+      node_hist[p.node] = static_cast<int64_t>(hists.size());
+      const csm_node3d& nd = nodes[p.node];
+      hists.insert(hists.end(), nd.histogram, nd.histogram + nd.histogram_size);
+    }
+    if (sub_hist[p.submap] < 0) {
+      sub_hist[p.submap] = static_cast<int64_t>(hists.size());
+      const auto& h = submaps[p.submap]->histogram;
+      hists.insert(hists.end(), h.begin(), h.end());
+    }
+    RotPair3Host r{};
+    r.node_hist = static_cast<int32_t>(node_hist[p.node]);
+    r.submap_hist = static_cast<int32_t>(sub_hist[p.submap]);
+    r.size = nodes[p.node].histogram_size;
+    r.window = prep[i].angular_window;
+    r.step = prep[i].astep;
+    r.yaw0 = prep[i].yaw0;
+    r.out = total;
+    r.min_score = submaps[p.submap]->options.min_rotational_score;
+    total += 2 * r.window + 1;
+    max_yaws = std::max(max_yaws, 2 * r.window + 1);
+    rp.push_back(r);
+    rp_pair->push_back(i);
+  }
+  return RunRotScores(ctx, rp, hists, total, max_yaws, run);
+}
+
+// Each searched pair's discrete-scan count, where its passing yaws start in
+// the compacted lists, and its leaf key layout.
+void TakeYawRanges(const std::vector<int64_t>& rp_pair, const RotRun& run, std::vector<PairPrep>* prep,
+                   std::vector<int64_t>* yaw_src) {
+  for (size_t j = 0; j < rp_pair.size(); ++j) {
+    const int64_t i = rp_pair[j];
+    (*prep)[i].num_yaws = run.range[j].y;
+    (*yaw_src)[i] = run.range[j].x;
+    KeyBits(run.range[j].y, &(*prep)[i]);
+  }
+}
+
+// Phase 3 (device): the discrete-scan poses of the yaws that pass, built into
+// ctx->f3_yaws from the compacted (k, score) lists; the few yaws whose float
+// sin / cos rounding the device cannot decide are rebuilt here with libm and
+// patched in, unless `defer_flags` leaves the flag check to the caller
+// (*dflag_count: the device's count). The build records are staged in
+// ctx->f3_up at `stage_at` (reserved by the caller, sizeof(YawBuild3) per
+// device pair); `ny` yaws in all.
+int YawBuildPhase(csm_context* ctx, const std::vector<Pair3Desc>& pdesc,
+                  const std::vector<int64_t>& pair_of, const std::vector<PairPrep>& prep,
+                  const std::vector<int64_t>& yaw_src, int ny, const RotRun& run, size_t stage_at,
+                  bool defer_flags, unsigned** dflag_count) {
+  const int np = static_cast<int>(pdesc.size());
+  hipStream_t st = ctx->stream;
+  const int32_t* dev_k = run.k;
+  const float* dev_s = run.s;
+  const unsigned kept = run.kept;
+  int rc;
+  std::vector<YawBuild3> yb(static_cast<size_t>(np));
+  for (int dp = 0; dp < np; ++dp) {
+    const PairPrep& pr = prep[pair_of[dp]];
+    YawBuild3& b = yb[dp];
+    b.siw = pr.submap_inv.w;
+    b.six = pr.submap_inv.x;
+    b.siy = pr.submap_inv.y;
+    b.siz = pr.submap_inv.z;
+    b.nqw = pr.node_q.w;
+    b.nqx = pr.node_q.x;
+    b.nqy = pr.node_q.y;
+    b.nqz = pr.node_q.z;
+    b.tx = pr.node_to_submap.t.x;
+    b.ty = pr.node_to_submap.t.y;
+    b.tz = pr.node_to_submap.t.z;
+    b.astep = pr.astep;
+    b.window = pr.angular_window;
+    b.src = static_cast<int32_t>(yaw_src[pair_of[dp]]);
+    b.yaw_begin = pdesc[dp].yaw_begin;
+    b.num = pdesc[dp].num_yaws;
+  }
+  // f3_items held the rotational-score inputs, which are consumed (synced).
+  // Layout [flag count (16 B) | flags | build records]: the count and the
+  // first 64 flags come back in one pinned copy.
+  if ((rc = ctx->f3_items.Reserve(16 + sizeof(YawFlag3) * kYawFlagCap + sizeof(YawBuild3) * np)))
+    return rc;
+  *dflag_count = ctx->f3_items.as<unsigned>();
+  YawFlag3* dflags = reinterpret_cast<YawFlag3*>(ctx->f3_items.as<char>() + 16);
+  YawBuild3* dyb = reinterpret_cast<YawBuild3*>(dflags + kYawFlagCap);
+  std::memcpy(ctx->f3_up.as<char>() + stage_at, yb.data(), sizeof(YawBuild3) * np);
+  CSM_HIP(hipMemcpyAsync(dyb, ctx->f3_up.as<char>() + stage_at, sizeof(YawBuild3) * np,
+                         hipMemcpyHostToDevice, st));
+  CSM_HIP(hipMemsetAsync(*dflag_count, 0, sizeof(unsigned), st));
+  CSM_HIP(LaunchYawBuild(dyb, np, dev_k, dev_s, ctx->f3_yaws.as<Yaw3Desc>(), *dflag_count, dflags,
+                         st));
+  if (defer_flags) return CSM_OK;
+  unsigned nflag = 0;
+  YawFlag3 flags[64];
+  const size_t flag_rb = 16 + sizeof(flags);
+  if ((rc = ctx->f3_rb.Reserve(flag_rb))) return rc;
+  CSM_HIP(hipMemcpyAsync(ctx->f3_rb.ptr, *dflag_count, flag_rb, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  std::memcpy(&nflag, ctx->f3_rb.ptr, sizeof(unsigned));
+  std::memcpy(flags, ctx->f3_rb.as<char>() + 16, sizeof(flags));
+  // CSM_YAW_HOST_BUILD (tests): the host path for every yaw.
+  if (nflag > static_cast<unsigned>(kYawFlagCap) || std::getenv("CSM_YAW_HOST_BUILD")) {
+    // More undecided roundings than the flag list holds (~2^-15 per value,
+    // so only in batches of ~10^8 yaws): rebuild every yaw on the host.
+    std::vector<int32_t> hk(std::max(kept, 1u));
+    std::vector<float> hs(std::max(kept, 1u));
+    CSM_HIP(hipMemcpyAsync(hk.data(), dev_k, sizeof(int32_t) * kept, hipMemcpyDeviceToHost, st));
+    CSM_HIP(hipMemcpyAsync(hs.data(), dev_s, sizeof(float) * kept, hipMemcpyDeviceToHost, st));
+    CSM_HIP(hipStreamSynchronize(st));
+    if ((rc = ctx->f3_host_yaws.Reserve(sizeof(Yaw3Desc) * ny))) return rc;
+    Yaw3Desc* hy = ctx->f3_host_yaws.as<Yaw3Desc>();
+    ParallelPairs(np, [&](int64_t dp) {
+      const int64_t i = pair_of[dp];
+      BuildYaws(hk.data() + yaw_src[i], hs.data() + yaw_src[i], prep[i].num_yaws,
+                static_cast<int32_t>(dp), prep[i], hy + pdesc[dp].yaw_begin);
+    });
+    CSM_HIP(hipMemcpyAsync(ctx->f3_yaws.ptr, hy, sizeof(Yaw3Desc) * ny, hipMemcpyHostToDevice, st));
+    nflag = 0;
+  }
+  if (nflag > 0) {
+    std::vector<YawFlag3> all(flags, flags + std::min<unsigned>(nflag, 64));
+    if (nflag > 64) {
+      all.resize(nflag);
+      CSM_HIP(hipMemcpy(all.data(), dflags, sizeof(YawFlag3) * nflag, hipMemcpyDeviceToHost));
+    }
+    if ((rc = ctx->f3_host_yaws.Reserve(sizeof(Yaw3Desc) * all.size()))) return rc;
+    Yaw3Desc* hy = ctx->f3_host_yaws.as<Yaw3Desc>();
+    for (size_t f = 0; f < all.size(); ++f) {
+      const YawFlag3& fl = all[f];
+      BuildYaws(&fl.k, &fl.score, 1, fl.dp, prep[pair_of[fl.dp]], &hy[f]);
+      hy[f].yaw_id = fl.j;
+      CSM_HIP(hipMemcpyAsync(ctx->f3_yaws.as<Yaw3Desc>() + pdesc[fl.dp].yaw_begin + fl.j, &hy[f],
+                             sizeof(Yaw3Desc), hipMemcpyHostToDevice, st));
+    }
+  }
+  return CSM_OK;
+}
+
 // defer_flags: the yaw build's flag count is read back with the results
 // instead of synchronizing after the build (one synchronization less per
 // batch; a flag, ~2^-16 per yaw, makes the caller rerun with the check).
@@ -1841,13 +2064,7 @@ int MatchBatch3(csm_context* ctx, csm_fast3d* const* submaps, int32_t num_submap
   ParallelPairs(num_pairs, [&](int64_t i) {
     if (results[i].status != CSM_NO_MATCH) return;
     const csm_pair3d& p = pairs[i];
-    const csm_node3d& nd = nodes[p.node];
-    if (nd.histogram_size != static_cast<int32_t>(submaps[p.submap]->histogram.size()) ||
-        nd.histogram_size > kMaxHistogram || (nd.histogram_size > 0 && !nd.histogram)) {
-      prep[i].status = CSM_EINVAL;
-      return;
-    }
-    PreparePair(submaps[p.submap], nd, p, max_norm[p.node], &prep[i]);
+    PreparePair(submaps[p.submap], nodes[p.node], p, max_norm[p.node], &prep[i]);
   });
   lap(1);
   if (prof3 && num_pairs > 0) {
@@ -1868,93 +2085,20 @@ int MatchBatch3(csm_context* ctx, csm_fast3d* const* submaps, int32_t num_submap
   // yaws (k, score) per pair come back compacted (yk, ys from yaw_src[i]).
   std::vector<int32_t> yk;
   std::vector<float> ys;
-  unsigned kept = 0;
-  const int32_t* dev_k = nullptr;
-  const float* dev_s = nullptr;
+  RotRun rot;
   std::vector<int64_t> yaw_src(static_cast<size_t>(num_pairs), 0);
   {
-    std::vector<float> hists;
-    std::vector<int64_t> node_hist(num_nodes, -1), sub_hist(num_submaps, -1);
-    std::vector<RotPair3Host> rp;
     std::vector<int64_t> rp_pair;
-    int64_t total = 0;
-    int max_yaws = 0;
-    for (int64_t i = 0; i < num_pairs; ++i) {
-      if (results[i].status != CSM_NO_MATCH || prep[i].status != CSM_OK) continue;
-      const csm_pair3d& p = pairs[i];
-      if (node_hist[p.node] < 0) {
-        node_hist[p.node] = static_cast<int64_t>(hists.size());
-        const csm_node3d& nd = nodes[p.node];
-        hists.insert(hists.end(), nd.histogram, nd.histogram + nd.histogram_size);
-      }
-      if (sub_hist[p.submap] < 0) {
-        sub_hist[p.submap] = static_cast<int64_t>(hists.size());
-        const auto& h = submaps[p.submap]->histogram;
-        hists.insert(hists.end(), h.begin(), h.end());
-      }
-      RotPair3Host r{};
-      r.node_hist = static_cast<int32_t>(node_hist[p.node]);
-      r.submap_hist = static_cast<int32_t>(sub_hist[p.submap]);
-      r.size = nodes[p.node].histogram_size;
-      r.window = prep[i].angular_window;
-      r.step = prep[i].astep;
-      r.yaw0 = prep[i].yaw0;
-      r.out = total;
-      r.min_score = submaps[p.submap]->options.min_rotational_score;
-      total += 2 * r.window + 1;
-      max_yaws = std::max(max_yaws, 2 * r.window + 1);
-      rp.push_back(r);
-      rp_pair.push_back(i);
-    }
-    std::vector<int2> range(rp.size());
-    if (!rp.empty()) {
-      int rc;
-      hipStream_t st = ctx->stream;
-      if ((rc = ctx->f3_items.Reserve(sizeof(RotPair3Host) * rp.size() +
-                                      sizeof(float) * std::max<size_t>(hists.size(), 1))))
-        return rc;
-      // [scores | passing k | passing scores | ranges | cursor]
-      if ((rc = ctx->f3_scores.Reserve(12 * total + sizeof(int2) * rp.size() + 16))) return rc;
-      float* dscores = ctx->f3_scores.as<float>();
-      int32_t* dk = reinterpret_cast<int32_t*>(dscores + total);
-      float* ds = reinterpret_cast<float*>(dk + total);
-      int2* drange = reinterpret_cast<int2*>(ds + total + (total & 1));
-      unsigned* dcursor = reinterpret_cast<unsigned*>(drange + rp.size());
-      RotPair3Host* drp = ctx->f3_items.as<RotPair3Host>();
-      float* dh = reinterpret_cast<float*>(drp + rp.size());
-      // Pinned staging both ways, one copy each: the pair records and
-      // histograms up (contiguous on the device), the ranges and the cursor
-      // (adjacent) back. Pageable copies cost ~25 us each, which dominated
-      // a single call's latency (profiles/r6h/).
-      const size_t up_bytes = sizeof(RotPair3Host) * rp.size() + sizeof(float) * hists.size();
-      const size_t rb_bytes = sizeof(int2) * rp.size() + sizeof(unsigned);
-      if ((rc = ctx->f3_up.Reserve(up_bytes)) || (rc = ctx->f3_rb.Reserve(rb_bytes))) return rc;
-      std::memcpy(ctx->f3_up.ptr, rp.data(), sizeof(RotPair3Host) * rp.size());
-      if (!hists.empty())
-        std::memcpy(ctx->f3_up.as<char>() + sizeof(RotPair3Host) * rp.size(), hists.data(),
-                    sizeof(float) * hists.size());
-      CSM_HIP(hipMemcpyAsync(drp, ctx->f3_up.ptr, up_bytes, hipMemcpyHostToDevice, st));
-      CSM_HIP(hipMemsetAsync(dcursor, 0, sizeof(unsigned), st));
-      CSM_HIP(LaunchRotScores(drp, static_cast<int>(rp.size()), max_yaws, dh, dscores, st));
-      CSM_HIP(LaunchYawCompact(drp, static_cast<int>(rp.size()), dscores, dcursor, drange, dk, ds,
-                               st));
-      CSM_HIP(hipMemcpyAsync(ctx->f3_rb.ptr, drange, rb_bytes, hipMemcpyDeviceToHost, st));
-      CSM_HIP(hipStreamSynchronize(st));
-      std::memcpy(range.data(), ctx->f3_rb.ptr, sizeof(int2) * rp.size());
-      std::memcpy(&kept, ctx->f3_rb.as<char>() + sizeof(int2) * rp.size(), sizeof(unsigned));
-      // The passing (k, score) lists stay on the device (f3_scores) for the
-      // yaw_build kernel; the host reads them back with the results.
-      dev_k = dk;
-      dev_s = ds;
-    }
+    int rc;
+    if ((rc = RotationalPhase(ctx, submaps, num_submaps, nodes, num_nodes, pairs, num_pairs, results,
+                              prep, &rp_pair, &rot)))
+      return rc;
     lap(2);
-    for (size_t j = 0; j < rp_pair.size(); ++j) {
-      const int64_t i = rp_pair[j];
-      prep[i].num_yaws = range[j].y;
-      yaw_src[i] = range[j].x;
-      KeyBits(range[j].y, &prep[i]);
-    }
+    TakeYawRanges(rp_pair, rot, &prep, &yaw_src);
   }
+  const unsigned kept = rot.kept;
+  const int32_t* const dev_k = rot.k;
+  const float* const dev_s = rot.s;
   lap(3);
   std::vector<Submap3Desc> sdesc(num_submaps);
   for (int i = 0; i < num_submaps; ++i) sdesc[i] = submaps[i]->desc;
@@ -2019,91 +2163,11 @@ int MatchBatch3(csm_context* ctx, csm_fast3d* const* submaps, int32_t num_submap
   std::memcpy(ctx->f3_up.as<char>() + sizeof(Pair3Desc) * np, sdesc.data(),
               sizeof(Submap3Desc) * num_submaps);
   CSM_HIP(hipMemcpyAsync(dpairs, ctx->f3_up.ptr, desc_bytes, hipMemcpyHostToDevice, st));
-  if (ny > 0) {
-    // Discrete-scan poses of the yaws that pass, built on the device from the
-    // compacted (k, score) lists; the few yaws whose float sin / cos rounding
-    // the device cannot decide are rebuilt here with libm and patched in.
-    std::vector<YawBuild3> yb(static_cast<size_t>(np));
-    for (int dp = 0; dp < np; ++dp) {
-      const PairPrep& pr = prep[pair_of[dp]];
-      YawBuild3& b = yb[dp];
-      b.siw = pr.submap_inv.w;
-      b.six = pr.submap_inv.x;
-      b.siy = pr.submap_inv.y;
-      b.siz = pr.submap_inv.z;
-      b.nqw = pr.node_q.w;
-      b.nqx = pr.node_q.x;
-      b.nqy = pr.node_q.y;
-      b.nqz = pr.node_q.z;
-      b.tx = pr.node_to_submap.t.x;
-      b.ty = pr.node_to_submap.t.y;
-      b.tz = pr.node_to_submap.t.z;
-      b.astep = pr.astep;
-      b.window = pr.angular_window;
-      b.src = static_cast<int32_t>(yaw_src[pair_of[dp]]);
-      b.yaw_begin = pdesc[dp].yaw_begin;
-      b.num = pdesc[dp].num_yaws;
-    }
-    // f3_items held the rotational-score inputs, which are consumed (synced).
-    // Layout [flag count (16 B) | flags | build records]: the count and the
-    // first 64 flags come back in one pinned copy.
-    if ((rc = ctx->f3_items.Reserve(16 + sizeof(YawFlag3) * kYawFlagCap + sizeof(YawBuild3) * np)))
-      return rc;
-    dflag_count = ctx->f3_items.as<unsigned>();
-    YawFlag3* dflags = reinterpret_cast<YawFlag3*>(ctx->f3_items.as<char>() + 16);
-    YawBuild3* dyb = reinterpret_cast<YawBuild3*>(dflags + kYawFlagCap);
-    std::memcpy(ctx->f3_up.as<char>() + yb_at, yb.data(), sizeof(YawBuild3) * np);
-    CSM_HIP(hipMemcpyAsync(dyb, ctx->f3_up.as<char>() + yb_at, sizeof(YawBuild3) * np,
-                           hipMemcpyHostToDevice, st));
-    CSM_HIP(hipMemsetAsync(dflag_count, 0, sizeof(unsigned), st));
-    CSM_HIP(LaunchYawBuild(dyb, np, dev_k, dev_s, ctx->f3_yaws.as<Yaw3Desc>(), dflag_count, dflags,
-                           st));
-    unsigned nflag = 0;
-    YawFlag3 flags[64];
-    const size_t flag_rb = 16 + sizeof(flags);
-    if (!defer_flags) {
-      if ((rc = ctx->f3_rb.Reserve(flag_rb))) return rc;
-      CSM_HIP(hipMemcpyAsync(ctx->f3_rb.ptr, dflag_count, flag_rb, hipMemcpyDeviceToHost, st));
-      CSM_HIP(hipStreamSynchronize(st));
-      std::memcpy(&nflag, ctx->f3_rb.ptr, sizeof(unsigned));
-      std::memcpy(flags, ctx->f3_rb.as<char>() + 16, sizeof(flags));
-      // CSM_YAW_HOST_BUILD (tests): the host path for every yaw.
-      if (nflag > static_cast<unsigned>(kYawFlagCap) || std::getenv("CSM_YAW_HOST_BUILD")) {
-        // More undecided roundings than the flag list holds (~2^-15 per value,
-        // so only in batches of ~10^8 yaws): rebuild every yaw on the host.
-        std::vector<int32_t> hk(std::max(kept, 1u));
-        std::vector<float> hs(std::max(kept, 1u));
-        CSM_HIP(hipMemcpyAsync(hk.data(), dev_k, sizeof(int32_t) * kept, hipMemcpyDeviceToHost, st));
-        CSM_HIP(hipMemcpyAsync(hs.data(), dev_s, sizeof(float) * kept, hipMemcpyDeviceToHost, st));
-        CSM_HIP(hipStreamSynchronize(st));
-        if ((rc = ctx->f3_host_yaws.Reserve(sizeof(Yaw3Desc) * ny))) return rc;
-        Yaw3Desc* hy = ctx->f3_host_yaws.as<Yaw3Desc>();
-        ParallelPairs(np, [&](int64_t dp) {
-          const int64_t i = pair_of[dp];
-          BuildYaws(hk.data() + yaw_src[i], hs.data() + yaw_src[i], prep[i].num_yaws,
-                    static_cast<int32_t>(dp), prep[i], hy + pdesc[dp].yaw_begin);
-        });
-        CSM_HIP(hipMemcpyAsync(ctx->f3_yaws.ptr, hy, sizeof(Yaw3Desc) * ny, hipMemcpyHostToDevice, st));
-        nflag = 0;
-      }
-      if (nflag > 0) {
-        std::vector<YawFlag3> all(flags, flags + std::min<unsigned>(nflag, 64));
-        if (nflag > 64) {
-          all.resize(nflag);
-          CSM_HIP(hipMemcpy(all.data(), dflags, sizeof(YawFlag3) * nflag, hipMemcpyDeviceToHost));
-        }
-        if ((rc = ctx->f3_host_yaws.Reserve(sizeof(Yaw3Desc) * all.size()))) return rc;
-        Yaw3Desc* hy = ctx->f3_host_yaws.as<Yaw3Desc>();
-        for (size_t f = 0; f < all.size(); ++f) {
-          const YawFlag3& fl = all[f];
-          BuildYaws(&fl.k, &fl.score, 1, fl.dp, prep[pair_of[fl.dp]], &hy[f]);
-          hy[f].yaw_id = fl.j;
-          CSM_HIP(hipMemcpyAsync(ctx->f3_yaws.as<Yaw3Desc>() + pdesc[fl.dp].yaw_begin + fl.j, &hy[f],
-                                 sizeof(Yaw3Desc), hipMemcpyHostToDevice, st));
-        }
-      }
-    }  // !defer_flags
-  }
+  // Phase 3 (device): the discrete-scan poses of the yaws that pass; the
+  // yaw-build records follow the descriptors in the staging buffer.
+  if (ny > 0 && (rc = YawBuildPhase(ctx, pdesc, pair_of, prep, yaw_src, ny, rot, yb_at, defer_flags,
+                                    &dflag_count)))
+    return rc;
   CSM_HIP(hipStreamWaitEvent(st, ctx->f3_points_ready, 0));
   {  // best keys, witnesses, statuses, claim counters and stats: one launch
     Segs3 z{};
@@ -2175,9 +2239,7 @@ int MatchBatch3(csm_context* ctx, csm_fast3d* const* submaps, int32_t num_submap
       h += g.bytes[k];
     }
   }
-  // Only with deferred flags; CSM_YAW_FORCE_RETRY (tests) takes the retry
-  // path on every batch.
-  if (nflag != 0 || (defer_flags && std::getenv("CSM_YAW_FORCE_RETRY"))) return kRetryWithYawFlags;
+  if (RetryWithYawFlags(nflag, defer_flags)) return kRetryWithYawFlags;  // only with deferred flags
   // Exactly tied maxima: the reference's pick (ResolveTies3d), then the
   // winning leaves' low-resolution scores (the Result field).
   std::vector<int8_t> tie_code(np, CSM_TIE_NONE);
@@ -2263,6 +2325,157 @@ int csm_fast3d_match_batch(csm_context* ctx, csm_fast3d* const* submaps, int32_t
                              /*defer_flags=*/true);
   if (rc != kRetryWithYawFlags) return rc;
   return MatchBatch3(ctx, submaps, num_submaps, nodes, num_nodes, pairs, num_pairs, results, false);
+}
+
+int csm_rotational_scores_batch(csm_context* ctx, const float* histograms, int64_t num_floats,
+                                const csm_rot_pair3d* pairs, int32_t num_pairs, float* scores,
+                                int32_t* ranges, int32_t* kept_k, float* kept_scores,
+                                int64_t* num_kept) {
+  if (!ctx || !num_kept || num_pairs < 0 || num_floats < 0 || num_floats > INT32_MAX ||
+      (num_floats > 0 && !histograms))
+    return CSM_EINVAL;
+  if (num_pairs > 0 && (!pairs || !scores || !ranges || !kept_k || !kept_scores)) return CSM_EINVAL;
+  *num_kept = 0;
+  std::vector<RotPair3Host> rp(static_cast<size_t>(num_pairs));
+  int64_t total = 0;
+  int max_yaws = 0;
+  for (int32_t p = 0; p < num_pairs; ++p) {
+    const csm_rot_pair3d& in = pairs[p];
+    if (in.size < 0 || in.size > kMaxHistogram || in.window < 0 || in.window > kMax3dYaws / 2 ||
+        !std::isfinite(in.step) || !std::isfinite(in.yaw0) || !std::isfinite(in.min_score) ||
+        in.node_histogram < 0 || in.submap_histogram < 0 ||
+        static_cast<int64_t>(in.node_histogram) + in.size > num_floats ||
+        static_cast<int64_t>(in.submap_histogram) + in.size > num_floats)
+      return CSM_EINVAL;
+    RotPair3Host& r = rp[p];
+    r.node_hist = in.node_histogram;
+    r.submap_hist = in.submap_histogram;
+    r.size = in.size;
+    r.window = in.window;
+    r.step = in.step;
+    r.yaw0 = in.yaw0;
+    r.out = total;
+    r.min_score = in.min_score;
+    total += 2 * in.window + 1;
+    max_yaws = std::max(max_yaws, 2 * in.window + 1);
+  }
+  if (num_pairs > 65535 || total > INT32_MAX) return CSM_ERANGE;  // one launch's grid.y; int2 ranges
+  if (num_pairs == 0) return CSM_OK;
+  try {
+    const std::vector<float> hists(histograms, histograms + num_floats);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    int rc;
+    if ((rc = EnsureDevice3(ctx))) return rc;
+    RotRun run;
+    if ((rc = RunRotScores(ctx, rp, hists, total, max_yaws, &run))) return rc;
+    hipStream_t st = ctx->stream;
+    CSM_HIP(hipMemcpyAsync(scores, run.scores, sizeof(float) * total, hipMemcpyDeviceToHost, st));
+    if (run.kept > 0) {
+      CSM_HIP(hipMemcpyAsync(kept_k, run.k, sizeof(int32_t) * run.kept, hipMemcpyDeviceToHost, st));
+      CSM_HIP(hipMemcpyAsync(kept_scores, run.s, sizeof(float) * run.kept, hipMemcpyDeviceToHost, st));
+    }
+    CSM_HIP(hipStreamSynchronize(st));
+    for (int32_t p = 0; p < num_pairs; ++p) {
+      ranges[2 * p] = run.range[p].x;
+      ranges[2 * p + 1] = run.range[p].y;
+    }
+    *num_kept = run.kept;
+  } catch (...) {  // no exception crosses the C-ABI
+    return CSM_ENOMEM;
+  }
+  return CSM_OK;
+}
+
+namespace {
+
+// One pass of csm_fast3d_discrete_scans: phases 1 to 3 of MatchBatch3 for one
+// pair, then f3_yaws and the kept k read back.
+int DiscreteScans3(csm_context* ctx, csm_fast3d* m, const csm_node3d& node, csm_pair3d pair,
+                   bool defer_flags, std::vector<csm_discrete_scan3d>* scans, PairPrep* prep_out,
+                   int32_t* status) {
+  scans->clear();
+  pair.submap = pair.node = 0;
+  csm_result3d res{};
+  res.status = CSM_NO_MATCH;
+  if (node.num_high_resolution < 0 || node.num_low_resolution < 0 ||
+      node.num_high_resolution > kMax3dPoints || node.histogram_size < 0 ||
+      (node.num_high_resolution > 0 && !node.high_resolution_xyz)) {
+    *status = node.num_high_resolution > kMax3dPoints ? CSM_ERANGE : CSM_EINVAL;
+    return CSM_OK;
+  }
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  int rc;
+  if ((rc = EnsureDevice3(ctx))) return rc;
+  if ((rc = WaitBuilt(m->ready, m->ctx->stream, ctx->stream))) return rc;
+  std::vector<PairPrep> prep(1);
+  PreparePair(m, node, pair, MaxNorm(node), &prep[0]);
+  RotRun rot;
+  std::vector<int64_t> yaw_src(1, 0), rp_pair;
+  if ((rc = RotationalPhase(ctx, &m, 1, &node, 1, &pair, 1, &res, prep, &rp_pair, &rot))) return rc;
+  TakeYawRanges(rp_pair, rot, &prep, &yaw_src);
+  *prep_out = prep[0];
+  *status = prep[0].status;
+  const int ny = prep[0].num_yaws;
+  if (prep[0].status != CSM_OK || ny == 0) return CSM_OK;
+  std::vector<Pair3Desc> pdesc(1, prep[0].desc);
+  pdesc[0].yaw_begin = 0;
+  pdesc[0].num_yaws = ny;
+  const std::vector<int64_t> pair_of(1, 0);
+  if ((rc = ctx->f3_yaws.Reserve(sizeof(Yaw3Desc) * ny))) return rc;
+  if ((rc = ctx->f3_up.Reserve(sizeof(YawBuild3)))) return rc;
+  if (std::getenv("CSM_YAW_HOST_BUILD")) defer_flags = false;
+  unsigned* dflag_count = nullptr;
+  if ((rc = YawBuildPhase(ctx, pdesc, pair_of, prep, yaw_src, ny, rot, 0, defer_flags, &dflag_count)))
+    return rc;
+  hipStream_t st = ctx->stream;
+  unsigned nflag = 0;  // deferred: read where the batch reads it, after the build
+  if (defer_flags) CSM_HIP(hipMemcpyAsync(&nflag, dflag_count, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  std::vector<Yaw3Desc> yaws(static_cast<size_t>(ny));
+  std::vector<int32_t> ks(static_cast<size_t>(ny));
+  CSM_HIP(hipMemcpyAsync(yaws.data(), ctx->f3_yaws.ptr, sizeof(Yaw3Desc) * ny, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipMemcpyAsync(ks.data(), rot.k + yaw_src[0], sizeof(int32_t) * ny, hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  if (RetryWithYawFlags(nflag, defer_flags)) return kRetryWithYawFlags;
+  scans->resize(static_cast<size_t>(ny));
+  for (int j = 0; j < ny; ++j) {
+    const Yaw3Desc& y = yaws[j];
+    csm_discrete_scan3d& s = (*scans)[j];
+    s.k = ks[j];
+    s.rotational_score = y.rotational_score;
+    s.q[0] = y.qw, s.q[1] = y.qx, s.q[2] = y.qy, s.q[3] = y.qz;
+    s.n[0] = y.nw, s.n[1] = y.nx, s.n[2] = y.ny, s.n[3] = y.nz;
+    s.t[0] = y.tx, s.t[1] = y.ty, s.t[2] = y.tz;
+  }
+  return CSM_OK;
+}
+
+}  // namespace
+
+int csm_fast3d_discrete_scans(csm_context* ctx, csm_fast3d* m, const csm_node3d* node,
+                              const csm_pair3d* pair, csm_discrete_scan3d* scans,
+                              int32_t capacity, int32_t* count, int32_t* angular_window,
+                              float* angular_step, float* yaw0, int32_t* status) {
+  if (!ctx || !m || !node || !pair || !count || !angular_window || !angular_step || !yaw0 ||
+      !status || capacity < 0 || (capacity > 0 && !scans) || m->ctx->device != ctx->device)
+    return CSM_EINVAL;
+  *count = *angular_window = 0;
+  *angular_step = *yaw0 = 0.f;
+  *status = CSM_OK;
+  try {
+    std::vector<csm_discrete_scan3d> out;
+    PairPrep prep;
+    int rc = DiscreteScans3(ctx, m, *node, *pair, /*defer_flags=*/true, &out, &prep, status);
+    if (rc == kRetryWithYawFlags) rc = DiscreteScans3(ctx, m, *node, *pair, false, &out, &prep, status);
+    if (rc) return rc;
+    *angular_window = prep.angular_window;
+    *angular_step = prep.astep;
+    *yaw0 = prep.yaw0;
+    *count = static_cast<int32_t>(out.size());
+    std::copy_n(out.begin(), std::min<size_t>(out.size(), static_cast<size_t>(capacity)), scans);
+  } catch (...) {  // no exception crosses the C-ABI
+    return CSM_ENOMEM;
+  }
+  return CSM_OK;
 }
 
 namespace {

@@ -615,6 +615,72 @@ def match_batch_3d(matchers: Sequence[FastCorrelativeScanMatcher3D], nodes: Sequ
     return list(results)
 
 
+ROT_PAIR3_DTYPE = np.dtype([("node_histogram", np.int32), ("submap_histogram", np.int32),
+                            ("size", np.int32), ("window", np.int32), ("step", np.float32),
+                            ("yaw0", np.float32), ("min_score", np.float64)])
+DISCRETE_SCAN3_DTYPE = np.dtype([("k", np.int32), ("rotational_score", np.float32),
+                                 ("q", np.float32, 4), ("n", np.float32, 4), ("t", np.float32, 3)])
+
+
+def rotational_scores_batch(histograms, pairs, context: Optional[Context] = None):
+    """csm_rotational_scores_batch (visible for testing): the batch search's
+    rot_scores and yaw_compact kernels on raw inputs. ``histograms``: one
+    float32 array; ``pairs``: a ROT_PAIR3_DTYPE array or (node offset, submap
+    offset, size, window, step, yaw0, min_score) tuples. Returns (scores: per
+    pair its 2 * window + 1 floats, ranges (P, 2): offset and count of each
+    pair's kept yaws, kept_k, kept_scores)."""
+    from . import RotPair3D
+    ctx = context or default_context()
+    assert ROT_PAIR3_DTYPE.itemsize == C.sizeof(RotPair3D)
+    hists = np.ascontiguousarray(np.asarray(histograms, np.float32).reshape(-1))
+    if isinstance(pairs, np.ndarray):
+        arr = np.ascontiguousarray(pairs, ROT_PAIR3_DTYPE)
+    else:
+        arr = np.array([tuple(p) for p in pairs], ROT_PAIR3_DTYPE)
+    counts = 2 * arr["window"].astype(np.int64) + 1
+    total = int(counts.clip(min=0).sum())
+    scores = np.zeros(max(total, 1), np.float32)
+    ranges = np.zeros((max(len(arr), 1), 2), np.int32)
+    kept_k = np.zeros(max(total, 1), np.int32)
+    kept_s = np.zeros(max(total, 1), np.float32)
+    kept = C.c_int64()
+    _check(ctx._lib.csm_rotational_scores_batch(
+        ctx.handle, _ptr(hists, C.c_float), len(hists), arr.ctypes.data_as(C.POINTER(RotPair3D)),
+        len(arr), _ptr(scores, C.c_float), _ptr(ranges, C.c_int32), _ptr(kept_k, C.c_int32),
+        _ptr(kept_s, C.c_float), C.byref(kept)), "csm_rotational_scores_batch")
+    ends = np.cumsum(counts)
+    per_pair = [scores[e - c:e] for c, e in zip(counts, ends)]
+    return per_pair, ranges[:len(arr)], kept_k[:kept.value], kept_s[:kept.value]
+
+
+def discrete_scans_3d(matcher: FastCorrelativeScanMatcher3D, node: NodeData3D, node_pose,
+                      submap_pose, full_submap: bool = False, min_score: float = 0.0,
+                      context: Optional[Context] = None):
+    """csm_fast3d_discrete_scans (visible for testing): the discrete scans the
+    batch search builds for this pair -> (DISCRETE_SCAN3_DTYPE array in
+    increasing k, angular_window, angular_step, yaw0). Poses as ((t), (w, x,
+    y, z)); for ``full_submap`` only their rotations are used."""
+    from . import DiscreteScan3D
+    ctx = context or matcher.context
+    assert DISCRETE_SCAN3_DTYPE.itemsize == C.sizeof(DiscreteScan3D)
+    cnode = node.to_c()
+    pair = Pair3D()
+    pair.full_submap = 1 if full_submap else 0
+    pair.min_score = min_score
+    pair.node_pose = _pose(node_pose)
+    pair.submap_pose = _pose(submap_pose)
+    count, window, status = C.c_int32(), C.c_int32(), C.c_int32()
+    step, yaw0 = C.c_float(), C.c_float()
+    out = np.zeros((1 << 16) + 1, DISCRETE_SCAN3_DTYPE)  # every yaw of the widest window
+    _check(ctx._lib.csm_fast3d_discrete_scans(
+        ctx.handle, matcher.handle, C.byref(cnode), C.byref(pair),
+        out.ctypes.data_as(C.POINTER(DiscreteScan3D)), len(out), C.byref(count),
+        C.byref(window), C.byref(step), C.byref(yaw0), C.byref(status)),
+        "csm_fast3d_discrete_scans")
+    _check(status.value, "csm_fast3d_discrete_scans")
+    return out[:count.value].copy(), window.value, float(step.value), float(yaw0.value)
+
+
 def ceres_refine_batch_3d(grids: Sequence[HybridGrid], nodes: Sequence[NodeData3D], items,
                           options=None, context: Optional[Context] = None,
                           intensity_grids: Optional[Sequence[IntensityHybridGrid]] = None,

@@ -506,6 +506,59 @@ int csm_fast3d_match_batch(csm_context* ctx, csm_fast3d* const* submaps, int32_t
                            const csm_node3d* nodes, int32_t num_nodes, const csm_pair3d* pairs,
                            int64_t num_pairs, csm_result3d* results);
 
+/* Test-visible: the batch search's rotational stage on raw inputs
+ * (RotationalScanMatcher::Match, rotational_scan_matcher.cc:119-185, and the
+ * min_rotational_score filter of GenerateDiscreteScans,
+ * fast_correlative_scan_matcher_3d.cc:258-270), through the two kernels the
+ * batch launches. Record p scores the 2 * window + 1 angles
+ * yaw0 + (k - window) * step (float arithmetic), k = 0..2 * window, of the
+ * `size` buckets at histograms[node_histogram] against those at
+ * histograms[submap_histogram]; records may share histograms. */
+typedef struct csm_rot_pair3d {
+  int32_t node_histogram;   /* float offsets into `histograms` */
+  int32_t submap_histogram;
+  int32_t size;             /* 0..512 buckets */
+  int32_t window;           /* 0..32768 */
+  float step, yaw0;
+  double min_score;         /* yaw k is kept unless (double)score_k < min_score */
+} csm_rot_pair3d;
+
+/* scores: every record's scores, record after record (sum of 2 * window + 1
+ * floats). ranges[2 * p], ranges[2 * p + 1]: offset and count of record p's
+ * kept yaws in kept_k / kept_scores (capacity: as `scores`), k increasing
+ * within a record; the records' ranges tile [0, *num_kept) in no fixed order.
+ * CSM_EINVAL: a null pointer, a size, window or histogram offset out of
+ * range, a non-finite step, yaw0 or min_score; CSM_ERANGE: more than 65535
+ * records or 2^31 - 1 scores. Waits for the stream. */
+int csm_rotational_scores_batch(csm_context* ctx, const float* histograms, int64_t num_floats,
+                                const csm_rot_pair3d* pairs, int32_t num_pairs, float* scores,
+                                int32_t* ranges, int32_t* kept_k, float* kept_scores,
+                                int64_t* num_kept);
+
+/* Test-visible: the discrete scans (GenerateDiscreteScans,
+ * fast_correlative_scan_matcher_3d.cc:246-295) that csm_fast3d_match_batch
+ * searches for the pair (m, node) with these poses, through the batch's own
+ * pair preparation, rotational stage and yaw build (the host patches of
+ * undecided roundings included). One record per kept yaw, k increasing:
+ * the scan's rotation q and GetPoseFromCandidate's normalized rotation n
+ * (both w, x, y, z) and its translation t, as the search kernels read them. */
+typedef struct csm_discrete_scan3d {
+  int32_t k;               /* angle index: angle = (k - angular_window) * angular_step */
+  float rotational_score;
+  float q[4];
+  float n[4];
+  float t[3];
+} csm_discrete_scan3d;
+
+/* status: the pair's status as csm_result3d.status reports it (CSM_OK, or the
+ * error that keeps the batch from searching the pair); *count: kept yaws, of
+ * which min(*count, capacity) are written to `scans` (may be NULL with
+ * capacity 0). yaw0: the initial angle of the rotational match. */
+int csm_fast3d_discrete_scans(csm_context* ctx, csm_fast3d* m, const csm_node3d* node,
+                              const csm_pair3d* pair, csm_discrete_scan3d* scans,
+                              int32_t capacity, int32_t* count, int32_t* angular_window,
+                              float* angular_step, float* yaw0, int32_t* status);
+
 /* ---- CeresScanMatcher2D refinement ------------------------------------------
  * ConstraintBuilder2D::ComputeConstraint refines every accepted match with
  * CeresScanMatcher2D::Match(target_translation = match translation,

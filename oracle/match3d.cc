@@ -300,6 +300,17 @@ void FastCorrelativeScanMatcher3D::Setup(bool full_submap, const Rigid3d& node_p
   *spf = CastRigidF(Rigid3d{Vec3d{0., 0., 0.}, submap_pose.q});
 }
 
+std::vector<FastCorrelativeScanMatcher3D::DiscreteScan3D> FastCorrelativeScanMatcher3D::DiscreteScansOf(
+    bool full_submap, const Rigid3d& node_pose, const Rigid3d& submap_pose, const NodeData3D& node,
+    DiscreteScanTrace* trace) const {
+  SearchParameters sp;
+  Rigid3f np, spf;
+  Setup(full_submap, node_pose, submap_pose, node, &sp, &np, &spf);
+  return GenerateDiscreteScans(sp, node.high_resolution_point_cloud,
+                               node.rotational_scan_matcher_histogram, node.gravity_alignment, np,
+                               spf, trace);
+}
+
 bool FastCorrelativeScanMatcher3D::EvaluateLeaf(bool full_submap, const Rigid3d& node_pose,
                                                 const Rigid3d& submap_pose, const NodeData3D& node,
                                                 const Rigid3d& pose, Fast3dResult* out) const {
@@ -432,7 +443,8 @@ FastCorrelativeScanMatcher3D::GenerateDiscreteScans(const SearchParameters& sp,
                                                     const std::vector<float>& histogram,
                                                     const Quatd& gravity_alignment,
                                                     const Rigid3f& global_node_pose,
-                                                    const Rigid3f& global_submap_pose) const {
+                                                    const Rigid3f& global_submap_pose,
+                                                    DiscreteScanTrace* trace) const {
   std::vector<DiscreteScan3D> result;
   float max_scan_range = 3.f * resolution_;
   for (const Vec3f& p : cloud) max_scan_range = std::max(NormF(p), max_scan_range);
@@ -448,8 +460,14 @@ FastCorrelativeScanMatcher3D::GenerateDiscreteScans(const SearchParameters& sp,
                   static_cast<float>(gi.z)};
   const std::vector<float> scores = RotationalMatch(
       *histogram_, histogram, GetYawF(QuatMulSse(node_to_submap.q, gif)), angles);
+  if (trace) {
+    trace->window = window;
+    trace->step = step;
+    trace->scores = scores;
+  }
   for (size_t i = 0; i != angles.size(); ++i) {
     if (scores[i] < options_.min_rotational_score) continue;
+    if (trace) trace->kept.push_back(static_cast<int>(i));
     const Quatf yaw = AngleAxisVectorToRotationQuaternionF(Vec3f{0.f, 0.f, angles[i]});
     const Rigid3f pose{node_to_submap.t,
                        QuatMulSse(QuatMulSse(QuatInverseSse(global_submap_pose.q), yaw),

@@ -284,12 +284,28 @@ class FastCorrelativeScanMatcher3D {
     float score = -std::numeric_limits<float>::infinity();  // (fast_correlative_scan_matcher_3d.cc:104)
     float low_resolution_score = 0.f;
   };
+  // Test hook: what GenerateDiscreteScans computed on the way: the angular
+  // window and step, every angle's rotational score and the angle index
+  // (0..2 * window) of each scan it kept.
+  struct DiscreteScanTrace {
+    int window = 0;
+    float step = 0.f;
+    std::vector<float> scores;
+    std::vector<int> kept;
+  };
   std::vector<DiscreteScan3D> GenerateDiscreteScans(const SearchParameters& sp,
                                                     const PointCloud& cloud,
                                                     const std::vector<float>& histogram,
                                                     const Quatd& gravity_alignment,
                                                     const Rigid3f& global_node_pose,
-                                                    const Rigid3f& global_submap_pose) const;
+                                                    const Rigid3f& global_submap_pose,
+                                                    DiscreteScanTrace* trace = nullptr) const;
+  // Test hook: GenerateDiscreteScans with the search parameters and poses of
+  // Match or (full_submap) MatchFullSubmap.
+  std::vector<DiscreteScan3D> DiscreteScansOf(bool full_submap, const Rigid3d& global_node_pose,
+                                              const Rigid3d& global_submap_pose,
+                                              const NodeData3D& node,
+                                              DiscreteScanTrace* trace) const;
 
  private:
   void Setup(bool full_submap, const Rigid3d& node_pose, const Rigid3d& submap_pose,

@@ -176,6 +176,44 @@ void oracle_fast3d_match_full_submap(void* h, const double* node_q, const double
   PutResult(r, out);
 }
 
+// Eigen's packet-order sum of v[0..n) (the reduction behind dot() and norm()).
+float oracle_redux_sum(const float* v, int n) { return ReduxSumSse(v, n); }
+
+// The matcher's own GenerateDiscreteScans with the search parameters of Match
+// (full_submap = 0) or MatchFullSubmap. window_step: the angular window and
+// step; all_scores (may be null): the 2 * window + 1 unfiltered scores when
+// score_capacity holds them. Per kept scan, when capacity holds them all: its
+// angle index k, its score and 11 floats: the pose's q (w, x, y, z), its t,
+// and GetPoseFromCandidate's rotation QuatNormalizedSse(QuatMulSse(identity,
+// q)). Returns the number of kept scans.
+int oracle_fast3d_discrete_scans(void* h, int full_submap, const double* node_pose,
+                                 const double* submap_pose, const float* high, int nh,
+                                 const float* low, int nl, const float* hist, int hsize,
+                                 const double* gravity_q, double* window_step, float* all_scores,
+                                 int score_capacity, int32_t* k, float* score, float* pose11,
+                                 int capacity) {
+  FastCorrelativeScanMatcher3D::DiscreteScanTrace trace;
+  const auto scans = static_cast<Fast3dHandle*>(h)->m->DiscreteScansOf(
+      full_submap != 0, Pose(node_pose), Pose(submap_pose),
+      Node(high, nh, low, nl, hist, hsize, gravity_q), &trace);
+  window_step[0] = trace.window;
+  window_step[1] = trace.step;
+  const int n = static_cast<int>(scans.size());
+  if (all_scores && score_capacity >= static_cast<int>(trace.scores.size()))
+    std::memcpy(all_scores, trace.scores.data(), sizeof(float) * trace.scores.size());
+  if (capacity < n) return n;
+  for (int i = 0; i < n; ++i) {
+    const Quatf& q = scans[i].pose.q;
+    const Quatf r = QuatNormalizedSse(QuatMulSse(Quatf{1.f, 0.f, 0.f, 0.f}, q));
+    k[i] = trace.kept[i];
+    score[i] = scans[i].rotational_score;
+    const float v[11] = {q.w, q.x, q.y, q.z, scans[i].pose.t.x, scans[i].pose.t.y, scans[i].pose.t.z,
+                         r.w, r.x, r.y, r.z};
+    std::memcpy(pose11 + 11 * i, v, sizeof(v));
+  }
+  return n;
+}
+
 // Tie checks: evaluates the leaf behind `pose` (t[3], q[4]); returns 1 if found.
 int oracle_fast3d_evaluate_leaf(void* h, int full_submap, const double* node_pose,
                                 const double* submap_pose, const float* high, int nh,

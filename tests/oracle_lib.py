@@ -269,6 +269,9 @@ _SIG3D = {
                                                P(D), F, P(D)]),
     "oracle_fast3d_evaluate_leaf": (I32, [VP, I32, P(D), P(D), P(F), I32, P(F), I32, P(F), I32,
                                           P(D), P(D), P(D)]),
+    "oracle_redux_sum": (F, [P(F), I32]),
+    "oracle_fast3d_discrete_scans": (I32, [VP, I32, P(D), P(D), P(F), I32, P(F), I32, P(F), I32,
+                                           P(D), P(D), P(F), I32, P(I32), P(F), P(F), I32]),
     "oracle_rt3d_match": (None, [VP, P(D), P(D), P(F), I32, P(D)]),
     "oracle_rt3d_score": (F, [VP, P(D), P(D), P(F), I32, I64, P(D)]),
     "oracle_rt3d_window": (None, [P(D), F, P(F), I32, P(I32), P(F), P(I32)]),
@@ -395,6 +398,30 @@ class OracleFast3D:
                                                     _p(p, D), _p(out, D))
         return self._out(out) if ok else None
 
+    def discrete_scans(self, node_pose, submap_pose, node, full_submap=False):
+        """The matcher's own GenerateDiscreteScans with Match's (or
+        MatchFullSubmap's) search parameters: dict with window, step (float32),
+        scores (every angle's, float32), and per kept scan k, score, q, t and
+        n = GetPoseFromCandidate's rotation (float32 arrays)."""
+        hi, lo, hist, g = self._node(node)
+        a = _pose7(*node_pose)
+        b = _pose7(*submap_pose)
+        ws = np.zeros(2)
+
+        def call(scores, k, s, poses):
+            return self.o.lib.oracle_fast3d_discrete_scans(
+                self.h, 1 if full_submap else 0, _p(a, D), _p(b, D), _p(hi, F), len(hi), _p(lo, F),
+                len(lo), _p(hist, F), len(hist), _p(g, D), _p(ws, D), _p(scores, F), len(scores),
+                _p(k, I32), _p(s, F), _p(poses, F), len(k))
+
+        none = np.zeros(0, np.float32)
+        n = call(none, np.zeros(0, np.int32), none, none)
+        scores = np.zeros(2 * int(ws[0]) + 1, np.float32)
+        k, s, poses = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 11), np.float32)
+        assert call(scores, k, s, poses) == n
+        return {"window": int(ws[0]), "step": np.float32(ws[1]), "scores": scores, "k": k,
+                "score": s, "q": poses[:, 0:4], "t": poses[:, 4:7], "n": poses[:, 7:11]}
+
     def match_full_submap(self, node_q, submap_q, node, min_score):
         hi, lo, hist, g = self._node(node)
         a = np.asarray(node_q, np.float64)
@@ -432,6 +459,26 @@ def _o3_histogram(self, cloud, size):
     return out
 
 
+def _o3_rotational_match(self, submap_histogram, histogram, initial_angle, angles):
+    """RotationalScanMatcher(&submap_histogram).Match(histogram, initial_angle,
+    angles): one float32 score per angle."""
+    _o3_hgrid(self, 1.0)
+    s = np.ascontiguousarray(submap_histogram, np.float32)
+    h = np.ascontiguousarray(histogram, np.float32)
+    assert s.shape == h.shape and s.ndim == 1
+    a = np.ascontiguousarray(angles, np.float32)
+    out = np.zeros(len(a), np.float32)
+    self.lib.oracle_rotational_match(_p(s, F), _p(h, F), len(h), float(np.float32(initial_angle)),
+                                     _p(a, F), len(a), _p(out, F))
+    return out
+
+
+def _o3_redux_sum(self, values):
+    _o3_hgrid(self, 1.0)
+    v = np.ascontiguousarray(values, np.float32)
+    return np.float32(self.lib.oracle_redux_sum(_p(v, F), len(v)))
+
+
 def _o3_rt3d_match(self, grid, options, initial, cloud):
     _o3_hgrid(self, 1.0)
     pts = np.ascontiguousarray(cloud, np.float32).reshape(-1, 3)
@@ -457,6 +504,8 @@ def _o3_rt3d_score(self, grid, options, initial, cloud, index):
 Oracle.hybrid_grid = _o3_hgrid
 Oracle.fast3d = _o3_fast3d
 Oracle.histogram = _o3_histogram
+Oracle.rotational_match = _o3_rotational_match
+Oracle.redux_sum = _o3_redux_sum
 Oracle.rt3d_match = _o3_rt3d_match
 Oracle.rt3d_score = _o3_rt3d_score
 
