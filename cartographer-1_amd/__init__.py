@@ -341,6 +341,8 @@ _SIGNATURES = {
     "csm_hybrid_grid_device_bytes": (C.c_int64, [C.c_void_p]),
     "csm_fast2d_read_level": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int64,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "csm_fast2d_read_plane": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int64,
+                                        C.POINTER(C.c_int32)]),
     "csm_scan_set_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64),
                                       C.c_int32, C.POINTER(C.c_void_p)]),
     "csm_scan_set_destroy": (None, [C.c_void_p]),
@@ -415,6 +417,10 @@ _SIGNATURES = {
     "csm_fast3d_destroy": (None, [C.c_void_p]),
     "csm_fast3d_read_level": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int64,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "csm_fast3d_search_levels": (C.c_int32, [C.c_void_p]),
+    "csm_fast3d_read_octets": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64), C.c_int64,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]),
     "csm_fast3d_match": (C.c_int, [C.c_void_p, C.POINTER(Pose3D), C.POINTER(Pose3D),
                                    C.POINTER(Node3D), C.c_float, C.POINTER(Result3D)]),
     "csm_fast3d_match_full_submap": (C.c_int, [C.c_void_p, C.POINTER(C.c_double),
@@ -1336,6 +1342,22 @@ class FastCorrelativeScanMatcher2D:
                                                out.size, C.byref(wnx), C.byref(wny)),
                "csm_fast2d_read_level")
         return out
+
+    def read_plane(self, level: int):
+        """The search plane of a level as the v4/v5 kernels load it
+        (csm_fast2d_read_plane): (layout, bytes). layout: entry_size (0 none,
+        4 quad, 16 hex), quad_w, quad_h, quad_pws, quad_pph, quad_bias,
+        cshift, bytes; the bytes are raw, in polyphase storage order."""
+        lay = (C.c_int32 * 8)()
+        _check(self._lib.csm_fast2d_read_plane(self.handle, level, None, 0, lay),
+               "csm_fast2d_read_plane")
+        out = np.zeros(int(lay[7]), np.uint8)
+        if out.size:
+            _check(self._lib.csm_fast2d_read_plane(self.handle, level, _ptr(out, C.c_uint8),
+                                                   out.size, lay), "csm_fast2d_read_plane")
+        keys = ("entry_size", "quad_w", "quad_h", "quad_pws", "quad_pph", "quad_bias", "cshift",
+                "bytes")
+        return dict(zip(keys, (int(v) for v in lay))), out
 
 
 class RealTimeCorrelativeScanMatcher2D:

@@ -37,9 +37,12 @@ struct SubmapDesc {
   int32_t wide_ny[kMaxLevels];
   int32_t zero_index[kMaxLevels];  // index of the trailing zero byte
   // Quad layout of level d (h = 2^d, search kernel v4): dword (X', Y'),
-  // X' < quad_w = wide_nx + h, Y' < quad_h = wide_ny + h, packs the values
-  // of the 2x2 children whose child (0,0) is at wide cell (X' - h, Y' - h):
-  // byte0 (0,0), byte1 (0,h), byte2 (h,0), byte3 (h,h); 0 outside the grid.
+  // X' < quad_w = wide_nx + (k - 1) + h, Y' < quad_h likewise (k: the scan
+  // cluster size below), packs the values of the 2x2 children whose child
+  // (0,0) is at widened cell (X' - h, Y' - h): byte0 (0,0), byte1 (0,h),
+  // byte2 (h,0), byte3 (h,h); 0 outside the grid. Storage entries past
+  // quad_w x quad_h (the polyphase planes are whole) are 0.
+  // csm_fast2d_read_plane returns a plane and these numbers to the tests.
   const uint32_t* quad[kMaxLevels];
   const uint8_t* pyramid_base;      // one allocation: row-major + quad levels
   int32_t pyramid_bytes;

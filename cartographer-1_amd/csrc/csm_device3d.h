@@ -102,7 +102,8 @@ struct Submap3Desc {
   int32_t search_levels;
   int32_t full_resolution_depth;
   float resolution;
-  // Octet layout of levels 0..num_levels-2 (the DFS child levels): one
+  // Octet layout of levels 0..search_levels-2 (the DFS child levels, those of
+  // nodes at the extra levels included): one
   // uint64 per cell c packs the 8 values at c + H*(x, y, z), x, y, z in {0,1},
   // byte (z << 2 | y << 1 | x); H = 2^L below full_resolution_depth, else
   // 2^(full_resolution_depth - 1). Boxes are the level's box grown by H

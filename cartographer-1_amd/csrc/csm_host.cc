@@ -1512,6 +1512,28 @@ int csm_fast2d_read_level(const csm_fast2d* m, int32_t level, uint8_t* out,
   return CSM_OK;
 }
 
+int csm_fast2d_read_plane(const csm_fast2d* m, int32_t level, uint8_t* out,
+                          int64_t capacity, int32_t* layout8) {
+  if (!m || level < 0 || level >= m->desc.levels || !layout8) return CSM_EINVAL;
+  const SubmapDesc& d = m->desc;
+  const int64_t n = d.quad_es[level] ? d.quad_bytes[level] : 0;
+  layout8[0] = d.quad_es[level];
+  layout8[1] = d.quad_w[level];
+  layout8[2] = d.quad_h[level];
+  layout8[3] = d.quad_pws[level];
+  layout8[4] = d.quad_pph[level];
+  layout8[5] = d.quad_bias[level];
+  layout8[6] = d.cshift[level];
+  layout8[7] = static_cast<int32_t>(n);
+  if (!out || n == 0) return CSM_OK;
+  if (capacity < n) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(m->ctx->mu);
+  if (EnsureDevice(m->ctx)) return CSM_EHIP;
+  CSM_HIP(hipMemcpyAsync(out, d.quad[level], n, hipMemcpyDeviceToHost, m->ctx->stream));
+  CSM_HIP(hipStreamSynchronize(m->ctx->stream));
+  return CSM_OK;
+}
+
 int csm_scan_set_create(csm_context* ctx, const float* points_xyz, const int64_t* offsets,
                         int32_t num_scans, csm_scan_set** out) {
   if (!ctx || !offsets || !out || num_scans < 0) return CSM_EINVAL;

@@ -1086,7 +1086,7 @@ void csm_fast3d_destroy(csm_fast3d* m) {
 
 int csm_fast3d_read_level(const csm_fast3d* m, int32_t level, uint8_t* out, int64_t capacity,
                           int32_t* origin3, int32_t* dims3) {
-  if (!m || level < 0 || level >= m->desc.num_levels) return CSM_EINVAL;
+  if (!m || level < 0 || level >= m->desc.search_levels) return CSM_EINVAL;
   const Brick3& b = m->desc.level[level];
   if (origin3) {
     origin3[0] = b.ox;
@@ -1107,6 +1107,37 @@ int csm_fast3d_read_level(const csm_fast3d* m, int32_t level, uint8_t* out, int6
   if (n > 0) {
     if (m->ready) CSM_HIP(hipEventSynchronize(m->ready));
     CSM_HIP(hipMemcpy(out, m->levels.as<uint8_t>() + b.offset, n, hipMemcpyDeviceToHost));
+  }
+  return CSM_OK;
+}
+
+int32_t csm_fast3d_search_levels(const csm_fast3d* m) { return m ? m->desc.search_levels : 0; }
+
+int csm_fast3d_read_octets(const csm_fast3d* m, int32_t level, uint64_t* out, int64_t capacity,
+                           int32_t* origin3, int32_t* dims3, int32_t* oct_h) {
+  if (!m || level < 0 || level + 1 >= m->desc.search_levels) return CSM_EINVAL;
+  const Brick3& b = m->desc.oct[level];
+  if (origin3) {
+    origin3[0] = b.ox;
+    origin3[1] = b.oy;
+    origin3[2] = b.oz;
+  }
+  if (dims3) {
+    dims3[0] = b.nx;
+    dims3[1] = b.ny;
+    dims3[2] = b.nz;
+  }
+  if (oct_h) *oct_h = m->desc.oct_h[level];
+  const int64_t n = static_cast<int64_t>(b.nx) * b.ny * b.nz;
+  if (!out) return CSM_OK;
+  if (capacity < n) return CSM_EINVAL;
+  std::lock_guard<std::mutex> lock(m->ctx->mu);
+  int rc;
+  if ((rc = EnsureDevice3(m->ctx))) return rc;
+  if (n > 0) {
+    if (m->ready) CSM_HIP(hipEventSynchronize(m->ready));
+    CSM_HIP(hipMemcpy(out, m->octs.as<uint8_t>() + b.offset, sizeof(uint64_t) * n,
+                      hipMemcpyDeviceToHost));
   }
   return CSM_OK;
 }

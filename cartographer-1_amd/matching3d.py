@@ -536,6 +536,23 @@ class FastCorrelativeScanMatcher3D:
                                                o, d), "csm_fast3d_read_level")
         return tuple(o), out.reshape(int(d[2]), int(d[1]), int(d[0]))
 
+    def search_levels(self) -> int:
+        """Levels built: branch_and_bound_depth plus the coarser ones the
+        device search roots at (csm_fast3d_search_levels)."""
+        return int(self._lib.csm_fast3d_search_levels(self.handle))
+
+    def read_octets(self, level: int):
+        """The octet brick of a level below search_levels() - 1 as the search
+        loads it: (origin, (nz, ny, nx) uint64, oct_h)."""
+        o, d, h = (C.c_int32 * 3)(), (C.c_int32 * 3)(), C.c_int32()
+        _check(self._lib.csm_fast3d_read_octets(self.handle, level, None, 0, o, d, C.byref(h)),
+               "csm_fast3d_read_octets")
+        out = np.zeros(int(d[0]) * int(d[1]) * int(d[2]), np.uint64)
+        _check(self._lib.csm_fast3d_read_octets(self.handle, level, _ptr(out, C.c_uint64),
+                                                out.size, o, d, C.byref(h)),
+               "csm_fast3d_read_octets")
+        return tuple(o), out.reshape(int(d[2]), int(d[1]), int(d[0])), int(h.value)
+
     def Match(self, global_node_pose, global_submap_pose, node: NodeData3D, min_score: float):
         n = node.to_c()
         r = Result3D()

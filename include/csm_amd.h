@@ -172,6 +172,14 @@ int64_t csm_fast2d_device_bytes(const csm_fast2d* m);
 int csm_fast2d_read_level(const csm_fast2d* m, int32_t level, uint8_t* out,
                           int64_t capacity, int32_t* wide_nx, int32_t* wide_ny);
 
+/* Test-visible: the search plane of level `level` as the v4/v5 kernels load
+ * it (raw bytes, polyphase storage order), and its layout in layout8:
+ * [0] entry bytes (0: the node chain reaches no plane at this level, 4: quad,
+ * 16: hex), [1] quad_w, [2] quad_h, [3] quad_pws, [4] quad_pph, [5] quad_bias,
+ * [6] cshift, [7] plane bytes. out == NULL: the layout only. */
+int csm_fast2d_read_plane(const csm_fast2d* m, int32_t level, uint8_t* out,
+                          int64_t capacity, int32_t* layout8);
+
 /* ---- Batched constraint search (the throughput path) ----------------------
  * Replaces the per-pair Tasks ConstraintBuilder2D schedules
  * (constraint_builder_2d.cc:77-137, ComputeConstraint :188-277): a set of
@@ -449,9 +457,17 @@ void csm_fast3d_destroy(csm_fast3d* m);
  * HybridGrid's bricks (as csm_fast2d_device_bytes). */
 int64_t csm_fast3d_device_bytes(const csm_fast3d* m);
 int64_t csm_hybrid_grid_device_bytes(const csm_hybrid_grid* g);
-/* Test-visible: copies pyramid level `level` (dense brick, x fastest). */
+/* Test-visible: copies pyramid level `level` (dense brick, x fastest);
+ * level < csm_fast3d_search_levels, which counts the levels above
+ * branch_and_bound_depth that only the device search roots at. */
 int csm_fast3d_read_level(const csm_fast3d* m, int32_t level, uint8_t* out, int64_t capacity,
                           int32_t* origin3, int32_t* dims3);
+int32_t csm_fast3d_search_levels(const csm_fast3d* m);
+/* Test-visible: the octet brick of level `level` < search_levels - 1 as the
+ * search loads it (one uint64 per cell, x fastest), its box and the child
+ * offset H (oct_h). out == NULL: the box and H only. */
+int csm_fast3d_read_octets(const csm_fast3d* m, int32_t level, uint64_t* out, int64_t capacity,
+                           int32_t* origin3, int32_t* dims3, int32_t* oct_h);
 
 /* The parts of TrajectoryNode::Data the matcher reads (trajectory_node.h):
  * high/low resolution point clouds, the rotational histogram and the
