@@ -16,8 +16,6 @@ constexpr int kMaxLevels = 12;
 constexpr int kNumXcd = 8;           // MI355X: 8 XCDs, 32 CUs each
 constexpr int kSearchThreads = 256;  // 4 waves per workgroup
 constexpr int kWaves = kSearchThreads / 64;
-constexpr int kStackCap = 160;       // per-wave DFS stack entries
-constexpr int kTopChunk = 64;        // top-level candidates per DFS chunk
 constexpr int kMaxPoints = 16448;    // 22-bit sum field: 16448 * 255 < 2^22
 constexpr int kIndexLimit = 16383;   // |discretized cell index| bound
 constexpr int kOffsetLimit = 8191;   // |candidate offset| bound (14-bit field)
@@ -114,17 +112,8 @@ struct WalkJob2 {
 };
 constexpr int kWalkStack = 64;  // 1 + 3 x depth entries at most
 
-// Per-XCD work queues over rotation chunks of pairs.
-struct WorkQueues {
-  const int32_t* pair_order;      // pairs, grouped by queue
-  const int64_t* chunk_prefix;    // per entry of pair_order: first chunk id
-  int32_t queue_begin[kNumXcd + 1];
-  int64_t queue_chunks[kNumXcd];  // chunks per queue
-  int32_t rot_chunk;              // rotations per chunk
-};
-
-// v4/v5 work queues: interleaved (csm_schedule.h BuildSchedule, DESIGN.md §5
-// "Rotation chunks"). A queue is a run of slots, claimed front to back with
+// Per-XCD work queues over rotation chunks of pairs, interleaved
+// (csm_schedule.h BuildSchedule, DESIGN.md §5 "Rotation chunks"). A queue is a run of slots, claimed front to back with
 // one atomicAdd each. Its pairs are grouped into blocks of pairs of one
 // submap, longest first, and a block is cut into rectangles: rectangle
 // (first, width, pos0) holds positions pos0, pos0 + 1, ... of entries

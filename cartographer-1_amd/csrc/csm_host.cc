@@ -207,7 +207,7 @@ const std::pair<SearchWindow2D, std::vector<ZRot>>& WindowFor(
 }
 
 struct SearchPlan {
-  bool use_v2 = true, hex = false, fifo = true;
+  bool hex = false, fifo = true;
   int rc = 2, max_npad = 64;
 };
 
@@ -234,36 +234,12 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
     pair_chunks[i] = (pdesc[i].num_scans + rc - 1) / rc;
   }
   const std::vector<std::vector<int32_t>> q = AssignQueues(pair_submap, spread_on);
-  // v1 kernel: pair-major, a pair's chunks in rotation order.
-  std::vector<int32_t> order;
-  std::vector<int64_t> prefix;
-  WorkQueues wq{};
-  wq.rot_chunk = rc;
-  // v4/v5 kernel: a block of pairs at a time, position-major (csm_schedule.h).
-  Schedule sched;
-  int64_t total_chunks = 0;
-  double sched_ms = 0.0;
-  if (plan.use_v2) {
-    const auto t0 = std::chrono::steady_clock::now();
-    sched = BuildSchedule(q, pair_submap, pair_chunks, rc);
-    sched_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    total_chunks = sched.items;
-  } else {
-    int64_t running = 0;
-    for (int x = 0; x < kNumXcd; ++x) {
-      wq.queue_begin[x] = static_cast<int32_t>(order.size());
-      const int64_t qstart = running;
-      for (int pi : q[x]) {
-        order.push_back(pi);
-        prefix.push_back(running);
-        running += (pdesc[pi].num_scans + rc - 1) / rc;
-      }
-      wq.queue_chunks[x] = running - qstart;
-    }
-    wq.queue_begin[kNumXcd] = static_cast<int32_t>(order.size());
-    prefix.push_back(running);
-    total_chunks = running;
-  }
+  // A block of pairs at a time, position-major (csm_schedule.h).
+  const auto sched_t0 = std::chrono::steady_clock::now();
+  const Schedule sched = BuildSchedule(q, pair_submap, pair_chunks, rc);
+  const double sched_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sched_t0).count();
+  const int64_t total_chunks = sched.items;
 
   // One device arena per launch (csm_context::arena): the inputs, uploaded
   // with one copy from pinned staging, then the outputs, zeroed with one
@@ -278,13 +254,11 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
     at = align(at + std::max<size_t>(bytes, 1));
     return o;
   };
-  // v1: pair_order | chunk_prefix; v4/v5: entries | rectangles | hints.
+  // Queue tables: entries | rectangles | hints.
   const size_t o_pd = region(sizeof(PairDesc) * np);
-  const size_t o_order = region(plan.use_v2 ? sizeof(SchedEntry) * sched.entries.size()
-                                            : sizeof(int32_t) * order.size()),
-               o_prefix = region(plan.use_v2 ? sizeof(SchedRect) * sched.rects.size()
-                                             : sizeof(int64_t) * prefix.size()),
-               o_blocks = region(sizeof(int32_t) * sched.hint.size());
+  const size_t o_entries = region(sizeof(SchedEntry) * sched.entries.size()),
+               o_rects = region(sizeof(SchedRect) * sched.rects.size()),
+               o_hint = region(sizeof(int32_t) * sched.hint.size());
   const size_t o_best = region(sizeof(uint64_t) * np), o_hi = region(sizeof(uint64_t) * np),
                o_status = region(sizeof(int32_t) * np), o_tcount = region(sizeof(int32_t) * np),
                o_counters = region(sizeof(unsigned long long) * kNumXcd);
@@ -300,14 +274,9 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
     return rcode;
   char* hin = ctx->arena_in.as<char>();
   std::memcpy(hin + o_pd, pdesc.data(), sizeof(PairDesc) * np);
-  if (plan.use_v2) {
-    std::memcpy(hin + o_order, sched.entries.data(), sizeof(SchedEntry) * sched.entries.size());
-    std::memcpy(hin + o_prefix, sched.rects.data(), sizeof(SchedRect) * sched.rects.size());
-    std::memcpy(hin + o_blocks, sched.hint.data(), sizeof(int32_t) * sched.hint.size());
-  } else {
-    std::memcpy(hin + o_order, order.data(), sizeof(int32_t) * order.size());
-    std::memcpy(hin + o_prefix, prefix.data(), sizeof(int64_t) * prefix.size());
-  }
+  std::memcpy(hin + o_entries, sched.entries.data(), sizeof(SchedEntry) * sched.entries.size());
+  std::memcpy(hin + o_rects, sched.rects.data(), sizeof(SchedRect) * sched.rects.size());
+  std::memcpy(hin + o_hint, sched.hint.data(), sizeof(int32_t) * sched.hint.size());
   if (init_best) std::memcpy(hin + o_best, init_best->data(), sizeof(uint64_t) * np);
   char* dev = ctx->arena.as<char>();
   hipStream_t st = ctx->stream;
@@ -321,61 +290,50 @@ int LaunchSearch(csm_context* ctx, csm_scan_set* scans, const std::vector<PairDe
   int32_t* d_tcount = reinterpret_cast<int32_t*>(dev + o_tcount);
   unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(dev + o_counters);
   unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(dev + o_stats);
-  wq.pair_order = reinterpret_cast<int32_t*>(dev + o_order);
-  wq.chunk_prefix = reinterpret_cast<int64_t*>(dev + o_prefix);
 
   // ---- launch: persistent workgroups ----------------------------------------
   const int max_npad = plan.max_npad;
   if (timed) CSM_HIP(hipEventRecord(ctx->ev0, st));
-  if (plan.use_v2) {
-    WorkQueues2 wq2 = sched.wq;
-    wq2.entries = reinterpret_cast<SchedEntry*>(dev + o_order);
-    wq2.rects = reinterpret_cast<SchedRect*>(dev + o_prefix);
-    wq2.hint = reinterpret_cast<int32_t*>(dev + o_blocks);
-    // Per rotation: npad raw cells and capc cluster-list entries. capc =
-    // 3/4 npad holds the three cluster lists of a typical scan (0.55 npad on
-    // C2); a list that does not fit falls back to a finer one in the kernel.
-    int capc = (3 * max_npad / 4 + 63) & ~63;
-    if (const char* ce = std::getenv("CSM_CAPC_PCT"))  // A/B: cluster-list room, % of npad
-      capc = std::max(64, (std::atoi(ce) * max_npad / 100 + 63) & ~63);
-    const int lds_cap = 96 * 1024;
-    // Per rotation: npad raw cells (4 B) + capc cluster entries (4 B cell + 1 B count).
-    auto dyn_bytes = [&](int cap) { return static_cast<size_t>(rc) * (max_npad * 4 + cap * 5); };
-    while (capc > 0 && dyn_bytes(capc) > lds_cap) capc -= 64;
-    const size_t dyn_lds = (dyn_bytes(capc) + 15) & ~size_t{15};
-    // Workgroups per CU: what registers and LDS allow (the runtime's
-    // occupancy query). CSM_WG_PER_CU caps it (A/B runs).
-    int per_cu = std::max(1, std::min(8, Fast2dSearchV2BlocksPerCu(plan.hex, plan.fifo, dyn_lds)));
-    if (const char* w = std::getenv("CSM_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(w)));
-    if (std::getenv("CSM_PROFILE2D") && !init_best)
-      std::fprintf(stderr, "fast2d launch: %s %s, %d rotations per item, %zu B dynamic LDS (capc %d), %d workgroups per CU; "
-                   "%lld items, %lld empty slots (%.3f %%), %zu rectangles, %zu hints, built in %.3f ms\n",
-                   plan.hex ? "v5" : "v4", plan.fifo ? "fifo" : "lifo", rc, dyn_lds, capc, per_cu,
-                   static_cast<long long>(sched.items), static_cast<long long>(sched.empty_slots),
-                   100.0 * sched.empty_slots / std::max<int64_t>(sched.items, 1), sched.rects.size(),
-                   sched.hint.size(), sched_ms);
-    // Concurrent single calls (call contexts, csm_internal.h) each take a
-    // share of the chip, so their persistent grids tile it instead of
-    // queueing behind one another (at least one workgroup per CU each).
-    const int64_t full = static_cast<int64_t>(ctx->num_cus) * per_cu;
-    const int64_t share = std::max<int64_t>(ctx->num_cus, full / std::max(1, ctx->grid_share));
-    const int grid = static_cast<int>(std::min<int64_t>(share, std::max<int64_t>(total_chunks, 1)));
-    // DFS stack spill: kSpill2 entries per persistent workgroup.
-    if ((rcode = ctx->spill.Reserve(sizeof(uint2) * kSpill2 * static_cast<size_t>(grid))))
-      return rcode;
-    CSM_HIP(LaunchFast2dSearchV2(grid, dyn_lds, st, ctx->submap_desc.as<SubmapDesc>(), d_pairs,
-                                 scans->points.as<float>(), scans->rot_dev.as<float2>(), wq2,
-                                 d_counters, d_best, d_status, d_stats, ctx->spill.as<uint2>(),
-                                 max_npad, capc, plan.hex, plan.fifo, d_hi,
-                                 ties ? ctx->ties.as<uint2>() : nullptr, d_tcount, ties != nullptr));
-  } else {
-    const size_t dyn_lds = static_cast<size_t>(rc) * max_npad * sizeof(uint32_t);
-    const int grid = static_cast<int>(std::min<int64_t>(static_cast<int64_t>(ctx->num_cus) * 4,
-                                                        std::max<int64_t>(total_chunks, 1)));
-    CSM_HIP(LaunchFast2dSearch(grid, dyn_lds, st, ctx->submap_desc.as<SubmapDesc>(), d_pairs,
-                               scans->points.as<float>(), scans->rot_dev.as<float2>(), wq,
-                               d_counters, d_best, d_status, d_stats));
-  }
+  WorkQueues2 wq2 = sched.wq;
+  wq2.entries = reinterpret_cast<SchedEntry*>(dev + o_entries);
+  wq2.rects = reinterpret_cast<SchedRect*>(dev + o_rects);
+  wq2.hint = reinterpret_cast<int32_t*>(dev + o_hint);
+  // Per rotation: npad raw cells and capc cluster-list entries. capc =
+  // 3/4 npad holds the three cluster lists of a typical scan (0.55 npad on
+  // C2); a list that does not fit falls back to a finer one in the kernel.
+  int capc = (3 * max_npad / 4 + 63) & ~63;
+  if (const char* ce = std::getenv("CSM_CAPC_PCT"))  // A/B: cluster-list room, % of npad
+    capc = std::max(64, (std::atoi(ce) * max_npad / 100 + 63) & ~63);
+  const int lds_cap = 96 * 1024;
+  // Per rotation: npad raw cells (4 B) + capc cluster entries (4 B cell + 1 B count).
+  auto dyn_bytes = [&](int cap) { return static_cast<size_t>(rc) * (max_npad * 4 + cap * 5); };
+  while (capc > 0 && dyn_bytes(capc) > lds_cap) capc -= 64;
+  const size_t dyn_lds = (dyn_bytes(capc) + 15) & ~size_t{15};
+  // Workgroups per CU: what registers and LDS allow (the runtime's
+  // occupancy query). CSM_WG_PER_CU caps it (A/B runs).
+  int per_cu = std::max(1, std::min(8, Fast2dSearchV2BlocksPerCu(plan.hex, plan.fifo, dyn_lds)));
+  if (const char* w = std::getenv("CSM_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(w)));
+  if (std::getenv("CSM_PROFILE2D") && !init_best)
+    std::fprintf(stderr, "fast2d launch: %s %s, %d rotations per item, %zu B dynamic LDS (capc %d), %d workgroups per CU; "
+                 "%lld items, %lld empty slots (%.3f %%), %zu rectangles, %zu hints, built in %.3f ms\n",
+                 plan.hex ? "v5" : "v4", plan.fifo ? "fifo" : "lifo", rc, dyn_lds, capc, per_cu,
+                 static_cast<long long>(sched.items), static_cast<long long>(sched.empty_slots),
+                 100.0 * sched.empty_slots / std::max<int64_t>(sched.items, 1), sched.rects.size(),
+                 sched.hint.size(), sched_ms);
+  // Concurrent single calls (call contexts, csm_internal.h) each take a
+  // share of the chip, so their persistent grids tile it instead of
+  // queueing behind one another (at least one workgroup per CU each).
+  const int64_t full = static_cast<int64_t>(ctx->num_cus) * per_cu;
+  const int64_t share = std::max<int64_t>(ctx->num_cus, full / std::max(1, ctx->grid_share));
+  const int grid = static_cast<int>(std::min<int64_t>(share, std::max<int64_t>(total_chunks, 1)));
+  // DFS stack spill: kSpill2 entries per persistent workgroup.
+  if ((rcode = ctx->spill.Reserve(sizeof(uint2) * kSpill2 * static_cast<size_t>(grid))))
+    return rcode;
+  CSM_HIP(LaunchFast2dSearchV2(grid, dyn_lds, st, ctx->submap_desc.as<SubmapDesc>(), d_pairs,
+                               scans->points.as<float>(), scans->rot_dev.as<float2>(), wq2,
+                               d_counters, d_best, d_status, d_stats, ctx->spill.as<uint2>(),
+                               max_npad, capc, plan.hex, plan.fifo, d_hi,
+                               ties ? ctx->ties.as<uint2>() : nullptr, d_tcount, ties != nullptr));
   if (timed) CSM_HIP(hipEventRecord(ctx->ev1, st));
   char* hout = ctx->arena_out.as<char>();
   CSM_HIP(hipMemcpyAsync(hout, dev + o_best, arena_bytes - o_best, hipMemcpyDeviceToHost, st));
@@ -931,22 +889,16 @@ int RunBatch(csm_context* ctx, csm_fast2d* const* submaps, int32_t num_submaps,
   const int np = static_cast<int>(pdesc.size());
   if (np == 0) return CSM_OK;
 
-  const char* forced_env = std::getenv("CSM_SEARCH_KERNEL");
-  const int forced = forced_env ? std::atoi(forced_env) : 0;
   SearchPlan plan;
-  // The v4/v5 kernel keeps rot_chunk discretized scans (4 B/point) and their
+  // The search kernel keeps rot_chunk discretized scans (4 B/point) and their
   // cluster lists in LDS: up to kMaxPoints (16448 points, one rotation per
-  // workgroup, ~128 KB) it fits, so it takes every batch; the v1 kernel
-  // (lanes = points) runs only when forced (CSM_SEARCH_KERNEL=1).
-  plan.use_v2 = forced != 1;
+  // workgroup, ~128 KB) it fits, so it takes every batch.
   plan.hex = hex;
   plan.max_npad = max_npad;
   const char* rc_env = std::getenv("CSM_ROT_CHUNK");
   const int v4_budget = 9 * 1024;  // C2 (1088 padded points): 2 rotations per chunk, the measured best
-  const int v4_rc = rc_env ? std::max(1, std::min(kV4MaxRotChunk, std::atoi(rc_env)))
-                           : std::max(1, std::min(std::min(8, kV4MaxRotChunk), v4_budget / (max_npad * 4)));
-  const int lds_budget = 40 * 1024;
-  plan.rc = plan.use_v2 ? v4_rc : std::max(1, std::min(16, lds_budget / (max_npad * 4)));
+  plan.rc = rc_env ? std::max(1, std::min(kV4MaxRotChunk, std::atoi(rc_env)))
+                   : std::max(1, std::min(std::min(8, kV4MaxRotChunk), v4_budget / (max_npad * 4)));
   // Node order: FIFO (level by level, the default) or LIFO (depth-first,
   // CSM_SEARCH_ORDER=lifo).
   const char* order_env = std::getenv("CSM_SEARCH_ORDER");
@@ -1040,8 +992,8 @@ int RunBatch(csm_context* ctx, csm_fast2d* const* submaps, int32_t num_submaps,
   const auto t_ties = std::chrono::steady_clock::now();
   const int64_t tied_before = ctx->t.tied_pairs;
   std::vector<int8_t> tie_code(np, CSM_TIE_NONE);
-  if (plan.use_v2 && (rcode = ResolveTies(ctx, submaps, scans, pdesc, rot_host, plan, &stat, keys_hi,
-                                           &keys, &tie_code)))
+  if ((rcode = ResolveTies(ctx, submaps, scans, pdesc, rot_host, plan, &stat, keys_hi, &keys,
+                           &tie_code)))
     return rcode;
   const double ties_ms = ms_since(t_ties);
   const auto t_decode = std::chrono::steady_clock::now();

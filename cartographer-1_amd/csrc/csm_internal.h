@@ -498,17 +498,20 @@ struct csm_hybrid_grid {
   csm::Brick3 brick{};
   csm::DevBuf values;    // uint16 brick
   csm::DevBuf prob;      // float probability brick
-  csm::DevBuf prob_pad;  // the same padded by one 0.1 cell per side (RTCSM3D), built on first use
-  bool prob_pad_ready = false;
-  csm::DevBuf prob_wide;  // padded by prob_wide_pad 0.1 cells per side (rt3d_score4)
-  int prob_wide_pad = 0;
-  csm::DevBuf prob_col;   // padded by prob_col_pad cells, z fastest (rt3d_score5)
-  int prob_col_pad = 0;
-  // Bumped by every insert that touches a cell; the padded copies above are
-  // those of the generation recorded next to them and are re-made when it
-  // differs (RunRt3d).
+  // Bumped by every insert that touches a cell.
   uint64_t generation = 0;
-  uint64_t prob_pad_gen = 0, prob_wide_gen = 0, prob_col_gen = 0;
+  // A copy of `prob` padded by `pad` cells of 0.1 per side (0: none yet), as
+  // of generation `gen`; RTCSM3D builds the one its kernel reads on first
+  // use and re-makes it when the pad or the generation differs
+  // (host3d.cc EnsurePaddedBrick).
+  struct PaddedBrick {
+    csm::DevBuf buf;
+    int pad = 0;
+    uint64_t gen = 0;
+  };
+  PaddedBrick prob_pad;   // one cell, x fastest (rt3d_score2)
+  PaddedBrick prob_wide;  // the window's reach + 2 cells, x fastest (rt3d_score4)
+  PaddedBrick prob_col;   // the same, z fastest (rt3d_score5)
   // csm_hybrid_grid_insert_stats' two counters, made by the first insert.
   csm::DevBuf insert_stats;
 };

@@ -2,12 +2,18 @@
 //
 //   K1  pyramid_level0 / pyramid_double — PrecomputationGridStack2D
 //       (fast_correlative_scan_matcher_2d.cc:91-186) built on the device.
-//   K2-K4 fast2d_search — per (pair, rotation chunk): discretize the rotated
-//       scan slice into LDS (correlative_scan_matcher_2d.cc:93-127 +
-//       map_limits.h:69-75), ShrinkToFit (:73-91), score the top-level lattice
-//       (fast_correlative_scan_matcher_2d.cc:264-333) and run an exact
-//       depth-first branch and bound per wave (:335-378) against a per-pair
+//   K1c pyramid_quad / pyramid_widen / pyramid_hex — the polyphase quad and
+//       hex planes the search gathers from.
+//   K2-K4 fast2d_search_v4 — per (pair, rotation chunk): discretize the
+//       rotated scan slice into LDS entry lists
+//       (correlative_scan_matcher_2d.cc:93-127 + map_limits.h:69-75),
+//       ShrinkToFit (:73-91), and run an exact branch and bound per workgroup
+//       (fast_correlative_scan_matcher_2d.cc:264-378) from virtual roots above
+//       the top-level lattice, in batches of nodes that score 2x2 children
+//       (v4) or 4x4 grandchildren (v5, kHex) per gather, against a per-pair
 //       incumbent shared through a 64-bit atomicMax.
+//   fast2d_score_queries / fast2d_walk / fast2d_rotation_bounds — tie
+//       resolution (csm_host.cc ResolveTies) over the row-major levels.
 // (RealTimeCorrelativeScanMatcher2D's kernels are in rt2d.hip.)
 //
 // Built with -ffp-contract=off; the discretization additionally uses the
@@ -103,7 +109,8 @@ __global__ void pyramid_double(const uint8_t* __restrict__ prev, int pnx, int pn
   next[static_cast<size_t>(ly) * nnx + lx] = static_cast<uint8_t>(v);
 }
 
-// ---------------------------------------------------------------- K2-K4 ----
+// ------------------------------------------------- row-major level scoring --
+// (fast2d_score_queries and fast2d_walk, below the search kernel.)
 
 struct LevelView {
   const uint8_t* data;
@@ -118,64 +125,6 @@ __device__ __forceinline__ LevelView MakeView(const SubmapDesc& s, int d) {
   v.zero = s.zero_index[d];
   v.bias = (1 << d) - 1;
   return v;
-}
-
-// Scores the (up to) four children (xo + {0,h}) x (yo + {0,h}) of one node
-// at level view L. Lanes walk the rotation's discretized points (packed
-// int16 pairs in LDS, padded with sentinels to a multiple of 64).
-__device__ __forceinline__ void ScoreChildren(const uint32_t* __restrict__ pts,
-                                              int npad, const LevelView& L,
-                                              int xo, int yo, int h, int out[4]) {
-  const int lane = threadIdx.x & 63;
-  int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-  const int hw = h * L.wnx;
-  // npad is a multiple of 64; take 4 points per lane per iteration so 16
-  // byte loads are in flight before any is consumed.
-  int i = lane;
-  for (; i + 192 < npad; i += 256) {
-    int ad[16];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t p = pts[i + 64 * u];
-      const int lx = static_cast<int>(static_cast<int16_t>(p & 0xffff)) + xo + L.bias;
-      const int lyy = (static_cast<int>(p) >> 16) + yo + L.bias;
-      const bool vx0 = static_cast<unsigned>(lx) < static_cast<unsigned>(L.wnx);
-      const bool vx1 = static_cast<unsigned>(lx + h) < static_cast<unsigned>(L.wnx);
-      const bool vy0 = static_cast<unsigned>(lyy) < static_cast<unsigned>(L.wny);
-      const bool vy1 = static_cast<unsigned>(lyy + h) < static_cast<unsigned>(L.wny);
-      const int base = lyy * L.wnx + lx;
-      ad[4 * u + 0] = (vx0 && vy0) ? base : L.zero;
-      ad[4 * u + 1] = (vx0 && vy1) ? base + hw : L.zero;
-      ad[4 * u + 2] = (vx1 && vy0) ? base + h : L.zero;
-      ad[4 * u + 3] = (vx1 && vy1) ? base + hw + h : L.zero;
-    }
-    int v[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = L.data[ad[u]];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      a0 += v[4 * u]; a1 += v[4 * u + 1]; a2 += v[4 * u + 2]; a3 += v[4 * u + 3];
-    }
-  }
-  for (; i < npad; i += 64) {
-    const uint32_t p = pts[i];
-    const int lx = static_cast<int>(static_cast<int16_t>(p & 0xffff)) + xo + L.bias;
-    const int ly = static_cast<int>(p) >> 16;
-    const int lyy = ly + yo + L.bias;
-    const bool vx0 = static_cast<unsigned>(lx) < static_cast<unsigned>(L.wnx);
-    const bool vx1 = static_cast<unsigned>(lx + h) < static_cast<unsigned>(L.wnx);
-    const bool vy0 = static_cast<unsigned>(lyy) < static_cast<unsigned>(L.wny);
-    const bool vy1 = static_cast<unsigned>(lyy + h) < static_cast<unsigned>(L.wny);
-    const int base = lyy * L.wnx + lx;
-    a0 += L.data[(vx0 && vy0) ? base : L.zero];
-    a1 += L.data[(vx0 && vy1) ? base + hw : L.zero];
-    a2 += L.data[(vx1 && vy0) ? base + h : L.zero];
-    a3 += L.data[(vx1 && vy1) ? base + hw + h : L.zero];
-  }
-  out[0] = WaveSum(a0);  // (xo,     yo)
-  out[1] = WaveSum(a1);  // (xo,     yo + h)
-  out[2] = WaveSum(a2);  // (xo + h, yo)
-  out[3] = WaveSum(a3);  // (xo + h, yo + h)
 }
 
 // Scores one candidate at level view L.
@@ -210,319 +159,6 @@ __device__ __forceinline__ int ScoreOne(const uint32_t* __restrict__ pts, int np
     acc += L.data[v ? ly * L.wnx + lx : L.zero];
   }
   return WaveSum(acc);
-}
-
-struct RotInfo {
-  int min_x, max_x, min_y, max_y;  // ShrinkToFit bounds
-  int top_begin;                   // prefix of top-level candidates
-  int top_nx, top_ny;
-  int pad;
-};
-
-// Stack entry: w0 = (uint16 xo) | (yo << 16); w1 = sum | rot << 22 | level << 27.
-__device__ __forceinline__ uint2 MakeEntry(int xo, int yo, int sum, int rot, int level) {
-  return make_uint2((static_cast<uint32_t>(xo) & 0xffff) | (static_cast<uint32_t>(yo) << 16),
-                    static_cast<uint32_t>(sum) | (static_cast<uint32_t>(rot) << 22) |
-                        (static_cast<uint32_t>(level) << 27));
-}
-
-__global__ void __launch_bounds__(kSearchThreads)
-fast2d_search(const SubmapDesc* __restrict__ submaps,
-              const PairDesc* __restrict__ pairs,
-              const float* __restrict__ points,        // xyz
-              const float2* __restrict__ rot_table,    // (w, s)
-              WorkQueues queues,
-              unsigned long long* __restrict__ counters,  // kNumXcd claim counters
-              uint64_t* __restrict__ best,            // per pair leaf key
-              int32_t* __restrict__ status,            // per pair
-              unsigned long long* __restrict__ stats)  // [0] candidates scored, [1] lookups
-{
-  extern __shared__ __align__(16) uint32_t lds_pts[];  // rot_chunk * npad_max
-  __shared__ RotInfo rinfo[32];
-  __shared__ uint2 stack[kWaves][kStackCap];
-  __shared__ uint32_t top_xy[kWaves][kTopChunk];
-  __shared__ int top_meta[kWaves][kTopChunk];  // sum | rot << 22
-  __shared__ int s_item_pair, s_item_chunk, s_total_top, s_next_chunk, s_queue;
-  __shared__ int s_mm[32][4];
-
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int rc = queues.rot_chunk;
-  unsigned long long local_cands = 0, local_lookups = 0;
-
-  if (tid == 0) s_queue = blockIdx.x % kNumXcd;
-  __syncthreads();
-  int tries = 0;
-  for (;;) {
-    // ---- claim a work item (pair, rotation chunk) from an XCD queue ------
-    if (tid == 0) {
-      int q = s_queue;
-      int pair = -1, chunk = 0;
-      while (tries < kNumXcd) {
-        const int64_t item = static_cast<int64_t>(atomicAdd(&counters[q], 1ull));
-        if (item < queues.queue_chunks[q]) {
-          // Binary search the pair whose chunk range holds `item`.
-          int lo = queues.queue_begin[q], hi = queues.queue_begin[q + 1] - 1;
-          const int64_t base = queues.chunk_prefix[queues.queue_begin[q]];
-          while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (queues.chunk_prefix[mid] - base <= item) lo = mid; else hi = mid - 1;
-          }
-          pair = queues.pair_order[lo];
-          chunk = static_cast<int>(item - (queues.chunk_prefix[lo] - base));
-          break;
-        }
-        q = (q + 1) % kNumXcd;  // own queue drained: help the next XCD's queue
-        ++tries;
-      }
-      s_queue = q;
-      s_item_pair = pair;
-      s_item_chunk = chunk;
-    }
-    __syncthreads();
-    const int pair_index = Uniform(s_item_pair);
-    if (pair_index < 0) break;
-    const PairDesc pd = pairs[pair_index];
-    const SubmapDesc& sm = submaps[pd.submap];
-    const int rot0 = Uniform(s_item_chunk) * rc;
-    const int nrot = min(rc, pd.num_scans - rot0);
-    const int n = pd.num_points;
-    const int npad = (n + 63) & ~63;
-
-    // ---- K2: discretize the chunk's rotated scans into LDS --------------
-    bool range_error = false;
-    for (int r = 0; r < nrot; ++r) {
-      const float2 q = rot_table[pd.rot_offset + rot0 + r];
-      int mnx = 0x7fffffff, mxx = -0x7fffffff, mny = 0x7fffffff, mxy = -0x7fffffff;
-      for (int i = tid; i < npad; i += kSearchThreads) {
-        uint32_t packed = (static_cast<uint32_t>(static_cast<uint16_t>(kSentinel))) |
-                          (static_cast<uint32_t>(static_cast<uint16_t>(kSentinel)) << 16);
-        if (i < n) {
-          const float* p = points + 3 * (pd.point_offset + i);
-          float x, y;
-          RotateZDev(pd.pre_w, pd.pre_s, p[0], p[1], &x, &y);
-          RotateZDev(q.x, q.y, x, y, &x, &y);
-          // Eigen::Affine2f(translation) * p == t + (1*x + 0*y) in float.
-          const float px = __fadd_rn(pd.tx, x);
-          const float py = __fadd_rn(pd.ty, y);
-          const double cx = CellCoord(sm.max_y, py, sm.resolution);
-          const double cy = CellCoord(sm.max_x, px, sm.resolution);
-          int ix = 0, iy = 0;
-          if (fabs(cx) > kIndexLimit || fabs(cy) > kIndexLimit) {
-            range_error = true;
-          } else {
-            ix = static_cast<int>(cx);
-            iy = static_cast<int>(cy);
-          }
-          mnx = min(mnx, ix); mxx = max(mxx, ix);
-          mny = min(mny, iy); mxy = max(mxy, iy);
-          packed = (static_cast<uint32_t>(ix) & 0xffff) | (static_cast<uint32_t>(iy) << 16);
-        }
-        lds_pts[r * npad + i] = packed;
-      }
-      mnx = WaveMin(mnx); mxx = WaveMax(mxx);
-      mny = WaveMin(mny); mxy = WaveMax(mxy);
-      if (lane == 0) {
-        if (wave == 0) { s_mm[r][0] = mnx; s_mm[r][1] = mxx; s_mm[r][2] = mny; s_mm[r][3] = mxy; }
-      }
-      __syncthreads();
-      if (lane == 0 && wave != 0) {
-        atomicMin(&s_mm[r][0], mnx); atomicMax(&s_mm[r][1], mxx);
-        atomicMin(&s_mm[r][2], mny); atomicMax(&s_mm[r][3], mxy);
-      }
-    }
-    if (range_error) atomicOr(&status[pair_index], kStatusRange);
-    __syncthreads();
-
-    // ---- ShrinkToFit + top-level lattice sizes -------------------------
-    const int top_level = sm.levels - 1;
-    const int step = 1 << top_level;
-    if (tid == 0) {
-      int total = 0;
-      for (int r = 0; r < nrot; ++r) {
-        RotInfo ri;
-        const int lo_x = min(0, -s_mm[r][1]), hi_x = max(0, sm.nx - 1 - s_mm[r][0]);
-        const int lo_y = min(0, -s_mm[r][3]), hi_y = max(0, sm.ny - 1 - s_mm[r][2]);
-        ri.min_x = max(-pd.num_linear, lo_x);
-        ri.max_x = min(pd.num_linear, hi_x);
-        ri.min_y = max(-pd.num_linear, lo_y);
-        ri.max_y = min(pd.num_linear, hi_y);
-        if (n == 0) { ri.min_x = ri.max_x = ri.min_y = ri.max_y = 0; }
-        ri.top_nx = (ri.max_x - ri.min_x + step) / step;
-        ri.top_ny = (ri.max_y - ri.min_y + step) / step;
-        ri.top_begin = total;
-        total += ri.top_nx * ri.top_ny;
-        rinfo[r] = ri;
-      }
-      s_total_top = total;
-      s_next_chunk = 0;
-    }
-    __syncthreads();
-
-    // ---- K3 + K4: top-level chunks, then depth-first branch and bound ---
-    const int total_top = s_total_top;
-    const int s_min = pd.max_rejected_sum;
-    uint64_t* pair_best = best + pair_index;
-    uint64_t cached = LoadBest(pair_best);
-    for (;;) {
-      int chunk = 0;
-      if (lane == 0) chunk = atomicAdd(&s_next_chunk, 1);
-      chunk = Uniform(chunk);
-      const int begin = chunk * kTopChunk;
-      if (begin >= total_top) break;
-      const int count = min(kTopChunk, total_top - begin);
-      const LevelView top = MakeView(sm, top_level);
-      // Score the chunk's candidates one after another (lanes = points).
-      for (int j = 0; j < count; ++j) {
-        const int t = begin + j;
-        int r = 0;
-        while (r + 1 < nrot && rinfo[r + 1].top_begin <= t) ++r;
-        const RotInfo& ri = rinfo[r];
-        const int k = t - ri.top_begin;
-        const int xo = ri.min_x + (k / ri.top_ny) * step;
-        const int yo = ri.min_y + (k % ri.top_ny) * step;
-        const int sum = ScoreOne(lds_pts + r * npad, npad, top, xo, yo);
-        if (lane == 0) {
-          top_xy[wave][j] = (static_cast<uint32_t>(xo) & 0xffff) | (static_cast<uint32_t>(yo) << 16);
-          top_meta[wave][j] = sum | (r << 22);
-        }
-      }
-      local_cands += count;
-      local_lookups += static_cast<unsigned long long>(count) * n;
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      const uint32_t best_sum = static_cast<uint32_t>(cached >> kSumShift);
-      // Keep candidates above min_score and not below the incumbent; sort
-      // them by bound, best on top of the stack.
-      int meta = lane < count ? top_meta[wave][lane] : 0;
-      int sum = meta & 0x3fffff;
-      const bool keep = lane < count && sum > s_min && static_cast<uint32_t>(sum) >= best_sum;
-      if (top_level == 0) {
-        // Depth-1 search: the top level is the leaf level.
-        uint64_t key = 0;
-        if (keep) {
-          const uint32_t xy = top_xy[wave][lane];
-          const int xo = static_cast<int16_t>(xy & 0xffff), yo = static_cast<int>(xy) >> 16;
-          key = PackLeafKey(sum, rot0 + (meta >> 22), xo, yo);
-        }
-        for (int m = 32; m >= 1; m >>= 1) {
-          const uint64_t o = __shfl_xor(key, m, 64);
-          key = o > key ? o : key;
-        }
-        if (key > cached) {
-          uint64_t old = 0;
-          if (lane == 0) old = atomicMax(reinterpret_cast<unsigned long long*>(pair_best), key);
-          old = __shfl(old, 0, 64);
-          cached = key > old ? key : old;
-        }
-        continue;
-      }
-      // Bitonic sort (descending) of (sum << 8 | lane) over the wave.
-      uint32_t skey = keep ? ((static_cast<uint32_t>(sum) << 8) | static_cast<uint32_t>(lane)) : 0u;
-      for (int k = 2; k <= 64; k <<= 1) {
-        for (int jj = k >> 1; jj >= 1; jj >>= 1) {
-          const uint32_t other = __shfl_xor(skey, jj, 64);
-          const bool up = ((lane & k) == 0);
-          const bool lower = ((lane & jj) == 0);
-          const uint32_t hi_v = skey > other ? skey : other;
-          const uint32_t lo_v = skey > other ? other : skey;
-          skey = (lower == up) ? hi_v : lo_v;
-        }
-      }
-      const int kept = __popcll(__ballot(keep));
-      int sp = 0;
-      if (lane < kept) {
-        const int j = skey & 0xff;
-        const uint32_t xy = top_xy[wave][j];
-        const int m2 = top_meta[wave][j];
-        // Largest sum at the highest stack slot.
-        stack[wave][kept - 1 - lane] =
-            make_uint2(xy, static_cast<uint32_t>(m2 & 0x3fffff) |
-                               (static_cast<uint32_t>(m2 >> 22) << 22) |
-                               (static_cast<uint32_t>(top_level) << 27));
-      }
-      sp = kept;
-      __builtin_amdgcn_wave_barrier();
-
-      // Depth-first branch and bound over this wave's stack.
-      int iter = 0;
-      while (sp > 0) {
-        --sp;
-        const uint2 e = stack[wave][sp];
-        const uint32_t e0 = Uniform(e.x), e1 = Uniform(e.y);
-        const int xo = static_cast<int16_t>(e0 & 0xffff);
-        const int yo = static_cast<int>(e0) >> 16;
-        const uint32_t bound = e1 & 0x3fffff;
-        const int r = (e1 >> 22) & 0x1f;
-        const int d = e1 >> 27;
-        if ((++iter & 7) == 0) {
-          uint64_t fresh = 0;
-          if (lane == 0) fresh = LoadBest(pair_best);
-          fresh = __shfl(fresh, 0, 64);
-          cached = fresh > cached ? fresh : cached;
-        }
-        if (bound < static_cast<uint32_t>(cached >> kSumShift)) continue;
-        const int h = 1 << (d - 1);
-        const RotInfo& ri = rinfo[r];
-        const bool hx = xo + h <= ri.max_x;
-        const bool hy = yo + h <= ri.max_y;
-        int sums[4];
-        const LevelView L = MakeView(sm, d - 1);
-        ScoreChildren(lds_pts + r * npad, npad, L, xo, yo, h, sums);
-        const int nchild = 1 + (hx ? 1 : 0) + (hy ? 1 : 0) + ((hx && hy) ? 1 : 0);
-        local_cands += nchild;
-        local_lookups += static_cast<unsigned long long>(nchild) * n;
-        const int cxo[4] = {xo, xo, xo + h, xo + h};
-        const int cyo[4] = {yo, yo + h, yo, yo + h};
-        const bool exists[4] = {true, hy, hx, hx && hy};
-        const uint32_t cur = static_cast<uint32_t>(cached >> kSumShift);
-        if (d - 1 == 0) {
-          uint64_t key = 0;
-          bool range_bad = false;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            if (!exists[c] || sums[c] <= s_min || static_cast<uint32_t>(sums[c]) < cur) continue;
-            if (cxo[c] < -kOffsetLimit || cxo[c] > kOffsetLimit || cyo[c] < -kOffsetLimit ||
-                cyo[c] > kOffsetLimit) { range_bad = true; continue; }
-            const uint64_t k2 = PackLeafKey(sums[c], rot0 + r, cxo[c], cyo[c]);
-            key = k2 > key ? k2 : key;
-          }
-          if (range_bad && lane == 0) atomicOr(&status[pair_index], kStatusRange);
-          if (key > cached) {
-            uint64_t old = 0;
-            if (lane == 0) old = atomicMax(reinterpret_cast<unsigned long long*>(pair_best), key);
-            old = __shfl(old, 0, 64);
-            cached = key > old ? key : old;
-          }
-        } else {
-          // Push surviving children, ascending by bound (best popped first).
-          int order[4];
-          int m = 0;
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            if (exists[c] && sums[c] > s_min && static_cast<uint32_t>(sums[c]) >= cur) order[m++] = c;
-          for (int a = 1; a < m; ++a) {  // insertion sort, ascending
-            const int v = order[a];
-            int b = a - 1;
-            while (b >= 0 && sums[order[b]] > sums[v]) { order[b + 1] = order[b]; --b; }
-            order[b + 1] = v;
-          }
-          if (lane < m) {
-            const int c = order[lane];
-            stack[wave][sp + lane] = MakeEntry(cxo[c], cyo[c], sums[c], r, d - 1);
-          }
-          sp += m;
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (stats && lane == 0) {
-    atomicAdd(&stats[0], local_cands);
-    atomicAdd(&stats[1], local_lookups);
-  }
 }
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t LevelRsrc(const uint8_t* base, int bytes) {
@@ -1906,15 +1542,6 @@ hipError_t LaunchPyramidDouble(const uint8_t* prev, int pnx, int pny, uint8_t* n
                                int nny, int h, hipStream_t st) {
   hipLaunchKernelGGL(pyramid_double, dim3((nnx + 255) / 256, nny), dim3(256), 0, st, prev, pnx, pny,
                      next, nnx, nny, h);
-  return hipGetLastError();
-}
-
-hipError_t LaunchFast2dSearch(int grid, size_t dyn_lds, hipStream_t st, const SubmapDesc* submaps,
-                              const PairDesc* pairs, const float* points, const float2* rot_table,
-                              const WorkQueues& queues, unsigned long long* counters,
-                              uint64_t* best, int32_t* status, unsigned long long* stats) {
-  hipLaunchKernelGGL(fast2d_search, dim3(grid), dim3(kSearchThreads), dyn_lds, st, submaps, pairs,
-                     points, rot_table, queues, counters, best, status, stats);
   return hipGetLastError();
 }
 

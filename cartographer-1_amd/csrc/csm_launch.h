@@ -12,10 +12,6 @@ hipError_t LaunchPyramidLevel0(const uint16_t* cells, const uint8_t* qtab, uint8
                                hipStream_t st);
 hipError_t LaunchPyramidDouble(const uint8_t* prev, int pnx, int pny, uint8_t* next, int nnx,
                                int nny, int h, hipStream_t st);
-hipError_t LaunchFast2dSearch(int grid, size_t dyn_lds, hipStream_t st, const SubmapDesc* submaps,
-                              const PairDesc* pairs, const float* points, const float2* rot_table,
-                              const WorkQueues& queues, unsigned long long* counters,
-                              uint64_t* best, int32_t* status, unsigned long long* stats);
 hipError_t LaunchPyramidQuad(const uint8_t* level, int wnx, int wny, int log_h, int km1,
                              uint32_t* out, int qw, int qh, int pws, int pph, int total,
                              hipStream_t st);

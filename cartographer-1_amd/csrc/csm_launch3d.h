@@ -43,30 +43,24 @@ hipError_t LaunchRt3dScore(int num_rot, hipStream_t st, const float* prob, const
                            float res, const float* points, int n, const float4* rot,
                            const float* rot_angle, const float4* trans, int num_trans, int t_base,
                            double wt, double wr, unsigned long long* best);
-// rt3d_score2 over a brick padded by one 0.1 cell per side (LaunchPadProbBrick
-// builds it); gb is the unpadded brick. num_trans <= kRt3dThreads.
-hipError_t LaunchPadProbBrick(const float* prob, const Brick3& gb, float* out, hipStream_t st);
+// The probability brick padded by P cells of 0.1 per side, x fastest.
+hipError_t LaunchPadProbBrickP(const float* prob, const Brick3& gb, int P, float* out,
+                               hipStream_t st);
+// rt3d_score2 over the brick padded by one cell per side; gb is the unpadded
+// brick. num_trans <= kRt3dThreads.
 hipError_t LaunchRt3dScore2( int num_rot, hipStream_t st, const float* pad,
                             const Brick3& gb, float res, const float* points, int n,
                             const float4* rot, const float* rot_angle, const float4* trans,
                             int num_trans, int t_base, double wt, double wr,
                             unsigned long long* best, float* scores = nullptr,
                             int scores_pitch = 0);
-// rt3d_score3 (same padded brick; byte offsets below 2^24): pre-scaled points
-// and translations, eps = bound on the fast cell coordinate's error.
-hipError_t LaunchRt3dScore3(int num_rot, hipStream_t st, const float* pad, const Brick3& gb,
-                            float res, float eps, const float* points, int n, const float4* rot,
-                            const float* rot_angle, const float4* trans, int num_trans, int t_base,
-                            double wt, double wr, unsigned long long* best, float* scores,
-                            int scores_pitch);
 // rt3d_score4: lanes = 64 rotations of a 4 x 4 x 4 block of the angular
 // lattice (rot / rot_index in block order, index -1 for holes), waves =
-// translations. `pad` is the brick padded by P cells per side (LaunchPadProbBrick
-// with P); points whose scaled rotation lies outside [safe_lo, safe_hi] take
-// the clamped path.
+// translations. `pad` is the brick padded by P cells per side
+// (LaunchPadProbBrickP); points whose scaled rotation lies outside [safe_lo,
+// safe_hi] take the clamped path. Pre-scaled points and translations; eps =
+// bound on the fast cell coordinate's error.
 constexpr int kRt4Waves = 8, kRt4Tw = 2, kRt4Tile = 32;
-hipError_t LaunchPadProbBrickP(const float* prob, const Brick3& gb, int P, float* out,
-                               hipStream_t st);
 hipError_t LaunchRt3dScore4(int num_blocks, hipStream_t st, const float* pad, const Brick3& gb,
                             int P, float res, float eps, float4 safe_lo, float4 safe_hi,
                             const float* points, int n, const float4* rot, const int* rot_index,

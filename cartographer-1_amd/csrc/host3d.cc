@@ -35,6 +35,7 @@
 #include "csm_internal.h"
 #include "csm_launch3d.h"
 #include "parallel_sort.h"
+#include "rt3d_select.h"
 
 using namespace csm;
 
@@ -482,6 +483,239 @@ int MakeRt3dWindow(const csm_rt_options* o, float res, const csm_pose3d* initial
   return CSM_OK;
 }
 
+// The best kernel the environment allows (read per call; the tests set the
+// variables per test): CSM_RT3D_V4 no columns, CSM_RT3D_V2 no rotation lanes,
+// CSM_RT3D_V1 the plain kernel only.
+Rt3dKernel Rt3dKernelCap() {
+  if (std::getenv("CSM_RT3D_V1")) return Rt3dKernel::kPlain;
+  if (std::getenv("CSM_RT3D_V2")) return Rt3dKernel::kPadded;
+  if (std::getenv("CSM_RT3D_V4")) return Rt3dKernel::kRotLanes;
+  return Rt3dKernel::kColumns;
+}
+
+// Makes *b the grid's probability brick padded by `pad` cells per side, x or
+// z fastest, unless it already is.
+int EnsurePaddedBrick(const csm_hybrid_grid* grid, csm_hybrid_grid::PaddedBrick* b, int pad,
+                      bool z_fastest, hipStream_t st) {
+  if (b->pad == pad && b->gen == grid->generation) return CSM_OK;
+  const Brick3& gb = grid->brick;
+  int rc;
+  if ((rc = b->buf.Reserve(sizeof(float) * (gb.nx + 2 * pad) * (gb.ny + 2 * pad) *
+                           (gb.nz + 2 * pad))))
+    return rc;
+  CSM_HIP((z_fastest ? LaunchPadProbBrickZ : LaunchPadProbBrickP)(grid->prob.as<float>(), gb, pad,
+                                                                  b->buf.as<float>(), st));
+  b->pad = pad;
+  b->gen = grid->generation;
+  return CSM_OK;
+}
+
+// One RunRt3d call's inputs, as its kernel families take them.
+struct Rt3dJob {
+  csm_context* ctx;
+  const csm_rt_options* o;
+  csm_hybrid_grid* grid;  // its padded bricks are caches
+  const float* xyz;
+  int32_t n;
+  const Rt3dWindow* w;
+  const float4* rot;  // host; drot / dangle: the same and the angles on the device
+  int64_t num_rot;
+  const float4* drot;
+  const float* dangle;
+  float* dscores;
+};
+
+// Translation lanes (rt3d_score over the brick, rt3d_score2 over the brick
+// padded by one cell): kRt3dThreads translations per launch.
+int ScoreTranslationLanes(const Rt3dJob& j, bool padded) {
+  csm_context* ctx = j.ctx;
+  hipStream_t st = ctx->stream;
+  const Brick3& gb = j.grid->brick;
+  int rc;
+  if (padded && (rc = EnsurePaddedBrick(j.grid, &j.grid->prob_pad, 1, false, st))) return rc;
+  if (ctx->timing) CSM_HIP(hipEventRecord(ctx->ev0, st));
+  const int64_t num_trans = j.w->num_trans;
+  for (int64_t t0 = 0; t0 < num_trans; t0 += kRt3dThreads) {
+    const int cnt = static_cast<int>(std::min<int64_t>(kRt3dThreads, num_trans - t0));
+    if (padded)
+      CSM_HIP(LaunchRt3dScore2(static_cast<int>(j.num_rot), st, j.grid->prob_pad.buf.as<float>(), gb,
+                               j.grid->resolution, ctx->rt3_points.as<float>(), j.n, j.drot,
+                               j.dangle, ctx->rt3_trans.as<float4>(), cnt, static_cast<int>(t0),
+                               j.o->translation_delta_cost_weight,
+                               j.o->rotation_delta_cost_weight,
+                               ctx->rt3_best.as<unsigned long long>(), j.dscores,
+                               static_cast<int>(num_trans)));
+    else
+      CSM_HIP(LaunchRt3dScore(static_cast<int>(j.num_rot), st, j.grid->prob.as<float>(), gb,
+                              j.grid->resolution, ctx->rt3_points.as<float>(), j.n, j.drot, j.dangle,
+                              ctx->rt3_trans.as<float4>(), cnt, static_cast<int>(t0),
+                              j.o->translation_delta_cost_weight, j.o->rotation_delta_cost_weight,
+                              ctx->rt3_best.as<unsigned long long>()));
+  }
+  return CSM_OK;
+}
+
+// Rotations in 4 x 4 x 4 blocks of the (rx, ry, rz) lattice (one block per
+// 64 lanes; holes past the lattice edge carry index -1), or in the given
+// order for a subset. Uploaded to ctx->rt3_rot4: the rotations, then the
+// indices.
+int UploadRotationBlocks(const Rt3dJob& j, bool lattice, const float4** drot4, const int32_t** didx,
+                         int* num_blocks) {
+  std::vector<float4> brot;
+  std::vector<int32_t> bidx;
+  if (lattice) {
+    const int64_t na = j.w->na, nb = (na + 3) / 4;
+    brot.assign(static_cast<size_t>(nb * nb * nb * 64), make_float4(0.f, 0.f, 0.f, 1.f));
+    bidx.assign(brot.size(), -1);
+    int64_t slot = 0;
+    for (int64_t bz = 0; bz < nb; ++bz)
+      for (int64_t by = 0; by < nb; ++by)
+        for (int64_t bx = 0; bx < nb; ++bx)
+          for (int lane = 0; lane < 64; ++lane, ++slot) {
+            const int64_t rx = 4 * bx + (lane & 3), ry = 4 * by + ((lane >> 2) & 3),
+                          rz = 4 * bz + (lane >> 4);
+            if (rx >= na || ry >= na || rz >= na) continue;
+            const int64_t r = (rz * na + ry) * na + rx;
+            brot[slot] = j.rot[r];
+            bidx[slot] = static_cast<int32_t>(r);
+          }
+  } else {
+    brot.assign(static_cast<size_t>((j.num_rot + 63) / 64 * 64), make_float4(0.f, 0.f, 0.f, 1.f));
+    bidx.assign(brot.size(), -1);
+    for (int64_t r = 0; r < j.num_rot; ++r) {
+      brot[r] = j.rot[r];
+      bidx[r] = static_cast<int32_t>(r);
+    }
+  }
+  csm_context* ctx = j.ctx;
+  int rc;
+  if ((rc = ctx->rt3_rot4.Reserve(sizeof(float4) * brot.size() + sizeof(int32_t) * bidx.size())))
+    return rc;
+  float4* d4 = ctx->rt3_rot4.as<float4>();
+  int32_t* di = reinterpret_cast<int32_t*>(d4 + brot.size());
+  CSM_HIP(hipMemcpyAsync(d4, brot.data(), sizeof(float4) * brot.size(), hipMemcpyHostToDevice,
+                         ctx->stream));
+  CSM_HIP(hipMemcpyAsync(di, bidx.data(), sizeof(int32_t) * bidx.size(), hipMemcpyHostToDevice,
+                         ctx->stream));
+  *drot4 = d4;
+  *didx = di;
+  *num_blocks = static_cast<int>(brot.size() / 64);
+  return CSM_OK;
+}
+
+// rt3d_score5's tables, uploaded to ctx->rt3_cols: per (x, y) column of the
+// translation lattice, step 0's scaled translation, then the per-axis
+// thresholds half - drift - allowance (drift: the largest |t'(k) - t'(0) -
+// k e_z|; allowance: the two float adds' rounding, 2^-22 (|a'| + |t'| + 1)).
+// amax: the cloud's largest norm.
+int UploadColumnTables(const Rt3dJob& j, float amax, float eps, const float4** col_t0,
+                       const float4** col_thr) {
+  const Rt3dWindow& w = *j.w;
+  const float res = j.grid->resolution, inv = 1.f / res;
+  const int nl = static_cast<int>(w.nl);
+  float tmaxs = 0.f;
+  for (const float4& t : w.trans)
+    tmaxs = std::max({tmaxs, std::fabs(t.x * inv), std::fabs(t.y * inv), std::fabs(t.z * inv)});
+  const float allow = static_cast<float>(
+      std::ldexp(1.0, -22) * (static_cast<double>(amax) * 1.001 / res + tmaxs + 1.0));
+  const float half = 0.5f - eps;
+  const int cols = nl * nl;
+  std::vector<float4> ct0(static_cast<size_t>(cols)), cth(static_cast<size_t>(cols));
+  for (int c = 0; c < cols; ++c) {
+    const float4 T0 = w.trans[c];
+    const float b0[3] = {T0.x * inv, T0.y * inv, T0.z * inv};
+    float dev[3] = {0.f, 0.f, 0.f};
+    for (int k = 1; k < nl; ++k) {
+      const float4 T = w.trans[static_cast<int64_t>(k) * cols + c];
+      const float bk[3] = {T.x * inv, T.y * inv, T.z * inv};
+      dev[0] = std::max(dev[0], std::fabs(bk[0] - b0[0]));
+      dev[1] = std::max(dev[1], std::fabs(bk[1] - b0[1]));
+      dev[2] = std::max(dev[2], std::fabs(static_cast<float>(
+                                    static_cast<double>(bk[2]) - b0[2] - k)));
+    }
+    ct0[c] = make_float4(b0[0], b0[1], b0[2], 0.f);
+    cth[c] = make_float4(half - dev[0] - allow, half - dev[1] - allow, half - dev[2] - allow,
+                         0.f);
+  }
+  csm_context* ctx = j.ctx;
+  int rc;
+  if ((rc = ctx->rt3_cols.Reserve(sizeof(float4) * 2 * cols))) return rc;
+  float4* d = ctx->rt3_cols.as<float4>();
+  CSM_HIP(hipMemcpyAsync(d, ct0.data(), sizeof(float4) * cols, hipMemcpyHostToDevice, ctx->stream));
+  CSM_HIP(hipMemcpyAsync(d + cols, cth.data(), sizeof(float4) * cols, hipMemcpyHostToDevice,
+                         ctx->stream));
+  *col_t0 = d;
+  *col_thr = d + cols;
+  return CSM_OK;
+}
+
+// Rotation lanes (rt3d_score4 over the brick padded by P cells; rt3d_score5,
+// `columns`, over the same brick z fastest with its column tables).
+int ScoreRotationLanes(const Rt3dJob& j, bool columns, int P, bool lattice) {
+  csm_context* ctx = j.ctx;
+  hipStream_t st = ctx->stream;
+  const Rt3dWindow& w = *j.w;
+  const Brick3& gb = j.grid->brick;
+  const float res = j.grid->resolution;
+  int rc;
+  csm_hybrid_grid::PaddedBrick* brick = columns ? &j.grid->prob_col : &j.grid->prob_wide;
+  if ((rc = EnsurePaddedBrick(j.grid, brick, P, columns, st))) return rc;
+  // |(a' + tr') - fl(fl(a + tr) / res)| <= 2.5 * 2^-23 * (|a| + |tr|) / res
+  // (the fast cell rule, kernels3d.hip); the threshold takes
+  // 4 * 2^-23 * (A + T + 1).
+  float amax = 0.f, tmax = 0.f;
+  for (int i = 0; i < j.n; ++i)
+    amax = std::max(amax, NormV(V3{j.xyz[3 * i], j.xyz[3 * i + 1], j.xyz[3 * i + 2]}));
+  for (const float4& t : w.trans)
+    tmax = std::max({tmax, std::fabs(t.x), std::fabs(t.y), std::fabs(t.z)});
+  const float eps = static_cast<float>(4.0 * std::ldexp(1.0, -23) *
+                                       (static_cast<double>(amax) * 1.001 / res + tmax / res + 1.0));
+  const float4* drot4 = nullptr;
+  const int32_t* didx = nullptr;
+  int num_blocks = 0;
+  if ((rc = UploadRotationBlocks(j, lattice, &drot4, &didx, &num_blocks))) return rc;
+  // The scaled rotated point a' keeps rint(a' + t') inside the padded box
+  // for every translation t' when a' + min t' >= lo and a' + max t' <= hi
+  // per axis (a margin covers the add's rounding).
+  float tmin[3] = {0.f, 0.f, 0.f}, tmax3[3] = {0.f, 0.f, 0.f};
+  const float inv = 1.f / res;
+  for (int64_t t = 0; t < w.num_trans; ++t) {
+    const float v[3] = {w.trans[t].x * inv, w.trans[t].y * inv, w.trans[t].z * inv};
+    for (int a = 0; a < 3; ++a) {
+      tmin[a] = t == 0 ? v[a] : std::min(tmin[a], v[a]);
+      tmax3[a] = t == 0 ? v[a] : std::max(tmax3[a], v[a]);
+    }
+  }
+  const int org[3] = {gb.ox, gb.oy, gb.oz}, dim[3] = {gb.nx, gb.ny, gb.nz};
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = static_cast<float>(org[a] - P) - tmin[a] + 0.01f;
+    hi[a] = static_cast<float>(org[a] - P + dim[a] + 2 * P - 1) - tmax3[a] - 0.01f;
+  }
+  const float4 safe_lo = make_float4(lo[0], lo[1], lo[2], 0.f),
+               safe_hi = make_float4(hi[0], hi[1], hi[2], 0.f);
+  const int num_trans = static_cast<int>(w.num_trans);
+  if (columns) {
+    const float4 *col_t0 = nullptr, *col_thr = nullptr;
+    if ((rc = UploadColumnTables(j, amax, eps, &col_t0, &col_thr))) return rc;
+    if (ctx->timing) CSM_HIP(hipEventRecord(ctx->ev0, st));
+    CSM_HIP(LaunchRt3dScore5(static_cast<int>(w.nl), num_blocks, st, brick->buf.as<float>(), gb, P,
+                             res, eps, safe_lo, safe_hi, ctx->rt3_points.as<float>(), j.n, drot4,
+                             didx, j.dangle, ctx->rt3_trans.as<float4>(), col_t0, col_thr,
+                             static_cast<int>(j.num_rot), j.o->translation_delta_cost_weight,
+                             j.o->rotation_delta_cost_weight,
+                             ctx->rt3_best.as<unsigned long long>(), j.dscores, num_trans));
+  } else {
+    if (ctx->timing) CSM_HIP(hipEventRecord(ctx->ev0, st));
+    CSM_HIP(LaunchRt3dScore4(num_blocks, st, brick->buf.as<float>(), gb, P, res, eps, safe_lo,
+                             safe_hi, ctx->rt3_points.as<float>(), j.n, drot4, didx, j.dangle,
+                             ctx->rt3_trans.as<float4>(), num_trans, static_cast<int>(j.num_rot),
+                             j.o->translation_delta_cost_weight, j.o->rotation_delta_cost_weight,
+                             ctx->rt3_best.as<unsigned long long>(), j.dscores, num_trans));
+  }
+  return CSM_OK;
+}
+
 // Scores the window's candidates over `rot` (num_rot of the window's
 // rotations, angles alongside): the best key (scores == nullptr) or every
 // candidate's score into the device array scores[r * num_trans + t].
@@ -505,209 +739,26 @@ int RunRt3d(csm_context* ctx, const csm_rt_options* o, const csm_hybrid_grid* gr
   CSM_HIP(hipMemcpyAsync(ctx->rt3_points.ptr, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice,
                          st));
   CSM_HIP(hipMemsetAsync(ctx->rt3_best.ptr, 0, sizeof(unsigned long long), st));
+  // The rotation-lane kernels read a brick padded by P cells: the translation
+  // lattice's reach in cells + 2.
+  float reach = 0.f;
+  const float4 c = w.trans[w.num_trans / 2];  // the centre: initial translation
+  for (const float4& t : w.trans)
+    reach = std::max({reach, std::fabs(t.x - c.x), std::fabs(t.y - c.y), std::fabs(t.z - c.z)});
+  const int P = static_cast<int>(std::ceil(reach / res)) + 2;
   const Brick3& gb = grid->brick;
-  // v2 addresses the padded brick with 24-bit row products and a 32-bit byte
-  // offset; larger bricks take the v1 kernel (no scoring mode).
-  const bool v2 = !std::getenv("CSM_RT3D_V1") &&
-                  static_cast<int64_t>(gb.nx + 2) * (gb.ny + 2) * (gb.nz + 2) < (int64_t{1} << 29) &&
-                  static_cast<int64_t>(gb.ny + 2) * (gb.nz + 2) < (int64_t{1} << 24);
-  if (dscores && !v2) return CSM_ERANGE;
-  if (v2 && (!grid->prob_pad_ready || grid->prob_pad_gen != grid->generation)) {
-    csm_hybrid_grid* g = const_cast<csm_hybrid_grid*>(grid);
-    if ((rc = g->prob_pad.Reserve(sizeof(float) * (gb.nx + 2) * (gb.ny + 2) * (gb.nz + 2))))
-      return rc;
-    CSM_HIP(LaunchPadProbBrick(grid->prob.as<float>(), gb, g->prob_pad.as<float>(), st));
-    g->prob_pad_ready = true;
-    g->prob_pad_gen = grid->generation;
-  }
-  // v4 (rotation lanes) over a brick padded by P cells, P = the translation
-  // lattice's reach in cells + 2, when its byte offsets are exact in float.
-  int P = 0;
-  {
-    float reach = 0.f;
-    const float4 c = w.trans[w.num_trans / 2];  // the centre: initial translation
-    for (const float4& t : w.trans)
-      reach = std::max({reach, std::fabs(t.x - c.x), std::fabs(t.y - c.y), std::fabs(t.z - c.z)});
-    P = static_cast<int>(std::ceil(reach / res)) + 2;
-  }
-  const bool v4 = v2 && !std::getenv("CSM_RT3D_V3") && !std::getenv("CSM_RT3D_V2") &&
-                  4 * static_cast<int64_t>(gb.nx + 2 * P) * (gb.ny + 2 * P) * (gb.nz + 2 * P) <
-                      (int64_t{1} << 24);
-  // v3 when the padded brick's byte offsets are exact in float (< 2^24).
-  const bool v3 = v2 && !v4 && !std::getenv("CSM_RT3D_V2") &&
-                  4 * static_cast<int64_t>(gb.nx + 2) * (gb.ny + 2) * (gb.nz + 2) < (int64_t{1} << 24);
-  // |(a' + tr') - fl(fl(a + tr) / res)| <= 2.5 * 2^-23 * (|a| + |tr|) / res
-  // (rt3d_score3); the threshold takes 4 * 2^-23 * (A + T + 1).
-  float eps = 0.f;
-  if (v3 || v4) {
-    float amax = 0.f, tmax = 0.f;
-    for (int i = 0; i < n; ++i)
-      amax = std::max(amax, NormV(V3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]}));
-    for (const float4& t : w.trans)
-      tmax = std::max({tmax, std::fabs(t.x), std::fabs(t.y), std::fabs(t.z)});
-    eps = static_cast<float>(4.0 * std::ldexp(1.0, -23) *
-                             (static_cast<double>(amax) * 1.001 / res + tmax / res + 1.0));
-  }
-  if (v4) {
-    csm_hybrid_grid* g = const_cast<csm_hybrid_grid*>(grid);
-    if (g->prob_wide_pad != P || g->prob_wide_gen != g->generation) {
-      if ((rc = g->prob_wide.Reserve(sizeof(float) * (gb.nx + 2 * P) * (gb.ny + 2 * P) *
-                                     (gb.nz + 2 * P))))
-        return rc;
-      CSM_HIP(LaunchPadProbBrickP(grid->prob.as<float>(), gb, P, g->prob_wide.as<float>(), st));
-      g->prob_wide_pad = P;
-      g->prob_wide_gen = g->generation;
-    }
-    // Rotations in 4 x 4 x 4 blocks of the (rx, ry, rz) lattice (one block
-    // per 64 lanes; holes past the lattice edge carry index -1), or in the
-    // given order for a subset.
-    std::vector<float4> brot;
-    std::vector<int32_t> bidx;
-    if (lattice) {
-      const int64_t na = w.na, nb = (na + 3) / 4;
-      brot.assign(static_cast<size_t>(nb * nb * nb * 64), make_float4(0.f, 0.f, 0.f, 1.f));
-      bidx.assign(brot.size(), -1);
-      int64_t slot = 0;
-      for (int64_t bz = 0; bz < nb; ++bz)
-        for (int64_t by = 0; by < nb; ++by)
-          for (int64_t bx = 0; bx < nb; ++bx)
-            for (int lane = 0; lane < 64; ++lane, ++slot) {
-              const int64_t rx = 4 * bx + (lane & 3), ry = 4 * by + ((lane >> 2) & 3),
-                            rz = 4 * bz + (lane >> 4);
-              if (rx >= na || ry >= na || rz >= na) continue;
-              const int64_t r = (rz * na + ry) * na + rx;
-              brot[slot] = rot[r];
-              bidx[slot] = static_cast<int32_t>(r);
-            }
-    } else {
-      brot.assign(static_cast<size_t>((num_rot + 63) / 64 * 64), make_float4(0.f, 0.f, 0.f, 1.f));
-      bidx.assign(brot.size(), -1);
-      for (int64_t r = 0; r < num_rot; ++r) {
-        brot[r] = rot[r];
-        bidx[r] = static_cast<int32_t>(r);
-      }
-    }
-    // The scaled rotated point a' keeps rint(a' + t') inside the padded box
-    // for every translation t' when a' + min t' >= lo and a' + max t' <= hi
-    // per axis (a margin covers the add's rounding).
-    float tmin[3] = {0.f, 0.f, 0.f}, tmax3[3] = {0.f, 0.f, 0.f};
-    const float inv = 1.f / res;
-    for (int64_t t = 0; t < num_trans; ++t) {
-      const float v[3] = {w.trans[t].x * inv, w.trans[t].y * inv, w.trans[t].z * inv};
-      for (int a = 0; a < 3; ++a) {
-        tmin[a] = t == 0 ? v[a] : std::min(tmin[a], v[a]);
-        tmax3[a] = t == 0 ? v[a] : std::max(tmax3[a], v[a]);
-      }
-    }
-    const int org[3] = {gb.ox, gb.oy, gb.oz}, dim[3] = {gb.nx, gb.ny, gb.nz};
-    float lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = static_cast<float>(org[a] - P) - tmin[a] + 0.01f;
-      hi[a] = static_cast<float>(org[a] - P + dim[a] + 2 * P - 1) - tmax3[a] - 0.01f;
-    }
-    const size_t rot_bytes = sizeof(float4) * brot.size() + sizeof(int32_t) * bidx.size();
-    if ((rc = ctx->rt3_rot4.Reserve(rot_bytes))) return rc;
-    float4* drot4 = ctx->rt3_rot4.as<float4>();
-    int32_t* didx = reinterpret_cast<int32_t*>(drot4 + brot.size());
-    CSM_HIP(hipMemcpyAsync(drot4, brot.data(), sizeof(float4) * brot.size(), hipMemcpyHostToDevice,
-                           st));
-    CSM_HIP(hipMemcpyAsync(didx, bidx.data(), sizeof(int32_t) * bidx.size(), hipMemcpyHostToDevice,
-                           st));
-    // v5 (column gathers) for z columns of 3 to 15 steps (one wave per
-    // column, nl waves per workgroup; wider windows run v4).
-    const int nl = static_cast<int>(w.nl);
-    const bool v5 = !std::getenv("CSM_RT3D_V4") && nl >= 3 && nl <= 15 && (nl & 1);
-    if (v5) {
-      csm_hybrid_grid* g = const_cast<csm_hybrid_grid*>(grid);
-      if (g->prob_col_pad != P || g->prob_col_gen != g->generation) {
-        if ((rc = g->prob_col.Reserve(sizeof(float) * (gb.nx + 2 * P) * (gb.ny + 2 * P) *
-                                      (gb.nz + 2 * P))))
-          return rc;
-        CSM_HIP(LaunchPadProbBrickZ(grid->prob.as<float>(), gb, P, g->prob_col.as<float>(), st));
-        g->prob_col_pad = P;
-        g->prob_col_gen = g->generation;
-      }
-      // Per column: step 0's scaled translation and the per-axis thresholds
-      // half - drift - allowance (drift: the largest |t'(k) - t'(0) - k e_z|;
-      // allowance: the two float adds' rounding, 2^-22 (|a'| + |t'| + 1)).
-      float amax = 0.f, tmaxs = 0.f;
-      for (int i = 0; i < n; ++i)
-        amax = std::max(amax, NormV(V3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]}));
-      for (int64_t t = 0; t < num_trans; ++t)
-        tmaxs = std::max({tmaxs, std::fabs(w.trans[t].x * inv), std::fabs(w.trans[t].y * inv),
-                          std::fabs(w.trans[t].z * inv)});
-      const float allow = static_cast<float>(
-          std::ldexp(1.0, -22) * (static_cast<double>(amax) * 1.001 / res + tmaxs + 1.0));
-      const float half = 0.5f - eps;
-      const int cols = nl * nl;
-      std::vector<float4> ct0(static_cast<size_t>(cols)), cth(static_cast<size_t>(cols));
-      for (int c = 0; c < cols; ++c) {
-        const float4 T0 = w.trans[c];
-        const float b0[3] = {T0.x * inv, T0.y * inv, T0.z * inv};
-        float dev[3] = {0.f, 0.f, 0.f};
-        for (int k = 1; k < nl; ++k) {
-          const float4 T = w.trans[static_cast<int64_t>(k) * cols + c];
-          const float bk[3] = {T.x * inv, T.y * inv, T.z * inv};
-          dev[0] = std::max(dev[0], std::fabs(bk[0] - b0[0]));
-          dev[1] = std::max(dev[1], std::fabs(bk[1] - b0[1]));
-          dev[2] = std::max(dev[2], std::fabs(static_cast<float>(
-                                        static_cast<double>(bk[2]) - b0[2] - k)));
-        }
-        ct0[c] = make_float4(b0[0], b0[1], b0[2], 0.f);
-        cth[c] = make_float4(half - dev[0] - allow, half - dev[1] - allow, half - dev[2] - allow,
-                             0.f);
-      }
-      if ((rc = ctx->rt3_cols.Reserve(sizeof(float4) * 2 * cols))) return rc;
-      float4* dct0 = ctx->rt3_cols.as<float4>();
-      CSM_HIP(hipMemcpyAsync(dct0, ct0.data(), sizeof(float4) * cols, hipMemcpyHostToDevice, st));
-      CSM_HIP(hipMemcpyAsync(dct0 + cols, cth.data(), sizeof(float4) * cols, hipMemcpyHostToDevice,
-                             st));
-      if (ctx->timing) CSM_HIP(hipEventRecord(ctx->ev0, st));
-      CSM_HIP(LaunchRt3dScore5(nl, static_cast<int>(brot.size() / 64), st, grid->prob_col.as<float>(),
-                               gb, P, res, eps, make_float4(lo[0], lo[1], lo[2], 0.f),
-                               make_float4(hi[0], hi[1], hi[2], 0.f), ctx->rt3_points.as<float>(),
-                               n, drot4, didx, dangle, ctx->rt3_trans.as<float4>(), dct0,
-                               dct0 + cols, static_cast<int>(num_rot),
-                               o->translation_delta_cost_weight, o->rotation_delta_cost_weight,
-                               ctx->rt3_best.as<unsigned long long>(), dscores,
-                               static_cast<int>(num_trans)));
-    } else {
-    if (ctx->timing) CSM_HIP(hipEventRecord(ctx->ev0, st));
-    CSM_HIP(LaunchRt3dScore4(static_cast<int>(brot.size() / 64), st, grid->prob_wide.as<float>(), gb,
-                             P, res, eps, make_float4(lo[0], lo[1], lo[2], 0.f),
-                             make_float4(hi[0], hi[1], hi[2], 0.f), ctx->rt3_points.as<float>(), n,
-                             drot4, didx, dangle, ctx->rt3_trans.as<float4>(),
-                             static_cast<int>(num_trans), static_cast<int>(num_rot),
-                             o->translation_delta_cost_weight, o->rotation_delta_cost_weight,
-                             ctx->rt3_best.as<unsigned long long>(), dscores,
-                             static_cast<int>(num_trans)));
-    }
-  } else if (ctx->timing) {
-    CSM_HIP(hipEventRecord(ctx->ev0, st));
-  }
-  for (int64_t t0 = 0; t0 < num_trans && !v4; t0 += kRt3dThreads) {
-    const int cnt = static_cast<int>(std::min<int64_t>(kRt3dThreads, num_trans - t0));
-    if (v3)
-      CSM_HIP(LaunchRt3dScore3(static_cast<int>(num_rot), st, grid->prob_pad.as<float>(), gb, res,
-                               eps, ctx->rt3_points.as<float>(), n, drot, dangle,
-                               ctx->rt3_trans.as<float4>(), cnt, static_cast<int>(t0),
-                               o->translation_delta_cost_weight, o->rotation_delta_cost_weight,
-                               ctx->rt3_best.as<unsigned long long>(), dscores,
-                               static_cast<int>(num_trans)));
-    else if (v2)
-      CSM_HIP(LaunchRt3dScore2(static_cast<int>(num_rot), st, grid->prob_pad.as<float>(), gb, res,
-                               ctx->rt3_points.as<float>(), n, drot, dangle,
-                               ctx->rt3_trans.as<float4>(), cnt, static_cast<int>(t0),
-                               o->translation_delta_cost_weight, o->rotation_delta_cost_weight,
-                               ctx->rt3_best.as<unsigned long long>(), dscores,
-                               static_cast<int>(num_trans)));
-    else
-      CSM_HIP(LaunchRt3dScore(static_cast<int>(num_rot), st, grid->prob.as<float>(), gb, res,
-                              ctx->rt3_points.as<float>(), n, drot, dangle,
-                              ctx->rt3_trans.as<float4>(), cnt, static_cast<int>(t0),
-                              o->translation_delta_cost_weight, o->rotation_delta_cost_weight,
-                              ctx->rt3_best.as<unsigned long long>()));
-  }
+  const Rt3dKernel kernel =
+      SelectRt3dKernel(gb.nx, gb.ny, gb.nz, P, static_cast<int>(w.nl), Rt3dKernelCap());
+  if (dscores && kernel == Rt3dKernel::kPlain) return CSM_ERANGE;  // no scoring mode
+  const Rt3dJob job{ctx, o, const_cast<csm_hybrid_grid*>(grid), xyz, n, &w, rot, num_rot, drot,
+                    dangle, dscores};
+  // Each family records ev0 after its own uploads and brick build,
+  // immediately before its first scoring launch.
+  if (kernel >= Rt3dKernel::kRotLanes)
+    rc = ScoreRotationLanes(job, kernel == Rt3dKernel::kColumns, P, lattice);
+  else
+    rc = ScoreTranslationLanes(job, kernel == Rt3dKernel::kPadded);
+  if (rc) return rc;
   if (ctx->timing) CSM_HIP(hipEventRecord(ctx->ev1, st));
   if (key) CSM_HIP(hipMemcpyAsync(key, ctx->rt3_best.ptr, sizeof(*key), hipMemcpyDeviceToHost, st));
   CSM_HIP(hipStreamSynchronize(st));
@@ -1070,8 +1121,9 @@ int64_t csm_fast3d_device_bytes(const csm_fast3d* m) {
 }
 
 int64_t csm_hybrid_grid_device_bytes(const csm_hybrid_grid* g) {
-  return g ? static_cast<int64_t>(g->values.bytes + g->prob.bytes + g->prob_pad.bytes +
-                                  g->prob_wide.bytes + g->prob_col.bytes + g->insert_stats.bytes)
+  return g ? static_cast<int64_t>(g->values.bytes + g->prob.bytes + g->prob_pad.buf.bytes +
+                                  g->prob_wide.buf.bytes + g->prob_col.buf.bytes +
+                                  g->insert_stats.bytes)
            : 0;
 }
 

@@ -1,10 +1,8 @@
 """GPU parity: FastCorrelativeScanMatcher2D on the MI355X vs the oracle.
 
 Bar (north star): score identical (the branch-and-bound maximum is an integer
-sum, so bit-identical float), pose identical — or, when another leaf has
-exactly the same maximal sum (the reference's unstable std::sort makes its
-pick among ties unspecified, fast_correlative_scan_matcher_2d.cc:331-332),
-the GPU's leaf must score exactly that maximum in the oracle.
+sum, so bit-identical float) and pose identical, the reference's pick among
+exactly tied maximal leaves included (csm_host.cc ResolveTies).
 
 Scenarios restate the reference tests (fast_correlative_scan_matcher_2d_test.cc)
 plus BASELINE-shaped synthetic pairs and edge cases.
@@ -18,52 +16,24 @@ from conftest import assert_search_ok
 pytestmark = pytest.mark.gpu
 
 
-def _window_of(oracle, limits, cells, init, lin, ang, cloud, sp_from_rotated=0):
-    import ctypes as C
-    res, mx, my = limits
-    pts = np.ascontiguousarray(cloud, np.float32)
-    init = np.asarray(init, np.float64)
-    ns, step = C.c_int32(), C.c_double()
-    oracle.lib.oracle_discretize(res, mx, my, cells.shape[1], cells.shape[0],
-                                 init.ctypes.data_as(C.POINTER(C.c_double)), lin, ang,
-                                 pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts),
-                                 sp_from_rotated, C.byref(ns), None, None, 0, C.byref(step))
-    return ns.value, step.value
-
-
 def full_submap_center(limits, cells):
     res, mx, my = limits
     half = 0.5 * res
     return (mx - half * cells.shape[0], my - half * cells.shape[1], 0.0)
 
 
-def assert_fast_parity(oracle, om, limits, cells, gpu, ref, full, init, cloud, ties_ok=False):
-    """Same match decision, bit-identical score and the reference's pose. The
-    v4/v5 kernels restore the reference's pick among exactly tied leaves
-    (csm_host.cc ResolveTies), so the pose must be identical; only the v1
-    kernel (CSM_SEARCH_KERNEL=1, never chosen by default) keeps the smallest tied leaf
-    (ties_ok=True), which is then checked to score exactly the maximum."""
+def assert_fast_parity(oracle, om, limits, cells, gpu, ref, full, init, cloud):
+    """Same match decision, bit-identical score and the reference's pose: every
+    search kernel restores the reference's pick among exactly tied leaves
+    (csm_host.cc ResolveTies), so the pose must be identical."""
     g_ok, g_score, g_pose = gpu
     o_ok, o_score, o_pose = ref[:3]
     assert g_ok == o_ok, (gpu, ref[:3])
     if not o_ok:
         return "nomatch"
     assert np.float32(g_score) == np.float32(o_score), (g_score, o_score)
-    if tuple(g_pose) == tuple(o_pose):
-        return "exact"
-    assert ties_ok, ("pose differs from the reference's pick", g_pose, o_pose)
-    # Exact tie: recover the GPU leaf (scan index, offsets) and score it.
-    res = limits[0]
-    lin, ang = (1e6 * res, math.pi) if full else (om.lin, om.ang)
-    ns, step = _window_of(oracle, limits, cells, init, lin, ang, cloud)
-    n_ang = (ns - 1) // 2
-    k = int(round((g_pose[2] - init[2]) / step)) + n_ang
-    x_off = int(round(-(g_pose[1] - init[1]) / res))
-    y_off = int(round(-(g_pose[0] - init[0]) / res))
-    assert 0 <= k < ns, (k, ns, g_pose, o_pose)
-    _, s = om.score_candidate(full, None if full else init, cloud, k, x_off, y_off, 0)
-    assert np.float32(s) == np.float32(o_score), ("GPU leaf is not a tied maximum", g_pose, o_pose)
-    return "tie"
+    assert tuple(g_pose) == tuple(o_pose), ("pose differs from the reference's pick", g_pose, o_pose)
+    return "exact"
 
 
 def test_precomputation_levels_match_oracle(csm, oracle):
@@ -115,12 +85,11 @@ def test_correct_pose_match(csm, oracle, search_kernel):
         init = (0.0, 0.0, 0.0)
         gpu = m.Match(init, cloud, 0.1)
         ref = om.match(init, cloud, 0.1)
-        kinds.append(assert_fast_parity(oracle, om, limits, cells, gpu, ref, False, init, cloud,
-                                        ties_ok=search_kernel == "v1"))
+        kinds.append(assert_fast_parity(oracle, om, limits, cells, gpu, ref, False, init, cloud))
         assert gpu[0] and gpu[1] > 0.1
         # The reference test's own acceptance: pose within IsNearly 0.03.
         assert abs(gpu[2][0] - expected[0]) < 0.1 and abs(gpu[2][1] - expected[1]) < 0.1
-    assert kinds.count("exact") + kinds.count("tie") == 50
+    assert kinds.count("exact") == 50
 
 
 def test_full_submap_matching(csm, oracle, search_kernel):
@@ -144,8 +113,7 @@ def test_full_submap_matching(csm, oracle, search_kernel):
         gpu = m.MatchFullSubmap(cloud, 0.1)
         ref = om.match_full_submap(cloud, 0.1)
         init = full_submap_center(limits, cells)
-        assert_fast_parity(oracle, om, limits, cells, gpu, ref, True, init, cloud,
-                           ties_ok=search_kernel == "v1")
+        assert_fast_parity(oracle, om, limits, cells, gpu, ref, True, init, cloud)
         assert gpu[0]
 
 
@@ -158,6 +126,8 @@ SEARCH_KERNELS = {"v5": {}, "v5-all-hex": {"CSM_SEARCH_KERNEL": "5"},
                   "v5-mixed-lifo": {"CSM_HEX_LEVELS": "8,6,3", "CSM_SEARCH_ORDER": "lifo"},
                   "v4": {"CSM_SEARCH_KERNEL": "4"},
                   "v4-lifo": {"CSM_SEARCH_KERNEL": "4", "CSM_SEARCH_ORDER": "lifo"},
+                  # The retired v1 kernel's setting: an unrecognised value now, which
+                  # must run the default kernel, tie resolution included.
                   "v1": {"CSM_SEARCH_KERNEL": "1"}}
 
 
@@ -166,8 +136,8 @@ def search_kernel(request, monkeypatch):
     """Every search kernel and node order: v5 (the default: hex planes for the
     top level and the one two below, quad planes elsewhere, FIFO node order),
     v5 with every even level hex, hex levels mixed into quad ones under the
-    depth-first LIFO order, v4 (quad planes only) in both orders, and v1
-    (lanes = points, row-major pyramid; only when forced). The plane
+    depth-first LIFO order, and v4 (quad planes only) in both orders; "v1"
+    keeps the retired kernel's setting, which now selects nothing. The plane
     layout is fixed when a matcher is created, so the variables are set
     before."""
     for var in ("CSM_SEARCH_KERNEL", "CSM_HEX_LEVELS", "CSM_SEARCH_ORDER"):
@@ -199,7 +169,7 @@ def test_synthetic_full_submap_pairs(csm, oracle, world, depth_mode, search_kern
         gpu = (res[k]["status"] == 0, float(res[k]["score"]),
                (res[k]["x"], res[k]["y"], res[k]["theta"]))
         assert_fast_parity(oracle, om, limits, g.cells, gpu, ref, True,
-                           full_submap_center(limits, g.cells), cloud, ties_ok=search_kernel == "v1")
+                           full_submap_center(limits, g.cells), cloud)
         matched += int(gpu[0])
     assert matched >= 3
 
@@ -238,8 +208,7 @@ def test_match_window_mode_parity(csm, oracle, world, search_kernel):
         cloud = world.cloud(n)
         gpu = m.Match(init, cloud, 0.55)
         ref = om.match(init, cloud, 0.55)
-        assert_fast_parity(oracle, om, limits, g.cells, gpu, ref, False, init, cloud,
-                           ties_ok=search_kernel == "v1")
+        assert_fast_parity(oracle, om, limits, g.cells, gpu, ref, False, init, cloud)
 
 
 def test_edge_cases(csm, oracle, search_kernel):
@@ -255,8 +224,7 @@ def test_edge_cases(csm, oracle, search_kernel):
     om = oracle.fast2d(limits, cells, 0.5, 0.3, 4)
     gpu = m.MatchFullSubmap(cloud, 0.0)
     ref = om.match_full_submap(cloud, 0.0)
-    assert_fast_parity(oracle, om, limits, cells, gpu, ref, True, full_submap_center(limits, cells), cloud,
-                       ties_ok=search_kernel == "v1")
+    assert_fast_parity(oracle, om, limits, cells, gpu, ref, True, full_submap_center(limits, cells), cloud)
     # min_score above every attainable score: no match.
     assert m.MatchFullSubmap(cloud, 0.95)[0] is False
     # 1x1 grid.
@@ -266,7 +234,7 @@ def test_edge_cases(csm, oracle, search_kernel):
     gpu = m1.Match((0.0, 0.0, 0.0), cloud, 0.0)
     ref = om1.match((0.0, 0.0, 0.0), cloud, 0.0)
     assert_fast_parity(oracle, om1, (0.05, 0.05, 0.05), np.full((1, 1), 20000, np.uint16), gpu, ref,
-                       False, (0.0, 0.0, 0.0), cloud, ties_ok=search_kernel == "v1")
+                       False, (0.0, 0.0, 0.0), cloud)
 
 
 def _run_list_clouds(world):
@@ -310,8 +278,7 @@ def test_run_lists_parity(csm, oracle, world, search_kernel):
                (float(res[k]["x"]), float(res[k]["y"]), float(res[k]["theta"])))
         ref = om.match_full_submap(c, 0.3)
         kinds.append(assert_fast_parity(oracle, om, limits, g.cells, gpu, ref, True,
-                                        full_submap_center(limits, g.cells), c,
-                                        ties_ok=search_kernel == "v1"))
+                                        full_submap_center(limits, g.cells), c))
     assert kinds.count("nomatch") < len(kinds)
 
 
@@ -328,13 +295,12 @@ def _large_cloud(world, n_points, seed):
     return np.ascontiguousarray(c, np.float32)
 
 
-@pytest.mark.parametrize("kernel", ["v5", "v4", "v1"])
+@pytest.mark.parametrize("kernel", ["v5", "v4"])
 def test_large_clouds_match_oracle(csm, oracle, world, kernel, monkeypatch):
     """Clouds past 8192 points, up to the boundary's limit kMaxPoints = 16448
     (csm_device.h): Match() with a local window, in one batch with a small
     cloud. v5 (the default for every size) runs one rotation per workgroup
-    here, its 16448-point scan and lists in ~128 KB of LDS; v4 and the forced
-    v1 kernel too."""
+    here, its 16448-point scan and lists in ~128 KB of LDS; v4 too."""
     for var in ("CSM_SEARCH_KERNEL", "CSM_HEX_LEVELS", "CSM_SEARCH_ORDER"):
         monkeypatch.delenv(var, raising=False)
     if kernel != "v5":
@@ -359,8 +325,7 @@ def test_large_clouds_match_oracle(csm, oracle, world, kernel, monkeypatch):
         gpu = (int(res[k]["status"]) == csm.CSM_OK, float(res[k]["score"]),
                (float(res[k]["x"]), float(res[k]["y"]), float(res[k]["theta"])))
         ref = om.match(init, c, 0.3)
-        assert_fast_parity(oracle, om, limits, g.cells, gpu, ref, False, init, c,
-                           ties_ok=kernel == "v1")
+        assert_fast_parity(oracle, om, limits, g.cells, gpu, ref, False, init, c)
         matched += int(gpu[0])
     assert matched == 3
     # One point past the limit is refused, not searched.

@@ -198,13 +198,12 @@ RT_CLOUD = np.array([[-3, 2, 0], [-4, 2, 0], [-5, 2, 0], [-6, 2, 0], [-6, 3, 1],
                      [-7, 3, 1]], np.float32)
 
 
-# Every RTCSM3D kernel the host can select (host3d.cc RunRt3d): v5 (column
-# gathers, the default for 3-, 5- and 7-step z columns), v4 (rotation lanes,
-# other windows), v3 / v2 (bricks too large for v4's / v3's float byte
-# offsets) and v1 (bricks past v2's 2^29 cells). The variables force the
-# fallbacks on small inputs; the last two tests reach v4 and v2 unforced.
-RT3D_KERNELS = {"v5": None, "v4": "CSM_RT3D_V4", "v3": "CSM_RT3D_V3", "v2": "CSM_RT3D_V2",
-                "v1": "CSM_RT3D_V1"}
+# Every RTCSM3D kernel the host can select (rt3d_select.h): v5 (column
+# gathers, the default for 3- to 15-step z columns), v4 (rotation lanes,
+# other windows), v2 (bricks too large for v4's float byte offsets) and v1
+# (bricks past v2's 2^29 cells). The variables force the fallbacks on small
+# inputs; the last two tests reach v4 and v2 unforced.
+RT3D_KERNELS = {"v5": None, "v4": "CSM_RT3D_V4", "v2": "CSM_RT3D_V2", "v1": "CSM_RT3D_V1"}
 
 
 @pytest.fixture(params=list(RT3D_KERNELS))
@@ -284,10 +283,11 @@ def test_rt3d_column_kernel_tilted_initial(csm, oracle, window, rt3d_kernel):
         assert pose == ref_pose
 
 
-@pytest.mark.parametrize("steps", [9, 11, 13])
+@pytest.mark.parametrize("steps", [9, 11, 13, 15])
 def test_rt3d_wide_z_windows(csm, oracle, rt3d_kernel, steps):
-    """+-0.4 / 0.5 / 0.6 m at 0.1 m: 9-, 11- and 13-step z columns, which v5
-    takes with three or four 16-byte loads per column (rt3d_score5<9..13>),
+    """+-0.4 / 0.5 / 0.6 / 0.7 m at 0.1 m: 9- to 15-step z columns, which v5
+    takes with three or four 16-byte loads per column (rt3d_score5<9..15>,
+    15 the largest instantiation the host selects),
     under a tilted and a yawed initial pose (real_time_correlative_scan_
     matcher_3d.cc:55-113 generates the same lattice)."""
     rng = np.random.default_rng(19)
@@ -308,11 +308,14 @@ def test_rt3d_wide_z_windows(csm, oracle, rt3d_kernel, steps):
         assert pose == ref_pose
 
 
-@pytest.mark.parametrize("kernel", ["v2", "v1"])
+@pytest.mark.parametrize("kernel", ["v2", "v1", "v2-band"])
 def test_rt3d_large_brick(csm, oracle, kernel, monkeypatch):
     """A HybridGrid whose known cells span 30 x 30 x 6 m at 0.1 m (5.5e6
-    voxels, a 22 MB float brick): past v4's and v3's 2^24-byte float offsets,
-    so the host selects v2 unforced (and v1 when forced)."""
+    voxels, a 22 MB float brick): past v4's 2^24-byte float offsets, so the
+    host selects v2 unforced (and v1 when forced). "v2-band": 159 cells per
+    axis (a 16 MB brick), under 2^22 cells padded by one cell and at or over
+    it padded by two, the least v4 pads by: the bricks the retired v3 kernel
+    took, which v2 now covers unforced."""
     for var in RT3D_KERNELS.values():
         if var:
             monkeypatch.delenv(var, raising=False)
@@ -322,9 +325,13 @@ def test_rt3d_large_brick(csm, oracle, kernel, monkeypatch):
     cloud = rng.uniform(-4, 4, (250, 3)).astype(np.float32) * np.float32([1, 1, 0.4])
     og = oracle.hybrid_grid(0.1)
     og.insert((0, 0, 0), cloud, 0.7, 0.4, 5)
-    og.set_probability(-150, -150, -30, 0.6)
-    og.set_probability(150, 150, 30, 0.6)
+    corner = (79, 79, 79) if kernel == "v2-band" else (150, 150, 30)
+    og.set_probability(-corner[0], -corner[1], -corner[2], 0.6)
+    og.set_probability(*corner, 0.6)
     g = gpu_grid(csm, og)
+    if kernel == "v2-band":
+        nx, ny, nz = g.info()[1]
+        assert (nx + 2) * (ny + 2) * (nz + 2) < 2 ** 22 <= (nx + 4) * (ny + 4) * (nz + 4), (nx, ny, nz)
     opts = (0.2, math.radians(1.0), 0.1, 0.1)
     m = csm.RealTimeCorrelativeScanMatcher3D(csm.RealTimeCorrelativeScanMatcherOptions(*opts))
     for initial in [((0.04, -0.02, 0.03), quat_z(0.02)), ((0.0, 0.0, 0.0), (1, 0, 0, 0))]:

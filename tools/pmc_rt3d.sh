@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes (one counter group per rocprofv3 run, no tracing) over one C4
 # RTCSM3D match (tools/probe_rt3d.py). Usage (GPU box): tools/pmc_rt3d.sh OUTDIR SETTING
-#   SETTING: probe_rt3d.py's env setting, e.g. CSM_RT3D_V3=- (v4) or CSM_RT3D_V3=1 (v3)
+#   SETTING: probe_rt3d.py's env setting, e.g. CSM_RT3D_V4=- (v5) or CSM_RT3D_V4=1 (v4)
 set -u
 OUT=$1
 SET=$2

@@ -1,5 +1,7 @@
-"""C4 RTCSM3D timing per scoring-loop unroll (CSM_RT3D_UNROLL) and kernel
-version (CSM_RT3D_V1): prints kernel ms and the best score for each setting."""
+"""C4 RTCSM3D timing per kernel: each argument is an environment setting,
+"-" unsets (e.g. CSM_RT3D_V4=- for the default rt3d_score5, CSM_RT3D_V4=1 for
+rt3d_score4, CSM_RT3D_V2=1 for rt3d_score2, CSM_RT3D_V1=1 for rt3d_score);
+prints kernel ms and the best score for each setting."""
 import importlib.util
 import os
 import sys
