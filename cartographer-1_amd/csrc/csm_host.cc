@@ -31,7 +31,7 @@
 #include "csm_internal.h"
 #include "csm_launch.h"
 #include "csm_schedule.h"
-#include "parallel_sort.h"
+#include "tie_order.h"
 #include "search_window.h"
 
 namespace csm {
@@ -379,24 +379,167 @@ void RotationBounds(const csm_scan_set* scans, const PairDesc& d, const SubmapDe
   b[3] = std::min(d.num_linear, std::max(0, sm.ny - 1 - mny));
 }
 
+using Clock = std::chrono::steady_clock;
+
+// The reference's exact bounds of lattice nodes `qs` (level, x, y), grouped
+// into (pair, rotation) jobs that index the last search's pair descriptors
+// (ctx->pair_desc_dev), summed on the device (fast2d_score_queries).
+int ScoreQueries2(csm_context* ctx, csm_scan_set* scans, const SearchPlan& plan,
+                  const std::vector<ScoreJob>& js, const std::vector<int4>& qs,
+                  std::vector<int32_t>* sums) {
+  return ScoreQueriesRoundTrip(ctx->stream, ctx->sq_jobs, ctx->sq_queries, ctx->sq_sums, js, qs, sums, [&] {
+    return LaunchFast2dScoreQueries(static_cast<int>(js.size()), plan.max_npad, ctx->stream,
+                                    ctx->submap_desc.as<SubmapDesc>(),
+                                    static_cast<const PairDesc*>(ctx->pair_desc_dev), scans->points.as<float>(),
+                                    scans->rot_dev.as<float2>(), ctx->sq_jobs.as<ScoreJob>(),
+                                    ctx->sq_queries.as<int4>(), ctx->sq_sums.as<int32_t>());
+  });
+}
+
+// The top lists of tied pairs `ts` (indices into `pd`, the collect search's
+// descriptors): ShrinkToFit bounds of every rotation on the device, every
+// lattice node scored in one launch, up to 8 lists sorted at once on 8 threads
+// between them. `t_built`, `t_scored`: when that was done (CSM_PROFILE2D).
+int TopLists2(csm_context* ctx, csm_fast2d* const* submaps, csm_scan_set* scans, const SearchPlan& plan,
+              const std::vector<PairDesc>& pd, const std::vector<int>& ts, std::vector<TopList>* out,
+              Clock::time_point* t_built, Clock::time_point* t_scored) {
+  out->clear();
+  if (ts.empty()) return CSM_OK;
+  std::vector<int2> bjobs;
+  for (int t : ts)
+    for (int r = 0; r < pd[t].num_scans; ++r) bjobs.push_back(make_int2(t, r));
+  int rc;
+  if ((rc = ctx->sq_jobs.Reserve(sizeof(int2) * bjobs.size()))) return rc;
+  if ((rc = ctx->sq_sums.Reserve(sizeof(int4) * bjobs.size()))) return rc;
+  hipStream_t st = ctx->stream;
+  std::vector<int4> bounds(bjobs.size());
+  CSM_HIP(hipMemcpyAsync(ctx->sq_jobs.ptr, bjobs.data(), sizeof(int2) * bjobs.size(),
+                         hipMemcpyHostToDevice, st));
+  CSM_HIP(LaunchFast2dRotationBounds(static_cast<int>(bjobs.size()), st, ctx->submap_desc.as<SubmapDesc>(),
+                                     static_cast<const PairDesc*>(ctx->pair_desc_dev), scans->points.as<float>(),
+                                     scans->rot_dev.as<float2>(), ctx->sq_jobs.as<int2>(),
+                                     ctx->sq_sums.as<int4>()));
+  CSM_HIP(hipMemcpyAsync(bounds.data(), ctx->sq_sums.ptr, sizeof(int4) * bjobs.size(),
+                         hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  std::vector<ScoreJob> tj;
+  std::vector<int4> tq;
+  std::vector<int64_t> base(ts.size());
+  size_t bi = 0;
+  for (size_t pi = 0; pi < ts.size(); ++pi) {
+    const PairDesc& d = pd[ts[pi]];
+    const int T = submaps[d.submap]->options.branch_and_bound_depth - 1;
+    out->push_back(TopList{TopLattice(T, false), {}, {}});
+    TopLattice& lat = out->back().lat;
+    base[pi] = static_cast<int64_t>(tq.size());
+    for (int r = 0; r < d.num_scans; ++r, ++bi) {
+      const int4 b = bounds[bi];
+      lat.AddRotation({{b.x, b.z, 0}, {b.y, b.w, 0}});
+      ScoreJob job{ts[pi], r, static_cast<int32_t>(tq.size()), 0};
+      lat.ForEachOfRotation(r, [&](int x, int y, int) { tq.push_back(make_int4(T, x, y, 0)); });
+      job.count = static_cast<int32_t>(tq.size()) - job.first;
+      if (job.count) tj.push_back(job);
+    }
+  }
+  *t_built = Clock::now();
+  std::vector<int32_t> sc;
+  if ((rc = ScoreQueries2(ctx, scans, plan, tj, tq, &sc))) return rc;
+  *t_scored = Clock::now();
+  // ScoreCandidates: score = ToScore(sum / n), then the reference's sort.
+  const size_t nthreads = std::min<size_t>(ts.size(), 8);
+  const int sort_threads = static_cast<int>(8 / std::max<size_t>(nthreads, 1));
+  auto sort_one = [&](size_t pi) {
+    TopList& c = (*out)[pi];
+    const PairDesc& d = pd[ts[pi]];
+    const csm_fast2d* m = submaps[d.submap];
+    c.sums.assign(sc.begin() + base[pi], sc.begin() + base[pi] + c.lat.size());
+    c.ord = TopListOrder(
+        c.lat.size(), [&](int64_t i) { return SumToScore(c.sums[i], d.num_points, m->min_s, m->max_s); },
+        sort_threads);
+  };
+  std::atomic<size_t> next{0};
+  auto drain = [&] {
+    for (size_t pi; (pi = next.fetch_add(1)) < ts.size();) sort_one(pi);
+  };
+  std::vector<std::thread> pool;
+  for (size_t i = 1; i < nthreads; ++i) pool.emplace_back(drain);
+  drain();
+  for (auto& th : pool) th.join();
+  return CSM_OK;
+}
+
+// Pairs `walk` (indices into `pd` and `tied`) whose tied leaves overflow the
+// collect record: the device walks the reference's visiting order
+// (fast2d_walk) from the sorted top list, of which only the entries whose sum
+// reaches the maximum can lead to it.
+int WalkTies2(csm_context* ctx, csm_fast2d* const* submaps, csm_scan_set* scans, const SearchPlan& plan,
+              const std::vector<PairDesc>& pd, const std::vector<int>& tied, const std::vector<int>& walk,
+              std::vector<uint64_t>* keys, std::vector<int32_t>* stat, Clock::time_point* t_built,
+              Clock::time_point* t_scored) {
+  std::vector<TopList> tl;
+  int rc;
+  if ((rc = TopLists2(ctx, submaps, scans, plan, pd, walk, &tl, t_built, t_scored))) return rc;
+  std::vector<WalkJob2> wj;
+  std::vector<int4> wtop, wb;
+  for (size_t wi = 0; wi < walk.size(); ++wi) {
+    const int t = walk[wi];
+    const PairDesc& d = pd[t];
+    const csm_fast2d* m = submaps[d.submap];
+    const TopList& c = tl[wi];
+    WalkJob2 j{t, d.collect_sum, m->options.branch_and_bound_depth - 1, static_cast<int32_t>(wtop.size()), 0,
+               static_cast<int32_t>(wb.size()), m->min_s, m->max_s};
+    for (const auto& b : c.lat.boxes) wb.push_back(make_int4(b.lo[0], b.hi[0], b.lo[1], b.hi[1]));
+    for (const int32_t li : c.ord.order) {
+      if (c.sums[li] < d.collect_sum) continue;
+      const TieNode n = c.lat.Node(li);
+      wtop.push_back(make_int4(n.rot, n.x, n.y, c.sums[li]));
+    }
+    j.top_count = static_cast<int32_t>(wtop.size()) - j.top_first;
+    wj.push_back(j);
+  }
+  // One buffer: jobs | top entries | bounds | results.
+  const size_t o_top = (sizeof(WalkJob2) * wj.size() + 15) & ~size_t{15};
+  const size_t o_b = o_top + sizeof(int4) * std::max<size_t>(wtop.size(), 1);
+  const size_t o_out = o_b + sizeof(int4) * wb.size();
+  const size_t bytes = o_out + sizeof(int4) * wj.size();
+  if ((rc = ctx->walk_buf.Reserve(bytes))) return rc;
+  char* dw = ctx->walk_buf.as<char>();
+  std::vector<char> hw(o_out);
+  std::memcpy(hw.data(), wj.data(), sizeof(WalkJob2) * wj.size());
+  if (!wtop.empty()) std::memcpy(hw.data() + o_top, wtop.data(), sizeof(int4) * wtop.size());
+  std::memcpy(hw.data() + o_b, wb.data(), sizeof(int4) * wb.size());
+  hipStream_t st = ctx->stream;
+  CSM_HIP(hipMemcpyAsync(dw, hw.data(), o_out, hipMemcpyHostToDevice, st));
+  CSM_HIP(LaunchFast2dWalk(static_cast<int>(wj.size()), plan.max_npad, st,
+                           ctx->submap_desc.as<SubmapDesc>(),
+                           static_cast<const PairDesc*>(ctx->pair_desc_dev), scans->points.as<float>(),
+                           scans->rot_dev.as<float2>(), reinterpret_cast<const WalkJob2*>(dw),
+                           reinterpret_cast<const int4*>(dw + o_top),
+                           reinterpret_cast<const int4*>(dw + o_b), reinterpret_cast<int4*>(dw + o_out)));
+  std::vector<int4> found(wj.size());
+  CSM_HIP(hipMemcpyAsync(found.data(), dw + o_out, sizeof(int4) * wj.size(), hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  for (size_t wi = 0; wi < walk.size(); ++wi) {
+    const int k = tied[walk[wi]];
+    if (!found[wi].w) {
+      // Unreachable: the maximum is some leaf's sum, and the walk visits
+      // every node whose sum reaches it. Never return a leaf that is not
+      // the reference's: the pair's result is void.
+      (*keys)[k] = 0;
+      (*stat)[k] |= kStatusRange;
+      continue;
+    }
+    (*keys)[k] = PackLeafKey(static_cast<uint32_t>(pd[walk[wi]].collect_sum), found[wi].x,
+                             found[wi].y, found[wi].z);
+  }
+  return CSM_OK;
+}
+
 // Exactly tied maxima. The device keeps the smallest (rotation, x, y) leaf;
-// the reference keeps the FIRST maximal leaf its depth-first search visits
-// (std::max keeps the incumbent on equal scores and later subtrees whose
-// bound does not exceed it are cut, fast_correlative_scan_matcher_2d.cc:
-// 344-376). It visits a node's children (<= 4, std::sort = insertion sort:
-// stable) by descending score, equal scores in generation order (x, then y;
-// :353-366), and the lowest-resolution candidates in the order std::sort
-// (introsort, not stable) leaves their generation order (scan, x, y;
-// :276-312) in. So among tied leaves the reference's pick is the one whose
-// chain of ancestors, top level first, comes first in those orders. For a
-// pair whose two witness keys show a tie: (1) a second search with the
-// maximum as its starting best records every leaf at it; (2) the ancestors'
-// exact bounds at the reference's depth are scored on the device
-// (fast2d_score_queries); (3) when two tied leaves descend from different
-// lowest-resolution candidates of equal score, the pair's whole
-// lowest-resolution list is scored and sorted with the same std::sort and
-// comparison, which reproduces the reference's permutation. No oracle and no
-// CPU scoring is involved.
+// the reference keeps the first maximal leaf its depth-first search visits,
+// and tie_order.h says which of the tied leaves that is. Every pair whose two
+// witness keys show a tie goes through the steps below; all scores come from
+// the device, no oracle and no CPU scoring is involved.
 int ResolveTies(csm_context* ctx, csm_fast2d* const* submaps, csm_scan_set* scans,
                 const std::vector<PairDesc>& pdesc, const std::vector<float2>& rot_host,
                 const SearchPlan& plan, std::vector<int32_t>* stat,
@@ -414,11 +557,10 @@ int ResolveTies(csm_context* ctx, csm_fast2d* const* submaps, csm_scan_set* scan
   if (tied.empty()) return CSM_OK;
   ctx->t.tied_pairs += static_cast<int64_t>(tied.size());
   const bool prof = std::getenv("CSM_PROFILE2D") != nullptr;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+  auto ms = [](Clock::time_point a, Clock::time_point b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
   };
-  const auto tp0 = now();
+  const auto tp0 = Clock::now();
   // (1) Every leaf at the maximum.
   std::vector<PairDesc> pd2;
   std::vector<uint64_t> init;
@@ -437,21 +579,18 @@ int ResolveTies(csm_context* ctx, csm_fast2d* const* submaps, csm_scan_set* scan
   if ((rc = LaunchSearch(ctx, scans, pd2, &init, plan, false, &k2, &kh2, &st2, stats2, &ties,
                          &counts)))
     return rc;
-  auto zrot = [&](const PairDesc& d, int r) {
-    const float2 z = rot_host[d.rot_offset + r];
-    return ZRot{z.x, z.y};
-  };
-  // (2) Ancestors at the reference's depth D: level d node of a leaf is
-  // (b0 + ((x - b0) >> d << d), b2 + ((y - b2) >> d << d)).
+  // (2) The leaves' ancestors at the reference's depth, grouped by rotation:
+  // one score job per (pair, rotation), a leaf's T queries next to each other.
   struct Tie {
-    int k, t, depth, leaves_first, leaves_count;
+    int k, t, first_query;
+    TieChains chains;
+    Live live;
+    int top;  // its top list, where one is needed
   };
   std::vector<Tie> work;
-  std::vector<int3> leaves;          // (rot, x, y)
   std::vector<ScoreJob> jobs;
   std::vector<int4> queries;
-  std::vector<int> leaf_query;       // per leaf: first of its D - 1 ancestor queries
-  std::vector<int> walk;             // tied pairs (pd2 index) whose leaves overflow the record
+  std::vector<int> walk;  // tied pairs (pd2 index) whose leaves overflow the record
   for (size_t t = 0; t < tied.size(); ++t) {
     const int k = tied[t];
     const int cnt = counts[t];
@@ -465,339 +604,70 @@ int ResolveTies(csm_context* ctx, csm_fast2d* const* submaps, csm_scan_set* scan
     }
     const PairDesc& d = pdesc[k];
     const csm_fast2d* m = submaps[d.submap];
-    Tie w{k, static_cast<int>(t), m->options.branch_and_bound_depth,
-          static_cast<int>(leaves.size()), cnt};
-    std::map<int, std::vector<int>> by_rot;
+    Tie w{k, static_cast<int>(t), static_cast<int>(queries.size()), {}, {}, -1};
+    const int T = w.chains.T = m->options.branch_and_bound_depth - 1;
+    std::map<int, std::vector<uint32_t>> by_rot;  // the leaves' packed (x, y)
     for (int i = 0; i < cnt; ++i) {
       const uint2 e = ties[static_cast<size_t>(t) * kTieCap + i];
-      const int r = static_cast<int>(e.x);
-      const int x = static_cast<int16_t>(e.y & 0xffff), y = static_cast<int>(e.y) >> 16;
-      leaves.push_back(make_int3(r, x, y));
-      by_rot[r].push_back(w.leaves_first + i);
+      by_rot[static_cast<int>(e.x)].push_back(e.y);
     }
-    leaf_query.resize(leaves.size(), -1);
-    const int T = w.depth - 1;
-    for (auto& [r, idx] : by_rot) {
-      int b[4];
-      RotationBounds(scans, d, m->desc, zrot(d, r), b);
-      if (T < 1) continue;
-      ScoreJob job{static_cast<int32_t>(t), r, static_cast<int32_t>(queries.size()), 0};
-      for (int li : idx) {
-        leaf_query[li] = static_cast<int>(queries.size());
+    for (const auto& [r, xy] : by_rot) {
+      int b[4] = {0, 0, 0, 0};
+      const float2 z = rot_host[d.rot_offset + r];
+      if (T > 0) RotationBounds(scans, d, m->desc, ZRot{z.x, z.y}, b);
+      ScoreJob job{static_cast<int32_t>(t), r, static_cast<int32_t>(queries.size()), T * static_cast<int32_t>(xy.size())};
+      for (const uint32_t e : xy) {
+        w.chains.AddLeaf(r, static_cast<int16_t>(e & 0xffff), static_cast<int>(e) >> 16, 0, b[0], b[2], 0);
         for (int lv = 1; lv <= T; ++lv) {
-          const int ax = b[0] + (((leaves[li].y - b[0]) >> lv) << lv);
-          const int ay = b[2] + (((leaves[li].z - b[2]) >> lv) << lv);
-          queries.push_back(make_int4(lv, ax, ay, 0));
+          const TieNode& a = w.chains.at(w.chains.count() - 1, lv);
+          queries.push_back(make_int4(lv, a.x, a.y, 0));
         }
       }
-      job.count = static_cast<int32_t>(queries.size()) - job.first;
-      jobs.push_back(job);
+      if (job.count) jobs.push_back(job);
     }
-    work.push_back(w);
+    work.push_back(std::move(w));
   }
-  auto score = [&](const std::vector<ScoreJob>& js, const std::vector<int4>& qs,
-                   std::vector<int32_t>* sums) -> int {
-    sums->assign(qs.size(), 0);
-    if (js.empty()) return CSM_OK;
-    int r2;
-    if ((r2 = ctx->sq_jobs.Reserve(sizeof(ScoreJob) * js.size()))) return r2;
-    if ((r2 = ctx->sq_queries.Reserve(sizeof(int4) * qs.size()))) return r2;
-    if ((r2 = ctx->sq_sums.Reserve(sizeof(int32_t) * qs.size()))) return r2;
-    hipStream_t st = ctx->stream;
-    CSM_HIP(hipMemcpyAsync(ctx->sq_jobs.ptr, js.data(), sizeof(ScoreJob) * js.size(),
-                           hipMemcpyHostToDevice, st));
-    CSM_HIP(hipMemcpyAsync(ctx->sq_queries.ptr, qs.data(), sizeof(int4) * qs.size(),
-                           hipMemcpyHostToDevice, st));
-    CSM_HIP(LaunchFast2dScoreQueries(static_cast<int>(js.size()), plan.max_npad, st,
-                                     ctx->submap_desc.as<SubmapDesc>(), static_cast<const PairDesc*>(ctx->pair_desc_dev),
-                                     scans->points.as<float>(), scans->rot_dev.as<float2>(),
-                                     ctx->sq_jobs.as<ScoreJob>(), ctx->sq_queries.as<int4>(),
-                                     ctx->sq_sums.as<int32_t>()));
-    CSM_HIP(hipMemcpyAsync(sums->data(), ctx->sq_sums.ptr, sizeof(int32_t) * qs.size(),
-                           hipMemcpyDeviceToHost, st));
-    CSM_HIP(hipStreamSynchronize(st));
-    return CSM_OK;
-  };
-  const auto tp1 = now();
+  const auto tp1 = Clock::now();
   // The jobs index pd2 (ctx->pair_desc_dev holds it after the second search).
   std::vector<int32_t> sums;
-  if ((rc = score(jobs, queries, &sums))) return rc;
-  // Per tie: the leaves that can come first. The reference visits the
-  // lowest-resolution candidates by descending score, so only leaves under a
-  // top-level ancestor of the highest score compete; the top-level order is
-  // needed only when two distinct such ancestors share that score.
-  struct Cand {
-    std::vector<int> live;  // leaf indices under a highest-score top ancestor
-    bool need_perm = false;
-    std::vector<std::array<int, 4>> rb;  // per rotation bounds (need_perm)
-    std::vector<int64_t> rot_first;      // per rotation first lattice index
-    std::vector<int64_t> pos;            // lattice index -> sorted position
-  };
-  std::vector<Cand> cand(work.size());
-  auto anc_of = [&](const Tie& w, int li, int lv) {
+  if ((rc = ScoreQueries2(ctx, scans, plan, jobs, queries, &sums))) return rc;
+  // (3) Per tie: the leaves that can come first, and whether picking among
+  // them takes the top list's order.
+  std::vector<int> perm;  // pd2 indices
+  for (Tie& w : work) {
     const PairDesc& d = pdesc[w.k];
     const csm_fast2d* m = submaps[d.submap];
-    const int4 q = queries[leaf_query[li] + lv - 1];
-    return std::make_tuple(q.y, q.z,
-                           SumToScore(sums[leaf_query[li] + lv - 1], d.num_points, m->min_s, m->max_s));
-  };
-  for (size_t wi = 0; wi < work.size(); ++wi) {
-    const Tie& w = work[wi];
-    Cand& c = cand[wi];
-    const int T = w.depth - 1;
-    if (T == 0) {  // the top-level list is the leaves themselves
-      for (int i = 0; i < w.leaves_count; ++i) c.live.push_back(w.leaves_first + i);
-      c.need_perm = true;
-      continue;
+    for (int i = 0, q = w.first_query; i < w.chains.count(); ++i)
+      for (int lv = 1; lv <= w.chains.T; ++lv, ++q)
+        w.chains.at(i, lv).score = SumToScore(sums[q], d.num_points, m->min_s, m->max_s);
+    w.live = LiveLeaves(w.chains);
+    (*tie_code)[w.k] = w.live.need_perm ? CSM_TIE_TOPLIST : CSM_TIE_ANCESTORS;
+    if (w.live.need_perm) {
+      w.top = static_cast<int>(perm.size());
+      perm.push_back(w.t);
     }
-    float top = -std::numeric_limits<float>::infinity();
-    for (int i = 0; i < w.leaves_count; ++i) top = std::max(top, std::get<2>(anc_of(w, w.leaves_first + i, T)));
-    std::set<std::tuple<int, int, int>> nodes;
-    for (int i = 0; i < w.leaves_count; ++i) {
-      const int li = w.leaves_first + i;
-      const auto [x, y, sc] = anc_of(w, li, T);
-      if (sc != top) continue;
-      c.live.push_back(li);
-      nodes.insert({leaves[li].x, x, y});
-    }
-    c.need_perm = nodes.size() > 1;
-  }
-  const auto tp2 = now();
-  auto tp3 = tp2, tp4 = tp2;
-  // (3) The whole lowest-resolution list of every pair that needs the
-  // top-level permutation: bounds of all its rotations on the device, every
-  // lattice node scored in one launch, each list sorted on its own thread.
-  std::vector<int> perm;
-  for (size_t wi = 0; wi < work.size(); ++wi) {
-    (*tie_code)[work[wi].k] = cand[wi].need_perm ? CSM_TIE_TOPLIST : CSM_TIE_ANCESTORS;
-    if (cand[wi].need_perm) perm.push_back(static_cast<int>(wi));
   }
   ctx->t.ties_toplist += static_cast<int64_t>(perm.size());
-  // The whole lowest-resolution list of tied pairs `ts` (pd2 indices) in the
-  // reference's order: ShrinkToFit bounds of every rotation on the device,
-  // every lattice node of the reference's top level scored in one launch
-  // (GenerateLowestResolutionCandidates, :276-312), each list sorted on its
-  // own threads.
-  struct TopList {
-    std::vector<std::array<int, 4>> rb;  // per rotation bounds
-    std::vector<int64_t> rot_first;      // per rotation first lattice index
-    std::vector<int32_t> sums;           // lattice index -> sum
-    std::vector<int32_t> order;          // sorted position -> lattice index
-  };
-  auto top_lists = [&](const std::vector<int>& ts, std::vector<TopList>* out) -> int {
-    out->assign(ts.size(), TopList{});
-    if (ts.empty()) return CSM_OK;
-    std::vector<int2> bjobs;
-    for (int t : ts)
-      for (int r = 0; r < pd2[t].num_scans; ++r) bjobs.push_back(make_int2(t, r));
-    int r2;
-    if ((r2 = ctx->sq_jobs.Reserve(sizeof(int2) * bjobs.size()))) return r2;
-    if ((r2 = ctx->sq_sums.Reserve(sizeof(int4) * bjobs.size()))) return r2;
-    hipStream_t st = ctx->stream;
-    std::vector<int4> bounds(bjobs.size());
-    CSM_HIP(hipMemcpyAsync(ctx->sq_jobs.ptr, bjobs.data(), sizeof(int2) * bjobs.size(),
-                           hipMemcpyHostToDevice, st));
-    CSM_HIP(LaunchFast2dRotationBounds(static_cast<int>(bjobs.size()), st, ctx->submap_desc.as<SubmapDesc>(),
-                                       static_cast<const PairDesc*>(ctx->pair_desc_dev), scans->points.as<float>(),
-                                       scans->rot_dev.as<float2>(), ctx->sq_jobs.as<int2>(),
-                                       ctx->sq_sums.as<int4>()));
-    CSM_HIP(hipMemcpyAsync(bounds.data(), ctx->sq_sums.ptr, sizeof(int4) * bjobs.size(),
-                           hipMemcpyDeviceToHost, st));
-    CSM_HIP(hipStreamSynchronize(st));
-    std::vector<ScoreJob> tj;
-    std::vector<int4> tq;
-    std::vector<int64_t> base(ts.size());
-    size_t bi = 0;
-    for (size_t pi = 0; pi < ts.size(); ++pi) {
-      const PairDesc& d = pd2[ts[pi]];
-      TopList& c = (*out)[pi];
-      const int n = d.num_scans;
-      const int T = submaps[d.submap]->options.branch_and_bound_depth - 1, step = 1 << T;
-      base[pi] = static_cast<int64_t>(tq.size());
-      c.rb.resize(n);
-      c.rot_first.assign(n + 1, 0);
-      for (int r = 0; r < n; ++r, ++bi) {
-        const int4 b = bounds[bi];
-        c.rb[r] = {b.x, b.y, b.z, b.w};
-        ScoreJob job{ts[pi], r, static_cast<int32_t>(tq.size()), 0};
-        for (int x = b.x; x <= b.y; x += step)
-          for (int y = b.z; y <= b.w; y += step) tq.push_back(make_int4(T, x, y, 0));
-        job.count = static_cast<int32_t>(tq.size()) - job.first;
-        c.rot_first[r + 1] = static_cast<int64_t>(tq.size()) - base[pi];
-        if (job.count) tj.push_back(job);
-      }
-    }
-    tp3 = now();
-    std::vector<int32_t> sc;
-    if ((r2 = score(tj, tq, &sc))) return r2;
-    tp4 = now();
-    // ScoreCandidates: score = ToScore(sum / n), then
-    // std::sort(greater<Candidate2D>) — the same algorithm and the same
-    // comparisons give the same permutation for any element type; IntroSort
-    // (parallel_sort.h) is that algorithm with independent partitions on
-    // threads. Up to 8 lists at once, 8 threads between them.
-    const size_t nthreads = std::min<size_t>(ts.size(), 8);
-    const int sort_threads = static_cast<int>(8 / std::max<size_t>(nthreads, 1));
-    auto sort_one = [&](size_t pi) {
-      TopList& c = (*out)[pi];
-      const PairDesc& d = pd2[ts[pi]];
-      const csm_fast2d* m = submaps[d.submap];
-      const int64_t n = c.rot_first.back();
-      c.sums.assign(sc.begin() + base[pi], sc.begin() + base[pi] + n);
-      // 8-byte elements (the comparisons, and so the permutation, are the
-      // same whatever the element carries).
-      std::vector<std::pair<float, int32_t>> lst(n);
-      ParallelRanges(n, sort_threads, [&](std::ptrdiff_t lo, std::ptrdiff_t hi) {
-        for (std::ptrdiff_t i = lo; i < hi; ++i)
-          lst[i] = {SumToScore(c.sums[i], d.num_points, m->min_s, m->max_s), static_cast<int32_t>(i)};
-      });
-      IntroSort(lst.data(), lst.data() + n,
-                [](const std::pair<float, int32_t>& a, const std::pair<float, int32_t>& b) {
-                  return a.first > b.first;
-                },
-                sort_threads);
-      c.order.resize(n);
-      ParallelRanges(n, sort_threads, [&](std::ptrdiff_t lo, std::ptrdiff_t hi) {
-        for (std::ptrdiff_t i = lo; i < hi; ++i) c.order[i] = lst[i].second;
-      });
-    };
-    if (nthreads <= 1) {
-      for (size_t pi = 0; pi < ts.size(); ++pi) sort_one(pi);
-    } else {
-      std::vector<std::thread> pool;
-      std::atomic<size_t> next{0};
-      for (size_t i = 0; i < nthreads; ++i)
-        pool.emplace_back([&] {
-          for (size_t pi; (pi = next.fetch_add(1)) < ts.size();) sort_one(pi);
-        });
-      for (auto& th : pool) th.join();
-    }
-    return CSM_OK;
-  };
-  if (!perm.empty()) {
-    std::vector<int> ts;
-    for (int wi : perm) ts.push_back(work[wi].t);
-    std::vector<TopList> tl;
-    if ((rc = top_lists(ts, &tl))) return rc;
-    for (size_t pi = 0; pi < perm.size(); ++pi) {
-      Cand& c = cand[perm[pi]];
-      c.rb = std::move(tl[pi].rb);
-      c.rot_first = std::move(tl[pi].rot_first);
-      const std::vector<int32_t>& order = tl[pi].order;
-      c.pos.resize(order.size());
-      ParallelRanges(static_cast<std::ptrdiff_t>(order.size()), 8,
-                     [&](std::ptrdiff_t lo, std::ptrdiff_t hi) {
-                       for (std::ptrdiff_t i = lo; i < hi; ++i) c.pos[order[i]] = i;
-                     });
-    }
-  }
-  // (4) Pairs whose tied leaves overflow the record: the device walks the
-  // reference's visiting order (fast2d_walk) from the sorted top list, of
-  // which only the entries whose sum reaches the maximum can lead to it.
-  if (!walk.empty()) {
-    std::vector<TopList> tl;
-    if ((rc = top_lists(walk, &tl))) return rc;
-    std::vector<WalkJob2> wj;
-    std::vector<int4> wtop, wb;
-    for (size_t wi = 0; wi < walk.size(); ++wi) {
-      const int t = walk[wi];
-      const PairDesc& d = pd2[t];
-      const csm_fast2d* m = submaps[d.submap];
-      const TopList& c = tl[wi];
-      const int T = m->options.branch_and_bound_depth - 1, step = 1 << T;
-      WalkJob2 j{t, d.collect_sum, T, static_cast<int32_t>(wtop.size()), 0,
-                 static_cast<int32_t>(wb.size()), m->min_s, m->max_s};
-      for (const auto& b : c.rb) wb.push_back(make_int4(b[0], b[1], b[2], b[3]));
-      for (const int32_t li : c.order) {
-        if (c.sums[li] < d.collect_sum) continue;
-        const int r = static_cast<int>(std::upper_bound(c.rot_first.begin(), c.rot_first.end(), li) -
-                                       c.rot_first.begin()) - 1;
-        const int ny = (c.rb[r][3] - c.rb[r][2] + step) / step;
-        const int64_t loc = li - c.rot_first[r];
-        wtop.push_back(make_int4(r, c.rb[r][0] + static_cast<int>(loc / ny) * step,
-                                 c.rb[r][2] + static_cast<int>(loc % ny) * step, c.sums[li]));
-      }
-      j.top_count = static_cast<int32_t>(wtop.size()) - j.top_first;
-      wj.push_back(j);
-    }
-    // One buffer: jobs | top entries | bounds | results.
-    const size_t o_top = (sizeof(WalkJob2) * wj.size() + 15) & ~size_t{15};
-    const size_t o_b = o_top + sizeof(int4) * std::max<size_t>(wtop.size(), 1);
-    const size_t o_out = o_b + sizeof(int4) * wb.size();
-    const size_t bytes = o_out + sizeof(int4) * wj.size();
-    if ((rc = ctx->walk_buf.Reserve(bytes))) return rc;
-    char* dw = ctx->walk_buf.as<char>();
-    std::vector<char> hw(o_out);
-    std::memcpy(hw.data(), wj.data(), sizeof(WalkJob2) * wj.size());
-    if (!wtop.empty()) std::memcpy(hw.data() + o_top, wtop.data(), sizeof(int4) * wtop.size());
-    std::memcpy(hw.data() + o_b, wb.data(), sizeof(int4) * wb.size());
-    hipStream_t st = ctx->stream;
-    CSM_HIP(hipMemcpyAsync(dw, hw.data(), o_out, hipMemcpyHostToDevice, st));
-    CSM_HIP(LaunchFast2dWalk(static_cast<int>(wj.size()), plan.max_npad, st,
-                             ctx->submap_desc.as<SubmapDesc>(),
-                             static_cast<const PairDesc*>(ctx->pair_desc_dev), scans->points.as<float>(),
-                             scans->rot_dev.as<float2>(), reinterpret_cast<const WalkJob2*>(dw),
-                             reinterpret_cast<const int4*>(dw + o_top),
-                             reinterpret_cast<const int4*>(dw + o_b), reinterpret_cast<int4*>(dw + o_out)));
-    std::vector<int4> found(wj.size());
-    CSM_HIP(hipMemcpyAsync(found.data(), dw + o_out, sizeof(int4) * wj.size(), hipMemcpyDeviceToHost, st));
-    CSM_HIP(hipStreamSynchronize(st));
-    for (size_t wi = 0; wi < walk.size(); ++wi) {
-      const int k = tied[walk[wi]];
-      if (!found[wi].w) {
-        // Unreachable: the maximum is some leaf's sum, and the walk visits
-        // every node whose sum reaches it. Never return a leaf that is not
-        // the reference's: the pair's result is void.
-        (*keys)[k] = 0;
-        (*stat)[k] |= kStatusRange;
-        continue;
-      }
-      (*keys)[k] = PackLeafKey(static_cast<uint32_t>(pd2[walk[wi]].collect_sum), found[wi].x,
-                               found[wi].y, found[wi].z);
-    }
-  }
-  const auto tp5 = now();
-  for (size_t wi = 0; wi < work.size(); ++wi) {
-    const Tie& w = work[wi];
-    const Cand& c = cand[wi];
-    const PairDesc& d2 = pd2[w.t];
-    const int T = w.depth - 1;
-    const int step = 1 << T;
-    auto anc = [&](int li, int lv) { return anc_of(w, li, lv); };
-    // Sorted position of the top-level node (rot, x, y).
-    auto top_pos = [&](int r, int x, int y) {
-      const int ny = (c.rb[r][3] - c.rb[r][2] + step) / step;
-      return c.pos[c.rot_first[r] + static_cast<int64_t>((x - c.rb[r][0]) / step) * ny +
-                   (y - c.rb[r][2]) / step];
-    };
-    // The reference's visiting order of two tied leaves.
-    auto first = [&](int a, int b) {
-      for (int lv = T; lv >= 1; --lv) {
-        const auto [ax, ay, as] = anc(a, lv);
-        const auto [bx, by, bs] = anc(b, lv);
-        const int ra = leaves[a].x, rb2 = leaves[b].x;
-        if (ra == rb2 && ax == bx && ay == by) continue;
-        if (as != bs) return as > bs;
-        if (lv == T) return top_pos(ra, ax, ay) < top_pos(rb2, bx, by);
-        return std::make_pair(ax, ay) < std::make_pair(bx, by);
-      }
-      if (T == 0)
-        return top_pos(leaves[a].x, leaves[a].y, leaves[a].z) <
-               top_pos(leaves[b].x, leaves[b].y, leaves[b].z);
-      return std::make_pair(leaves[a].y, leaves[a].z) < std::make_pair(leaves[b].y, leaves[b].z);
-    };
-    int best = c.live[0];
-    for (size_t i = 1; i < c.live.size(); ++i)
-      if (first(c.live[i], best)) best = c.live[i];
-    (*keys)[w.k] = PackLeafKey(static_cast<uint32_t>(d2.collect_sum), leaves[best].x,
-                               leaves[best].y, leaves[best].z);
+  const auto tp2 = Clock::now();
+  auto tp3 = tp2, tp4 = tp2;
+  std::vector<TopList> tl;
+  if ((rc = TopLists2(ctx, submaps, scans, plan, pd2, perm, &tl, &tp3, &tp4))) return rc;
+  // (4) Pairs whose tied leaves overflow the record.
+  if (!walk.empty() &&
+      (rc = WalkTies2(ctx, submaps, scans, plan, pd2, tied, walk, keys, stat, &tp3, &tp4)))
+    return rc;
+  const auto tp5 = Clock::now();
+  for (const Tie& w : work) {
+    auto top_pos = [&](const TieNode& n) { return tl[w.top].Pos(n); };
+    const TieNode& best = w.chains.at(FirstVisitedLeaf(w.chains, w.live.leaves, top_pos, SiblingsXY), 0);
+    (*keys)[w.k] = PackLeafKey(static_cast<uint32_t>(pd2[w.t].collect_sum), best.rot, best.x, best.y);
   }
   if (prof)
     std::fprintf(stderr,
                  "ties (ms): collect search %.2f, ancestors %.2f, bounds + lattice %.2f, "
                  "lattice scores %.2f, sorts %.2f, picks %.2f; %zu tied, %zu need the order\n",
                  ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3), ms(tp3, tp4), ms(tp4, tp5),
-                 ms(tp5, now()), tied.size(), perm.size());
+                 ms(tp5, Clock::now()), tied.size(), perm.size());
   return CSM_OK;
 }
 

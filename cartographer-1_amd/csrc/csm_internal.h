@@ -72,6 +72,26 @@ struct DevBuf {
   T* as() const { return static_cast<T*>(ptr); }
 };
 
+// One round trip of the tie resolvers' score kernels (fast2d_score_queries,
+// fast3d_score_queries): uploads the jobs and the queries they index into the
+// given scratch buffers, runs launch() and reads back one sum per query.
+template <typename Job, typename Query, typename Launch>
+int ScoreQueriesRoundTrip(hipStream_t st, DevBuf& jobs, DevBuf& queries, DevBuf& out, const std::vector<Job>& js,
+                          const std::vector<Query>& qs, std::vector<int32_t>* sums, Launch launch) {
+  sums->assign(qs.size(), 0);
+  if (js.empty()) return CSM_OK;
+  int rc;
+  if ((rc = jobs.Reserve(sizeof(Job) * js.size()))) return rc;
+  if ((rc = queries.Reserve(sizeof(Query) * qs.size()))) return rc;
+  if ((rc = out.Reserve(sizeof(int32_t) * qs.size()))) return rc;
+  CSM_HIP(hipMemcpyAsync(jobs.ptr, js.data(), sizeof(Job) * js.size(), hipMemcpyHostToDevice, st));
+  CSM_HIP(hipMemcpyAsync(queries.ptr, qs.data(), sizeof(Query) * qs.size(), hipMemcpyHostToDevice, st));
+  CSM_HIP(launch());
+  CSM_HIP(hipMemcpyAsync(sums->data(), out.ptr, sizeof(int32_t) * qs.size(), hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  return CSM_OK;
+}
+
 // Device buffers of destroyed matchers and grids (2D pyramids and cost
 // grids, 3D bricks, levels and octets), kept for reuse by the next create: a
 // sweep builds and drops thousands of submaps, and hipMalloc / hipFree of

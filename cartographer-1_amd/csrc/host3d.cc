@@ -34,7 +34,7 @@
 #include "csm_device3d.h"
 #include "csm_internal.h"
 #include "csm_launch3d.h"
-#include "parallel_sort.h"
+#include "tie_order.h"
 #include "rt3d_select.h"
 
 using namespace csm;
@@ -1457,23 +1457,133 @@ size_t SpillBytes3(const csm_context* ctx) {
          static_cast<size_t>(ctx->num_cus) * kSearch3dBlocksPerCuMax;
 }
 
+// What the tie steps share of a batch on the device.
+struct Ties3Dev {
+  csm_context* ctx;
+  const Submap3Desc* sub;
+  const Pair3Desc* pairs;
+  const Yaw3Desc* yaws;
+};
+
+// Exact scores of nodes `qs` (depth, x, y, z) at the reference's depths,
+// grouped into per-yaw jobs, summed on the device (fast3d_score_queries).
+int ScoreQueries3(const Ties3Dev& dev, const std::vector<Score3Job>& js, const std::vector<int4>& qs,
+                  std::vector<int32_t>* sums) {
+  csm_context* ctx = dev.ctx;
+  return ScoreQueriesRoundTrip(ctx->stream, ctx->f3_sq_jobs, ctx->f3_sq_queries, ctx->f3_sq_sums, js, qs, sums, [&] {
+    return LaunchFast3dScoreQueries(static_cast<int>(js.size()), ctx->stream, dev.sub, dev.pairs, dev.yaws,
+                                    ctx->f3_points.as<float>(), ctx->f3_sq_jobs.as<Score3Job>(),
+                                    ctx->f3_sq_queries.as<int4>(), ctx->f3_sq_sums.as<int32_t>());
+  });
+}
+
+// The top lists of device pairs `dps`: every lattice node of every yaw scored
+// in one launch, each list sorted with the reference's sort on 8 threads.
+int TopLists3(const Ties3Dev& dev, csm_fast3d* const* submaps, const std::vector<Pair3Desc>& pdesc,
+              const std::vector<int>& dps, std::vector<TopList>* out) {
+  out->clear();
+  if (dps.empty()) return CSM_OK;
+  std::vector<Score3Job> tj;
+  std::vector<int4> tq;
+  for (const int dp : dps) {
+    const Pair3Desc& d = pdesc[dp];
+    const int D = submaps[d.submap]->desc.num_levels - 1;
+    out->push_back(TopList{TopLattice(D, true), {}, {}});
+    TopLattice& lat = out->back().lat;
+    for (int j = 0; j < d.num_yaws; ++j) {
+      Score3Job job{d.yaw_begin + j, static_cast<int32_t>(tq.size()), 0, 0};
+      lat.AddRotation({{-d.wxy, -d.wxy, -d.wz}, {d.wxy, d.wxy, d.wz}});
+      lat.ForEachOfRotation(j, [&](int x, int y, int z) { tq.push_back(make_int4(D, x, y, z)); });
+      job.count = static_cast<int32_t>(tq.size()) - job.first;
+      tj.push_back(job);
+    }
+  }
+  std::vector<int32_t> ts;
+  int rc;
+  if ((rc = ScoreQueries3(dev, tj, tq, &ts))) return rc;
+  int64_t base = 0;
+  for (size_t k = 0; k < dps.size(); ++k) {
+    TopList& c = (*out)[k];
+    const int n = pdesc[dps[k]].num_points;
+    c.sums.assign(ts.begin() + base, ts.begin() + base + c.lat.size());
+    c.ord = TopListOrder(c.lat.size(), [&](int64_t i) { return SumToProbability(c.sums[i], n); }, 8);
+    base += c.lat.size();
+  }
+  return CSM_OK;
+}
+
+unsigned long long LeafKey3(const Pair3Desc& d, unsigned long long key, int yaw, int x, int y, int z) {
+  const unsigned long long mask = (1ull << d.key_shift) - 1;
+  return ((key >> d.key_shift) << d.key_shift) | (~LeafId3(d, yaw, x, y, z) & mask);
+}
+
+// Device pairs `walk` whose passing tied leaves overflow the collect record:
+// the device walks the reference's visiting order from the sorted top list
+// (fast3d_walk); only entries whose sum reaches the maximum can lead to the
+// pick.
+int WalkTies3(const Ties3Dev& dev, csm_fast3d* const* submaps, const std::vector<Pair3Desc>& pdesc,
+              const std::vector<int>& walk, std::vector<unsigned long long>* keys,
+              std::vector<int32_t>* stat) {
+  csm_context* ctx = dev.ctx;
+  hipStream_t st = ctx->stream;
+  std::vector<TopList> tl;
+  int rc;
+  if ((rc = TopLists3(dev, submaps, pdesc, walk, &tl))) return rc;
+  std::vector<Walk3Job> wj;
+  std::vector<int4> wtop;
+  for (size_t k = 0; k < walk.size(); ++k) {
+    const Pair3Desc& d = pdesc[walk[k]];
+    const TopList& c = tl[k];
+    const int32_t target = static_cast<int32_t>((*keys)[walk[k]] >> d.key_shift);
+    Walk3Job j{walk[k], target, submaps[d.submap]->desc.num_levels - 1, static_cast<int32_t>(wtop.size()), 0,
+               {0, 0, 0}};
+    for (const int32_t i : c.ord.order) {
+      if (c.sums[i] < target) continue;
+      const TieNode n = c.lat.Node(i);
+      wtop.push_back(make_int4(n.rot, (n.x & 0xffff) | (n.y << 16), n.z, c.sums[i]));
+    }
+    j.top_count = static_cast<int32_t>(wtop.size()) - j.top_first;
+    wj.push_back(j);
+  }
+  const size_t o_top = sizeof(Walk3Job) * wj.size();
+  const size_t o_out = o_top + sizeof(int4) * std::max<size_t>(wtop.size(), 1);
+  const size_t bytes = o_out + 2 * sizeof(int4) * wj.size();
+  if ((rc = ctx->f3_walk_buf.Reserve(bytes))) return rc;
+  char* dw = ctx->f3_walk_buf.as<char>();
+  std::vector<char> hw(o_out);
+  std::memcpy(hw.data(), wj.data(), o_top);
+  if (!wtop.empty()) std::memcpy(hw.data() + o_top, wtop.data(), sizeof(int4) * wtop.size());
+  CSM_HIP(hipMemcpyAsync(dw, hw.data(), o_out, hipMemcpyHostToDevice, st));
+  CSM_HIP(LaunchFast3dWalk(static_cast<int>(wj.size()), st, dev.sub, dev.pairs, dev.yaws,
+                           ctx->f3_points.as<float>(), ctx->f3_low_points.as<float>(),
+                           reinterpret_cast<const Walk3Job*>(dw),
+                           reinterpret_cast<const int4*>(dw + o_top),
+                           reinterpret_cast<int4*>(dw + o_out)));
+  std::vector<int4> found(2 * wj.size());
+  CSM_HIP(hipMemcpyAsync(found.data(), dw + o_out, 2 * sizeof(int4) * wj.size(),
+                         hipMemcpyDeviceToHost, st));
+  CSM_HIP(hipStreamSynchronize(st));
+  for (size_t k = 0; k < walk.size(); ++k) {
+    const int dp = walk[k];
+    if (!found[2 * k + 1].x) {
+      // Unreachable (the maximum is a passing leaf's sum and the walk visits
+      // every node whose sum reaches it): never return a leaf that is not
+      // the reference's, the pair's result is void.
+      (*stat)[dp] = CSM_ERANGE;
+      continue;
+    }
+    const int4 f = found[2 * k];
+    (*keys)[dp] = LeafKey3(pdesc[dp], (*keys)[dp], f.x, f.y, f.z, f.w);
+  }
+  return CSM_OK;
+}
+
 // Exactly tied maxima in 3D. The search keeps, among the
 // leaves that pass the low-resolution check at the best sum, the smallest
 // (yaw, x, y, z) key and, next to it, the largest (best_hi). The reference
-// returns the first such leaf its depth-first search reaches
-// (fast_correlative_scan_matcher_3d.cc:377-440): the lowest-resolution
-// candidates in the order std::sort(greater<Candidate3D>) leaves their
-// generation order (scan_index, z, y, x; :297-330, :353-354) in, each node's
-// children (<= 8, generated z, y, x with x fastest, :412-430) by descending
-// score with ties in generation order (insertion sort: stable), and at depth 0
-// the first child that passes the low-resolution check (:384-401), the
-// incumbent kept on equal scores (:433-437). For a tied pair: (1) a collect
-// search with the maximum as its starting best records every passing leaf at
-// it; (2) their ancestors' exact scores at every reference depth are computed
-// on the device (fast3d_score_queries); (3) when two distinct
-// lowest-resolution ancestors share the highest score, the pair's whole
-// lowest-resolution list is scored and ordered with the same introsort
-// (parallel_sort.h). No oracle and no CPU scoring is involved. `code` gets
+// returns the first such leaf its depth-first search reaches, and tie_order.h
+// says which that is. Every tied pair goes through the steps below; all scores
+// come from the device, no oracle and no CPU scoring is involved. `code` gets
 // CSM_TIE_* per device pair.
 int ResolveTies3d(csm_context* ctx, csm_fast3d* const* submaps, const std::vector<Pair3Desc>& pdesc,
                   std::vector<int32_t>* stat_io, const std::vector<unsigned long long>& keys_hi,
@@ -1496,16 +1606,19 @@ int ResolveTies3d(csm_context* ctx, csm_fast3d* const* submaps, const std::vecto
   Pair3Desc* dpairs = ctx->f3_pairs.as<Pair3Desc>();
   const Submap3Desc* dsub = reinterpret_cast<const Submap3Desc*>(dpairs + np);
   const Yaw3Desc* dyaws = ctx->f3_yaws.as<Yaw3Desc>();
+  const Ties3Dev dev{ctx, dsub, dpairs, dyaws};
   const int nt = static_cast<int>(tied.size());
   int rc;
   // (1) Collect search over the tied pairs' yaws (by search build tier).
   std::vector<Pair3Desc> mod(nt);
   std::vector<unsigned long long> init(nt);
+  std::vector<int> by_tier;  // the tied pairs in the order of their search build tiers
   int items = 0, tier_end[kSearch3dTiers] = {};
   for (int pass = 0; pass < kSearch3dTiers; ++pass) {
     for (int t = 0; t < nt; ++t) {
       const Pair3Desc& d = pdesc[tied[t]];
       if (Search3dTier(d.num_points) != pass) continue;
+      by_tier.push_back(t);
       items += d.num_yaws;
     }
     tier_end[pass] = items;
@@ -1515,15 +1628,12 @@ int ResolveTies3d(csm_context* ctx, csm_fast3d* const* submaps, const std::vecto
   if ((rc = ctx->f3_ties.Reserve(sizeof(uint4) * kTieCap3d * static_cast<size_t>(nt)))) return rc;
   Yaw3Desc* tyaws = ctx->f3_tie_yaws.as<Yaw3Desc>();
   int at = 0;
-  for (int pass = 0; pass < kSearch3dTiers; ++pass)
-    for (int t = 0; t < nt; ++t) {
-      const int dp = tied[t];
-      const Pair3Desc& d = pdesc[dp];
-      if (Search3dTier(d.num_points) != pass) continue;
-      CSM_HIP(hipMemcpyAsync(tyaws + at, dyaws + d.yaw_begin, sizeof(Yaw3Desc) * d.num_yaws,
-                             hipMemcpyDeviceToDevice, st));
-      at += d.num_yaws;
-    }
+  for (const int t : by_tier) {
+    const Pair3Desc& d = pdesc[tied[t]];
+    CSM_HIP(hipMemcpyAsync(tyaws + at, dyaws + d.yaw_begin, sizeof(Yaw3Desc) * d.num_yaws,
+                           hipMemcpyDeviceToDevice, st));
+    at += d.num_yaws;
+  }
   for (int t = 0; t < nt; ++t) {
     const int dp = tied[t];
     mod[t] = pdesc[dp];
@@ -1560,16 +1670,18 @@ int ResolveTies3d(csm_context* ctx, csm_fast3d* const* submaps, const std::vecto
                            hipMemcpyHostToDevice, st));
   CSM_HIP(hipStreamSynchronize(st));
 
-  // (2) Ancestor scores at every reference depth 1..D (D = max_depth).
+  // (2) The leaves' ancestors at every reference depth 1..D (D = max_depth),
+  // grouped by yaw: one score job per yaw, a leaf's D queries next to each other.
   struct Work {
-    int dp, t, D, first, count;
+    int dp, first_query;
+    TieChains chains;
+    Live live;
+    int top;  // its top list, where one is needed
   };
   std::vector<Work> work;
-  std::vector<int4> lv;  // per leaf: (yaw, x, y, z)
   std::vector<Score3Job> jobs;
   std::vector<int4> queries;
-  std::vector<int> leaf_query;  // per leaf: index of its depth-1 ancestor query
-  std::vector<int> walk;        // tied pairs (device index) whose leaves overflow the record
+  std::vector<int> walk;  // tied pairs (device index) whose leaves overflow the record
   for (int t = 0; t < nt; ++t) {
     const int dp = tied[t];
     const Pair3Desc& d = pdesc[dp];
@@ -1582,250 +1694,62 @@ int ResolveTies3d(csm_context* ctx, csm_fast3d* const* submaps, const std::vecto
       walk.push_back(dp);
       continue;
     }
-    const int D = submaps[d.submap]->desc.num_levels - 1;
-    Work w{dp, t, D, static_cast<int>(lv.size()), cnt};
-    std::vector<std::vector<int>> by_yaw(d.num_yaws);
+    Work w{dp, static_cast<int>(queries.size()), {}, {}, -1};
+    const int D = w.chains.T = submaps[d.submap]->desc.num_levels - 1;
+    std::vector<std::vector<uint4>> by_yaw(d.num_yaws);
     for (int i = 0; i < cnt; ++i) {
       const uint4 e = leaves_all[static_cast<size_t>(t) * kTieCap3d + i];
-      lv.push_back(make_int4(static_cast<int>(e.x), static_cast<int>(e.y), static_cast<int>(e.z),
-                             static_cast<int>(e.w)));
-      if (static_cast<int>(e.x) < d.num_yaws) by_yaw[e.x].push_back(w.first + i);
+      if (static_cast<int>(e.x) < d.num_yaws) by_yaw[e.x].push_back(e);
     }
-    leaf_query.resize(lv.size(), -1);
     for (int j = 0; j < d.num_yaws; ++j) {
-      if (by_yaw[j].empty() || D < 1) continue;
-      Score3Job job{d.yaw_begin + j, static_cast<int32_t>(queries.size()), 0, 0};
-      for (int li : by_yaw[j]) {
-        leaf_query[li] = static_cast<int>(queries.size());
-        for (int l = 1; l <= D; ++l)
-          queries.push_back(make_int4(l, -d.wxy + (((lv[li].y + d.wxy) >> l) << l),
-                                      -d.wxy + (((lv[li].z + d.wxy) >> l) << l),
-                                      -d.wz + (((lv[li].w + d.wz) >> l) << l)));
+      Score3Job job{d.yaw_begin + j, static_cast<int32_t>(queries.size()),
+                    D * static_cast<int32_t>(by_yaw[j].size()), 0};
+      for (const uint4& e : by_yaw[j]) {
+        w.chains.AddLeaf(j, static_cast<int>(e.y), static_cast<int>(e.z), static_cast<int>(e.w), -d.wxy,
+                         -d.wxy, -d.wz);
+        for (int l = 1; l <= D; ++l) {
+          const TieNode& a = w.chains.at(w.chains.count() - 1, l);
+          queries.push_back(make_int4(l, a.x, a.y, a.z));
+        }
       }
-      job.count = static_cast<int32_t>(queries.size()) - job.first;
-      jobs.push_back(job);
+      if (job.count) jobs.push_back(job);
     }
-    work.push_back(w);
+    work.push_back(std::move(w));
   }
-  auto score = [&](const std::vector<Score3Job>& js, const std::vector<int4>& qs,
-                   std::vector<int32_t>* sums) -> int {
-    sums->assign(qs.size(), 0);
-    if (js.empty()) return CSM_OK;
-    int r2;
-    if ((r2 = ctx->f3_sq_jobs.Reserve(sizeof(Score3Job) * js.size()))) return r2;
-    if ((r2 = ctx->f3_sq_queries.Reserve(sizeof(int4) * qs.size()))) return r2;
-    if ((r2 = ctx->f3_sq_sums.Reserve(sizeof(int32_t) * qs.size()))) return r2;
-    CSM_HIP(hipMemcpyAsync(ctx->f3_sq_jobs.ptr, js.data(), sizeof(Score3Job) * js.size(),
-                           hipMemcpyHostToDevice, st));
-    CSM_HIP(hipMemcpyAsync(ctx->f3_sq_queries.ptr, qs.data(), sizeof(int4) * qs.size(),
-                           hipMemcpyHostToDevice, st));
-    CSM_HIP(LaunchFast3dScoreQueries(static_cast<int>(js.size()), st, dsub, dpairs, dyaws,
-                                     ctx->f3_points.as<float>(), ctx->f3_sq_jobs.as<Score3Job>(),
-                                     ctx->f3_sq_queries.as<int4>(), ctx->f3_sq_sums.as<int32_t>()));
-    CSM_HIP(hipMemcpyAsync(sums->data(), ctx->f3_sq_sums.ptr, sizeof(int32_t) * qs.size(),
-                           hipMemcpyDeviceToHost, st));
-    CSM_HIP(hipStreamSynchronize(st));
-    return CSM_OK;
-  };
   std::vector<int32_t> sums;
-  if ((rc = score(jobs, queries, &sums))) return rc;
-  // Ancestor of leaf li at depth l: (yaw, x, y, z, score).
-  struct Anc {
-    int yaw, x, y, z;
-    float score;
-  };
-  auto anc = [&](const Work& w, int li, int l) {
-    const Pair3Desc& d = pdesc[w.dp];
-    if (l == 0) return Anc{lv[li].x, lv[li].y, lv[li].z, lv[li].w, 0.f};
-    const int4 q = queries[leaf_query[li] + l - 1];
-    return Anc{lv[li].x, q.y, q.z, q.w, SumToProbability(sums[leaf_query[li] + l - 1], d.num_points)};
-  };
+  if ((rc = ScoreQueries3(dev, jobs, queries, &sums))) return rc;
   // (3) Leaves under a highest-scoring lowest-resolution ancestor; the whole
   // top list of pairs where two distinct such ancestors tie.
-  struct Cand {
-    std::vector<int> live;
-    bool need_perm = false;
-    int nx = 0, ny = 0, nz = 0;
-    std::vector<int64_t> pos;  // generation index -> sorted position
-  };
-  std::vector<Cand> cand(work.size());
-  std::vector<int> perm;
-  for (size_t wi = 0; wi < work.size(); ++wi) {
-    const Work& w = work[wi];
-    Cand& c = cand[wi];
-    float top = -std::numeric_limits<float>::infinity();
-    for (int i = 0; i < w.count; ++i) top = std::max(top, anc(w, w.first + i, w.D).score);
-    std::vector<std::array<int, 4>> nodes;
-    for (int i = 0; i < w.count; ++i) {
-      const Anc a = anc(w, w.first + i, w.D);
-      if (w.D > 0 && a.score != top) continue;
-      c.live.push_back(w.first + i);
-      const std::array<int, 4> key{a.yaw, a.x, a.y, a.z};
-      if (std::find(nodes.begin(), nodes.end(), key) == nodes.end()) nodes.push_back(key);
+  std::vector<int> perm;  // device pairs
+  for (Work& w : work) {
+    for (int i = 0, q = w.first_query; i < w.chains.count(); ++i)
+      for (int l = 1; l <= w.chains.T; ++l, ++q)
+        w.chains.at(i, l).score = SumToProbability(sums[q], pdesc[w.dp].num_points);
+    w.live = LiveLeaves(w.chains);
+    (*code)[w.dp] = w.live.need_perm ? CSM_TIE_TOPLIST : CSM_TIE_ANCESTORS;
+    if (w.live.need_perm) {
+      w.top = static_cast<int>(perm.size());
+      perm.push_back(w.dp);
     }
-    c.need_perm = nodes.size() > 1;
-    (*code)[w.dp] = c.need_perm ? CSM_TIE_TOPLIST : CSM_TIE_ANCESTORS;
-    if (c.need_perm) perm.push_back(static_cast<int>(wi));
   }
   ctx->t.ties_toplist += static_cast<int64_t>(perm.size());
-  if (!perm.empty()) {
-    std::vector<Score3Job> tj;
-    std::vector<int4> tq;
-    std::vector<int64_t> base(perm.size());
-    for (size_t k = 0; k < perm.size(); ++k) {
-      const Work& w = work[perm[k]];
-      Cand& c = cand[perm[k]];
-      const Pair3Desc& d = pdesc[w.dp];
-      const int step = 1 << w.D;
-      c.nx = c.ny = (2 * d.wxy + step) / step;  // GenerateLowestResolutionCandidates (:301-310)
-      c.nz = (2 * d.wz + step) / step;
-      base[k] = static_cast<int64_t>(tq.size());
-      for (int j = 0; j < d.num_yaws; ++j) {
-        Score3Job job{d.yaw_begin + j, static_cast<int32_t>(tq.size()), 0, 0};
-        for (int z = -d.wz; z <= d.wz; z += step)
-          for (int y = -d.wxy; y <= d.wxy; y += step)
-            for (int x = -d.wxy; x <= d.wxy; x += step) tq.push_back(make_int4(w.D, x, y, z));
-        job.count = static_cast<int32_t>(tq.size()) - job.first;
-        tj.push_back(job);
-      }
-    }
-    std::vector<int32_t> ts;
-    if ((rc = score(tj, tq, &ts))) return rc;
-    for (size_t k = 0; k < perm.size(); ++k) {
-      const Work& w = work[perm[k]];
-      Cand& c = cand[perm[k]];
-      const int64_t n = static_cast<int64_t>(pdesc[w.dp].num_yaws) * c.nx * c.ny * c.nz;
-      // ScoreCandidates' std::sort(greater<Candidate3D>) on the generation
-      // order: the same comparisons give the same permutation for any element.
-      std::vector<std::pair<float, int32_t>> lst(n);
-      for (int64_t i = 0; i < n; ++i)
-        lst[i] = {SumToProbability(ts[base[k] + i], pdesc[w.dp].num_points), static_cast<int32_t>(i)};
-      IntroSort(lst.data(), lst.data() + n,
-                [](const std::pair<float, int32_t>& a, const std::pair<float, int32_t>& b) {
-                  return a.first > b.first;
-                },
-                8);
-      c.pos.resize(n);
-      for (int64_t i = 0; i < n; ++i) c.pos[lst[i].second] = i;
-    }
-  }
+  std::vector<TopList> tl;
+  if ((rc = TopLists3(dev, submaps, pdesc, perm, &tl))) return rc;
   // (4) The reference's first leaf among the live ones.
-  for (size_t wi = 0; wi < work.size(); ++wi) {
-    const Work& w = work[wi];
-    const Cand& c = cand[wi];
-    const Pair3Desc& d = pdesc[w.dp];
-    const int step = 1 << w.D;
-    auto top_pos = [&](const Anc& a) {
-      const int ix = (a.x + d.wxy) / step, iy = (a.y + d.wxy) / step, iz = (a.z + d.wz) / step;
-      return c.pos[((static_cast<int64_t>(a.yaw) * c.nz + iz) * c.ny + iy) * c.nx + ix];
-    };
-    auto first = [&](int a, int b) {
-      for (int l = w.D; l >= 0; --l) {
-        const Anc x = anc(w, a, l), y = anc(w, b, l);
-        if (x.yaw == y.yaw && x.x == y.x && x.y == y.y && x.z == y.z) continue;
-        if (l == w.D) {  // lowest-resolution candidates: score, then the sorted order
-          if (l > 0 && x.score != y.score) return x.score > y.score;
-          return top_pos(x) < top_pos(y);
-        }
-        if (l > 0 && x.score != y.score) return x.score > y.score;
-        // Siblings of one parent: generation order (z, then y, then x).
-        return std::make_tuple(x.z, x.y, x.x) < std::make_tuple(y.z, y.y, y.x);
-      }
-      return false;
-    };
-    int best = c.live[0];
-    for (size_t i = 1; i < c.live.size(); ++i)
-      if (first(c.live[i], best)) best = c.live[i];
-    const unsigned long long mask = (1ull << d.key_shift) - 1;
-    const unsigned long long sum = (*keys)[w.dp] >> d.key_shift;
-    (*keys)[w.dp] = (sum << d.key_shift) |
-                    (~LeafId3(d, lv[best].x, lv[best].y, lv[best].z, lv[best].w) & mask);
+  for (const Work& w : work) {
+    if (w.live.leaves.empty()) {
+      // Unreachable: the search records a leaf's yaw as its index among the
+      // pair's num_yaws, so none was left out above. As in the walk, never
+      // return a leaf that is not the reference's: the pair's result is void.
+      (*stat_io)[w.dp] = CSM_ERANGE;
+      continue;
+    }
+    auto top_pos = [&](const TieNode& n) { return tl[w.top].Pos(n); };
+    const TieNode& best = w.chains.at(FirstVisitedLeaf(w.chains, w.live.leaves, top_pos, SiblingsZYX), 0);
+    (*keys)[w.dp] = LeafKey3(pdesc[w.dp], (*keys)[w.dp], best.rot, best.x, best.y, best.z);
   }
-  // (5) Pairs whose passing tied leaves overflow the record: the whole
-  // lowest-resolution list scored and sorted as in (3), and the device walks
-  // the reference's visiting order from it (fast3d_walk); only entries whose
-  // sum reaches the maximum can lead to the pick.
-  if (!walk.empty()) {
-    std::vector<Score3Job> tj;
-    std::vector<int4> tq;
-    std::vector<int64_t> base(walk.size());
-    std::vector<int> wD(walk.size());
-    for (size_t k = 0; k < walk.size(); ++k) {
-      const Pair3Desc& d = pdesc[walk[k]];
-      const int D = submaps[d.submap]->desc.num_levels - 1, step = 1 << D;
-      wD[k] = D;
-      base[k] = static_cast<int64_t>(tq.size());
-      for (int j = 0; j < d.num_yaws; ++j) {
-        Score3Job job{d.yaw_begin + j, static_cast<int32_t>(tq.size()), 0, 0};
-        for (int z = -d.wz; z <= d.wz; z += step)  // GenerateLowestResolutionCandidates (:297-330)
-          for (int y = -d.wxy; y <= d.wxy; y += step)
-            for (int x = -d.wxy; x <= d.wxy; x += step) tq.push_back(make_int4(D, x, y, z));
-        job.count = static_cast<int32_t>(tq.size()) - job.first;
-        tj.push_back(job);
-      }
-    }
-    std::vector<int32_t> ts;
-    if ((rc = score(tj, tq, &ts))) return rc;
-    std::vector<Walk3Job> wj;
-    std::vector<int4> wtop;
-    for (size_t k = 0; k < walk.size(); ++k) {
-      const Pair3Desc& d = pdesc[walk[k]];
-      const int64_t n = (k + 1 < walk.size() ? base[k + 1] : static_cast<int64_t>(tq.size())) - base[k];
-      std::vector<std::pair<float, int32_t>> lst(n);
-      for (int64_t i = 0; i < n; ++i)
-        lst[i] = {SumToProbability(ts[base[k] + i], d.num_points), static_cast<int32_t>(i)};
-      IntroSort(lst.data(), lst.data() + n,
-                [](const std::pair<float, int32_t>& a, const std::pair<float, int32_t>& b) {
-                  return a.first > b.first;
-                },
-                8);
-      const int32_t target = static_cast<int32_t>((*keys)[walk[k]] >> d.key_shift);
-      Walk3Job j{walk[k], target, wD[k], static_cast<int32_t>(wtop.size()), 0, {0, 0, 0}};
-      const int per_yaw = static_cast<int>(n / std::max(1, d.num_yaws));
-      for (const auto& e : lst) {
-        const int32_t sum = ts[base[k] + e.second];
-        if (sum < target) continue;
-        const int4 q = tq[base[k] + e.second];
-        const int yaw = e.second / per_yaw;
-        wtop.push_back(make_int4(yaw, (q.y & 0xffff) | (q.z << 16), q.w, sum));
-      }
-      j.top_count = static_cast<int32_t>(wtop.size()) - j.top_first;
-      wj.push_back(j);
-    }
-    const size_t o_top = sizeof(Walk3Job) * wj.size();
-    const size_t o_out = o_top + sizeof(int4) * std::max<size_t>(wtop.size(), 1);
-    const size_t bytes = o_out + 2 * sizeof(int4) * wj.size();
-    if ((rc = ctx->f3_walk_buf.Reserve(bytes))) return rc;
-    char* dw = ctx->f3_walk_buf.as<char>();
-    std::vector<char> hw(o_out);
-    std::memcpy(hw.data(), wj.data(), o_top);
-    if (!wtop.empty()) std::memcpy(hw.data() + o_top, wtop.data(), sizeof(int4) * wtop.size());
-    CSM_HIP(hipMemcpyAsync(dw, hw.data(), o_out, hipMemcpyHostToDevice, st));
-    CSM_HIP(LaunchFast3dWalk(static_cast<int>(wj.size()), st, dsub, dpairs, dyaws,
-                             ctx->f3_points.as<float>(), ctx->f3_low_points.as<float>(),
-                             reinterpret_cast<const Walk3Job*>(dw),
-                             reinterpret_cast<const int4*>(dw + o_top),
-                             reinterpret_cast<int4*>(dw + o_out)));
-    std::vector<int4> found(2 * wj.size());
-    CSM_HIP(hipMemcpyAsync(found.data(), dw + o_out, 2 * sizeof(int4) * wj.size(),
-                           hipMemcpyDeviceToHost, st));
-    CSM_HIP(hipStreamSynchronize(st));
-    for (size_t k = 0; k < walk.size(); ++k) {
-      const int dp = walk[k];
-      const Pair3Desc& d = pdesc[dp];
-      if (!found[2 * k + 1].x) {
-        // Unreachable (the maximum is a passing leaf's sum and the walk visits
-        // every node whose sum reaches it): never return a leaf that is not
-        // the reference's, the pair's result is void.
-        (*stat_io)[dp] = CSM_ERANGE;
-        continue;
-      }
-      const int4 f = found[2 * k];
-      const unsigned long long mask = (1ull << d.key_shift) - 1;
-      const unsigned long long sum = (*keys)[dp] >> d.key_shift;
-      (*keys)[dp] = (sum << d.key_shift) | (~LeafId3(d, f.x, f.y, f.z, f.w) & mask);
-    }
-  }
+  // (5) Pairs whose passing tied leaves overflow the record.
+  if (!walk.empty() && (rc = WalkTies3(dev, submaps, pdesc, walk, keys, stat_io))) return rc;
   return CSM_OK;
 }
 
