@@ -1440,7 +1440,8 @@ int csm_fast2d_match_batch(csm_context* ctx, csm_fast2d* const* submaps, int32_t
 }
 
 // One single Match / MatchFullSubmap call waiting in its owner's queue.
-struct SingleReq2 {
+namespace csm {
+struct SingleReq2 : CoalesceReq {
   const csm_fast2d* m;
   int full;
   csm_pose2d initial;
@@ -1448,26 +1449,31 @@ struct SingleReq2 {
   int32_t n;
   float min_score;
   csm_result2d res;
-  int rc;
-  bool done;
 };
+}  // namespace csm
 
-constexpr int kCoalesceCap = 512;  // pairs per coalesced batch
-// Batches of queued single calls in flight, and a leader's longest wait for
-// more callers (A/B: CSM_COALESCE_LEADERS, CSM_COALESCE_WINDOW_US).
-static int CoalesceLeaders() {
-  static const int v = [] {
-    const char* e = std::getenv("CSM_COALESCE_LEADERS");
-    return e ? std::max(1, std::atoi(e)) : 3;
+// The 2D coalescer's knobs, read once per process (A/B runs): 3 batches of up
+// to 512 pairs in flight, a leader waiting up to 150 us for more callers.
+// share: the batch's part of the persistent grid, 1/share of it. The default
+// is the whole grid (a second batch's workgroups start as the first one's
+// drain; measured 11.3k -> 12.7k pairs/s at 16 threads against a share per
+// leader, profiles/r5r/); 0: one share per leader running.
+struct CoalesceKnobs2 {
+  CoalesceKnobs co;
+  int share;
+};
+static const CoalesceKnobs2& SingleKnobs2() {
+  static const CoalesceKnobs2 knobs = [] {
+    auto env = [](const char* name, int lowest, int otherwise) {
+      const char* e = std::getenv(name);
+      return e ? std::max(lowest, std::atoi(e)) : otherwise;
+    };
+    const char* on = std::getenv("CSM_SINGLE_COALESCE");
+    return CoalesceKnobs2{{!(on && std::strcmp(on, "0") == 0), env("CSM_COALESCE_LEADERS", 1, 3),
+                           env("CSM_COALESCE_WINDOW_US", 0, 150), /*cap=*/512},
+                          env("CSM_COALESCE_SHARE", 0, 1)};
   }();
-  return v;
-}
-static int CoalesceWindowUs() {
-  static const int v = [] {
-    const char* e = std::getenv("CSM_COALESCE_WINDOW_US");
-    return e ? std::max(0, std::atoi(e)) : 150;
-  }();
-  return v;
+  return knobs;
 }
 
 // Searches queued single calls as batches on one call context of `owner`: all
@@ -1534,17 +1540,10 @@ static int RunSingleBatch(csm_context* owner, const std::vector<SingleReq2*>& re
   return CSM_OK;
 }
 
-// The reference's tasks call Match / MatchFullSubmap concurrently from
-// ThreadPool workers (constraint_builder_2d.cc:100-111, :188-215). One call
-// is one pair, far too little to fill the GPU, so concurrent callers of one
-// owner context are coalesced: each queues its pair; a caller that finds
-// fewer than CoalesceLeaders() (3) batches running becomes a leader, waits up
-// to CoalesceWindowUs() (150 us) for as many callers as the previous batch
-// had, takes the
-// queue and searches it as one batch on a call context, then wakes the
-// callers it served. Results are the same as one call at a time (a pair's
-// result does not depend on its batch). CSM_SINGLE_COALESCE=0 runs each call
-// alone on its own call context.
+// Concurrent single calls on one owner context are coalesced into batches
+// (single_coalesce.h), a leader waiting for as many callers as the previous
+// batch had. CSM_SINGLE_COALESCE=0 runs each call alone on its own call
+// context, with one share of the grid per call in flight.
 static int SingleMatch(const csm_fast2d* m, const csm_pose2d* initial, int full,
                        const float* xyz, int32_t n, float min_score, float* score,
                        csm_pose2d* pose) {
@@ -1555,70 +1554,14 @@ static int SingleMatch(const csm_fast2d* m, const csm_pose2d* initial, int full,
     explicit InFlight(std::atomic<int>& a) : c(a) { ++c; }
     ~InFlight() { --c; }
   } in_flight(owner->calls_in_flight);
-  SingleReq2 r{m, full, full ? csm_pose2d{0., 0., 0.} : *initial, xyz, n, min_score, {}, CSM_OK, false};
-  static const bool coalesce = [] {
-    const char* e = std::getenv("CSM_SINGLE_COALESCE");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  if (!coalesce) {
-    std::vector<SingleReq2*> one{&r};
-    try {
-      r.rc = RunSingleBatch(owner, one, owner->calls_in_flight.load());
-    } catch (...) {  // no exception crosses the C-ABI
-      r.rc = CSM_ENOMEM;
-    }
-  } else {
-    std::unique_lock<std::mutex> lk(owner->co_mu);
-    owner->co_queue.push_back(&r);
-    owner->co_cv.notify_all();
-    while (!r.done) {
-      const bool queued = std::find(owner->co_queue.begin(), owner->co_queue.end(), &r) !=
-                          owner->co_queue.end();
-      if (queued && owner->co_leaders < CoalesceLeaders()) {
-        ++owner->co_leaders;
-        const size_t want = static_cast<size_t>(std::max(1, owner->co_last_batch));
-        const auto deadline =
-            std::chrono::steady_clock::now() + std::chrono::microseconds(CoalesceWindowUs());
-        while (owner->co_queue.size() < want &&
-               owner->co_cv.wait_until(lk, deadline) != std::cv_status::timeout) {
-        }
-        const size_t take_n = std::min<size_t>(owner->co_queue.size(), kCoalesceCap);
-        std::vector<SingleReq2*> take;
-        for (size_t i = 0; i < take_n; ++i) take.push_back(static_cast<SingleReq2*>(owner->co_queue[i]));
-        owner->co_queue.erase(owner->co_queue.begin(), owner->co_queue.begin() + take_n);
-        owner->co_last_batch = static_cast<int>(take_n);
-        // The batch's share of the persistent grid: the whole grid (a
-        // second batch's workgroups start as the first one's drain; measured
-        // 11.3k -> 12.7k pairs/s at 16 threads against a share per leader,
-        // profiles/r5r/). CSM_COALESCE_SHARE=n: 1/n of it; 0: one share per
-        // leader running.
-        static const int fixed_share = [] {
-          const char* e = std::getenv("CSM_COALESCE_SHARE");
-          return e ? std::max(0, std::atoi(e)) : 1;
-        }();
-        const int share = fixed_share ? fixed_share : owner->co_leaders;
-        lk.unlock();
-        // Whatever happens in the batch (an allocation that throws), every
-        // request taken is answered and the leader slot given back below;
-        // otherwise their callers would wait on co_cv forever.
-        int rc;
-        try {
-          rc = RunSingleBatch(owner, take, share);
-        } catch (...) {
-          rc = CSM_ENOMEM;
-        }
-        lk.lock();
-        for (SingleReq2* q : take) {
-          q->rc = rc;
-          q->done = true;
-        }
-        --owner->co_leaders;
-        owner->co_cv.notify_all();
-      } else {
-        owner->co_cv.wait(lk);
-      }
-    }
-  }
+  SingleReq2 r{{}, m, full, full ? csm_pose2d{0., 0., 0.} : *initial, xyz, n, min_score, {}};
+  const CoalesceKnobs2& knobs = SingleKnobs2();
+  owner->coalesce2.Call(&r, knobs.co, WantLastBatch,
+                        [&](const std::vector<SingleReq2*>& batch, int leaders_running) {
+                          int share = knobs.share ? knobs.share : leaders_running;
+                          if (!knobs.co.on) share = owner->calls_in_flight.load();
+                          return RunSingleBatch(owner, batch, share);
+                        });
   if (r.rc < 0) return r.rc;
   if (r.res.status == CSM_OK) {
     *score = r.res.score;

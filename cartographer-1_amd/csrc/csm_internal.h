@@ -18,6 +18,7 @@
 #include "csm_device.h"
 #include "csm_device3d.h"
 #include "search_window.h"
+#include "single_coalesce.h"
 
 namespace csm {
 
@@ -25,6 +26,10 @@ namespace csm {
   do {                                              \
     if ((call) != hipSuccess) return CSM_EHIP;      \
   } while (0)
+
+// One queued single call (csm_host.cc, host3d.cc).
+struct SingleReq2;
+struct SingleReq3;
 
 // Frees every context's idle pooled buffers (BufPool below); a device
 // allocation that fails calls it and tries once more.
@@ -281,21 +286,13 @@ struct csm_context {
   csm_context* call_owner = nullptr;  // set on call contexts
   std::atomic<int> calls_in_flight{0};  // single calls running on this owner's call contexts
   int grid_share = 1;  // a call context's search launch takes 1/grid_share of the GPU
-  // Coalesced single 2D calls (csm_host.cc SingleMatch): concurrent callers of
-  // this owner queue their pairs; a leader takes the queue after a short
-  // window and searches it as one batch on a call context, at most
-  // kCoalesceLeaders batches at a time.
-  std::mutex co_mu;
-  std::condition_variable co_cv;
-  std::vector<void*> co_queue;
-  int co_leaders = 0;
-  int co_last_batch = 1;  // the last batch's size: the next leader waits for as many
-  // The same for single 3D calls (host3d.cc SingleMatch3), under co_mu.
-  std::vector<void*> co3_queue;
-  int co3_leaders = 0;
-  int co3_last_batch = 1;
-  int co3_in_flight = 0;  // single 3D calls between queueing and their return
-  int co3_callers = 0;    // recent high-water of co3_in_flight (one less per batch)
+  // Coalesced single calls (single_coalesce.h): concurrent callers of this
+  // owner queue their pairs; a leader takes the queue after a short window and
+  // searches it as one batch on a call context, at most CoalesceKnobs::leaders
+  // batches at a time. 2D (csm_host.cc SingleMatch) and 3D (host3d.cc
+  // SingleMatch3) each have their own queue, lock and knobs.
+  csm::SingleCoalescer<csm::SingleReq2> coalesce2;
+  csm::SingleCoalescer<csm::SingleReq3> coalesce3;
   csm_timing call_t{};                // finished single calls' timing (call_mu)
   csm_scan_set single;                // the cloud of the current single 2D call
   csm::PinnedBuf single_stage;

@@ -34,6 +34,7 @@
 #include "csm_device3d.h"
 #include "csm_internal.h"
 #include "csm_launch3d.h"
+#include "host_pool.h"
 #include "tie_order.h"
 #include "rt3d_select.h"
 
@@ -1350,90 +1351,6 @@ void BuildYaws(const int32_t* ks, const float* scores, int count, int32_t pair,
   }
 }
 
-// A persistent pool of host workers for the batch's per-pair host phases
-// (spawning threads per phase cost ~1 ms per phase on the GPU box).
-class HostPool {
- public:
-  static HostPool& Get() {
-    static HostPool pool;
-    return pool;
-  }
-  // Runs f(i) for i in [0, num) on the workers and the calling thread.
-  void Run(int64_t num, const std::function<void(int64_t)>& f) {
-    if (num <= 0) return;
-    std::unique_lock<std::mutex> lock(mu_);  // one batch phase at a time
-    {
-      std::lock_guard<std::mutex> g(state_);
-      f_ = &f;
-      num_ = num;
-      next_.store(0);
-      active_ = static_cast<int>(workers_.size());
-      ++epoch_;
-    }
-    cv_.notify_all();
-    Work(f, num);
-    std::unique_lock<std::mutex> g(state_);
-    done_.wait(g, [&] { return active_ == 0; });
-    f_ = nullptr;
-  }
-  ~HostPool() {
-    {
-      std::lock_guard<std::mutex> g(state_);
-      stop_ = true;
-      ++epoch_;
-    }
-    cv_.notify_all();
-    for (auto& t : workers_) t.join();
-  }
-
- private:
-  HostPool() {
-    const int nt = static_cast<int>(
-        std::max<unsigned>(1, std::min<unsigned>(16, std::thread::hardware_concurrency())));
-    for (int t = 1; t < nt; ++t) workers_.emplace_back([this] { Loop(); });
-  }
-  void Work(const std::function<void(int64_t)>& f, int64_t num) {
-    for (int64_t i = next_.fetch_add(1); i < num; i = next_.fetch_add(1)) f(i);
-  }
-  void Loop() {
-    uint64_t seen = 0;
-    for (;;) {
-      const std::function<void(int64_t)>* f;
-      int64_t num;
-      {
-        std::unique_lock<std::mutex> g(state_);
-        cv_.wait(g, [&] { return stop_ || epoch_ != seen; });
-        if (stop_) return;
-        seen = epoch_;
-        f = f_;
-        num = num_;
-      }
-      Work(*f, num);
-      std::lock_guard<std::mutex> g(state_);
-      if (--active_ == 0) done_.notify_one();
-    }
-  }
-  std::mutex mu_, state_;
-  std::condition_variable cv_, done_;
-  std::vector<std::thread> workers_;
-  const std::function<void(int64_t)>* f_ = nullptr;
-  int64_t num_ = 0;
-  std::atomic<int64_t> next_{0};
-  int active_ = 0;
-  uint64_t epoch_ = 0;
-  bool stop_ = false;
-};
-
-template <typename F>
-void ParallelPairs(int64_t num, F&& f) {
-  if (num < 64) {  // not worth waking the pool
-    for (int64_t i = 0; i < num; ++i) f(i);
-    return;
-  }
-  const std::function<void(int64_t)> fn = f;
-  HostPool::Get().Run(num, fn);
-}
-
 uint64_t LeafId3(const Pair3Desc& d, int yaw, int x, int y, int z) {  // kernels3d.hip LeafId
   uint64_t id = static_cast<uint64_t>(yaw);
   id = (id << d.bits_xy) | static_cast<uint64_t>(x + d.wxy);
@@ -2485,19 +2402,33 @@ int csm_fast3d_discrete_scans(csm_context* ctx, csm_fast3d* m, const csm_node3d*
   return CSM_OK;
 }
 
-namespace {
-
 // One single Match / MatchFullSubmap call waiting in its owner's queue.
-struct SingleReq3 {
+namespace csm {
+struct SingleReq3 : CoalesceReq {
   const csm_fast3d* m;
   csm_pair3d pair;
   const csm_node3d* node;
   csm_result3d res;
-  int rc;
-  bool done;
 };
+}  // namespace csm
 
-constexpr int kCoalesceCap3 = 512;  // pairs per coalesced batch
+namespace {
+
+// The 3D coalescer's knobs, read once per process (A/B runs): 2 batches of up
+// to 512 pairs in flight, a leader waiting up to 300 us for its share of the
+// callers.
+const CoalesceKnobs& SingleKnobs3() {
+  static const CoalesceKnobs knobs = [] {
+    auto env = [](const char* name, int lowest, int otherwise) {
+      const char* e = std::getenv(name);
+      return e ? std::max(lowest, std::atoi(e)) : otherwise;
+    };
+    const char* on = std::getenv("CSM_SINGLE_COALESCE");
+    return CoalesceKnobs{!(on && std::strcmp(on, "0") == 0), env("CSM_COALESCE_LEADERS3", 1, 2),
+                         env("CSM_COALESCE_WINDOW_US3", 0, 300), /*cap=*/512};
+  }();
+  return knobs;
+}
 
 // Searches queued single calls as one batch on a call context of `owner`:
 // the distinct matchers as the batch's submaps, one node per request.
@@ -2529,85 +2460,18 @@ int RunSingleBatch3(csm_context* owner, const std::vector<SingleReq3*>& reqs) {
   return CSM_OK;
 }
 
-// Concurrent single 3D calls on one owner context are coalesced (as in 2D,
-// csm_host.cc SingleMatch): each queues its pair; a caller that finds fewer
-// than CSM_COALESCE_LEADERS3 (2) batches running becomes a leader, waits up
-// to CSM_COALESCE_WINDOW_US3 (300 us) until the queue holds its share of the
-// callers, ceil(callers / leaders), searches the queue as one batch and
-// wakes the callers it served. `callers` is the owner's recent high-water
-// mark of calls in flight (decaying by one per batch), so with T threads
-// calling back to back two batches of about T / 2 alternate, one searching
-// while the other's callers return and queue again. A 3D pair costs a few
-// microseconds of device time against ~0.3 ms of fixed latency per batch
-// (the pipeline's launches, copies and synchronizations), so batch size,
-// not device time, sets the single-call rate: the previous rule (wait for
-// as many callers as the previous batch had, 3 leaders) settled at ~2
-// pairs per batch (profiles/r6h/). A pair's result does not depend on its
-// batch. CSM_SINGLE_COALESCE=0: each call alone on its own call context.
+// Concurrent single 3D calls on one owner context are coalesced into batches
+// (single_coalesce.h), a leader waiting until the queue holds its share of
+// the callers, ceil(callers / leaders). CSM_SINGLE_COALESCE=0: each call
+// alone on its own call context.
 int SingleMatch3(const csm_fast3d* m, const csm_pair3d& pair, const csm_node3d* node,
                  csm_result3d* result) {
   csm_context* owner = m->ctx;
-  SingleReq3 r{m, pair, node, csm_result3d{}, CSM_OK, false};
-  static const bool coalesce = [] {
-    const char* e = std::getenv("CSM_SINGLE_COALESCE");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  static const int leaders = [] {
-    const char* e = std::getenv("CSM_COALESCE_LEADERS3");
-    return e ? std::max(1, std::atoi(e)) : 2;
-  }();
-  static const int window_us = [] {
-    const char* e = std::getenv("CSM_COALESCE_WINDOW_US3");
-    return e ? std::max(0, std::atoi(e)) : 300;
-  }();
-  if (!coalesce) {
-    std::vector<SingleReq3*> one{&r};
-    try {
-      r.rc = RunSingleBatch3(owner, one);
-    } catch (...) {  // no exception crosses the C-ABI
-      r.rc = CSM_ENOMEM;
-    }
-  } else {
-    std::unique_lock<std::mutex> lk(owner->co_mu);
-    owner->co3_queue.push_back(&r);
-    owner->co3_callers = std::max(owner->co3_callers, ++owner->co3_in_flight);
-    owner->co_cv.notify_all();
-    while (!r.done) {
-      const bool queued = std::find(owner->co3_queue.begin(), owner->co3_queue.end(), &r) !=
-                          owner->co3_queue.end();
-      if (queued && owner->co3_leaders < leaders) {
-        ++owner->co3_leaders;
-        owner->co3_callers = std::max(owner->co3_in_flight, owner->co3_callers - 1);
-        const size_t want = static_cast<size_t>((owner->co3_callers + leaders - 1) / leaders);
-        const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(window_us);
-        while (owner->co3_queue.size() < want &&
-               owner->co_cv.wait_until(lk, deadline) != std::cv_status::timeout) {
-        }
-        const size_t take_n = std::min<size_t>(owner->co3_queue.size(), kCoalesceCap3);
-        std::vector<SingleReq3*> take;
-        for (size_t i = 0; i < take_n; ++i) take.push_back(static_cast<SingleReq3*>(owner->co3_queue[i]));
-        owner->co3_queue.erase(owner->co3_queue.begin(), owner->co3_queue.begin() + take_n);
-        owner->co3_last_batch = static_cast<int>(take_n);
-        lk.unlock();
-        int rc;  // as in 2D: every request taken is answered, whatever the batch throws
-        try {
-          rc = RunSingleBatch3(owner, take);
-        } catch (...) {
-          rc = CSM_ENOMEM;
-        }
-        lk.lock();
-        for (SingleReq3* q : take) {
-          q->rc = rc;
-          q->done = true;
-        }
-        --owner->co3_leaders;
-        owner->co_cv.notify_all();
-      } else {
-        owner->co_cv.wait(lk);
-      }
-    }
-    --owner->co3_in_flight;
-  }
+  SingleReq3 r{{}, m, pair, node, csm_result3d{}};
+  owner->coalesce3.Call(&r, SingleKnobs3(), WantShareOfCallers,
+                        [&](const std::vector<SingleReq3*>& batch, int /*leaders_running*/) {
+                          return RunSingleBatch3(owner, batch);
+                        });
   *result = r.res;
   if (r.rc < 0) return r.rc;
   return result->status;

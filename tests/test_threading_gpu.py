@@ -111,7 +111,7 @@ def test_threads_on_several_handles(csm, world, cases):
     ctx.enable_timing(False)
     _check(got, refs + refs, cs + cs)
     t = ctx.timing()
-    # Concurrent calls are coalesced into batches (csm_host.cc SingleMatch):
+    # Concurrent calls are coalesced into batches (csrc/single_coalesce.h):
     # fewer launches than calls, every call counted once among them.
     assert 1 <= t.search_launches < 2 * len(cs), t.search_launches
     assert t.search_errors == 0
@@ -183,7 +183,8 @@ def test_threads_3d_single_calls(csm):
 
 def test_threads_3d_single_calls_several_matchers(csm):
     """Concurrent single 3D calls on three matchers of one context are
-    coalesced into shared batches (host3d.cc SingleMatch3): 16 threads, each
+    coalesced into shared batches (csrc/single_coalesce.h, the 3D rule): 16
+    threads, each
     result equal to the batch path's for the same pair."""
     w = csm.SyntheticWorld3D(num_nodes=24, num_submaps=3, seed=7)
     o = csm.FastCorrelativeScanMatcherOptions3D()
@@ -228,3 +229,34 @@ def test_cpp_threads_match_single_thread_results():
     assert out.returncode == 0, (out.stdout, out.stderr)
     r = json.loads(out.stdout.strip().splitlines()[-1])
     assert r["mismatches"] == 0 and r["matched"] > 0, r
+
+
+def _tool_without_coalescing(name, *args, timeout):
+    """A tools/ program in a fresh process with CSM_SINGLE_COALESCE=0 (the
+    switch is read once per process): every single call runs alone on its own
+    call context. Returns its JSON line."""
+    import json
+    import os
+    import subprocess
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", name)
+    assert os.path.exists(exe), "build() makes tools/" + name
+    out = subprocess.run([exe, *args], capture_output=True, text=True, timeout=timeout,
+                         env=dict(os.environ, CSM_SINGLE_COALESCE="0"))
+    assert out.returncode == 0, (out.stdout, out.stderr)
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_cpp_threads_without_coalescing_2d():
+    """test_cpp_threads_match_single_thread_results with coalescing off.
+    Measured at 0.6 s on an MI355X; the limit leaves room for a cold start."""
+    r = _tool_without_coalescing("dropin_threads", "0", "0.55", "--check", timeout=60)
+    assert r["mismatches"] == 0 and r["matched"] > 0, r
+
+
+def test_cpp_threads_without_coalescing_3d():
+    """tools/dropin_threads3d with coalescing off on its smallest useful
+    slice, 128 calls on 2 submaps x 16 nodes from 1 to 32 threads: every
+    result equals the batch path's. Measured at 0.9 s on an MI355X; the limit
+    leaves room for a cold start."""
+    r = _tool_without_coalescing("dropin_threads3d", "128", "2", "16", timeout=60)
+    assert r["mismatches_vs_batch"] == 0, r
