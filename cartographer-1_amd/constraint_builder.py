@@ -245,6 +245,149 @@ def _budget_parts(pending, key_of, cache: _MatcherCache, make, bytes_of):
         cache.trim()
 
 
+class _ConstraintBuilderBase:
+    """The host skeleton ConstraintBuilder2D and ConstraintBuilder3D share (the
+    mirror of include/cartographer_amd/constraint_builder_base.h): submission
+    slots, samplers, the budgeted matcher cache, flushing in parts that fit
+    the budget, the walk over a searched batch, DeleteScanMatcher, WhenDone.
+
+    A subclass sets ``_name`` (its name in stderr messages), ``_metrics`` and
+    ``_num_scores``, and provides ``_make_matcher(p)`` (with ``_bytes_of`` if a
+    matcher is more than one object), ``_log_when_done(computations,
+    constraints)`` and ``_run_batch(pending, held)``, which searches one batch
+    on the device and returns per pair ``(status, scores, constraint,
+    match_line)``: the last three are read only when the status is CSM_OK, the
+    line only if ``log_matches``. A pending pair ``p`` is the subclass's own
+    object with ``submap_id``, ``full`` and a ``slot`` the base assigns."""
+    _name = ""
+    _metrics: _BuilderMetrics
+    _num_scores = 1
+
+    def __init__(self, options: "ConstraintBuilderOptions", context: Optional[Context] = None):
+        self.options = options
+        self._histograms = [_metrics.ScoreHistogram() for _ in range(self._num_scores)]
+        self.score_histogram = self._histograms[0]  # score_histogram_
+        self.log_sink = _LOG.info  # where the log_matches lines go (LOG(INFO))
+        self.context = context or default_context()
+        self._matchers = _MatcherCache(options.matcher_cache_bytes)
+        self._samplers: Dict[Tuple[int, int], FixedRatioSampler] = {}
+        self._constraints: list = []
+        self._pending: list = []
+        self._started_nodes = 0
+        self._finished_nodes = 0
+        self.constraints_searched = 0
+        self.constraints_found = 0
+        self.global_constraints_searched = 0
+        self.global_constraints_found = 0
+        self.constraints_failed = 0  # pairs skipped on a device error status
+        self.last_error = CSM_OK
+        self.constraint_scores: List[float] = []
+        self.global_constraint_scores: List[float] = []
+
+    def NotifyEndOfNode(self):
+        self._started_nodes += 1
+        if len(self._pending) >= self.options.flush_pairs:
+            self._flush()
+
+    def WhenDone(self, callback: Callable[[list], None]):
+        self._flush()
+        result = [c for c in self._constraints if c is not None]
+        if self.options.log_matches:
+            self._log_when_done(len(self._constraints), len(result))
+        self._constraints = []
+        self._metrics.queue_length.Set(len(self._constraints))
+        callback(result)
+
+    def GetNumFinishedNodes(self) -> int:
+        return self._finished_nodes
+
+    def DeleteScanMatcher(self, submap_id):
+        """Also drops the submap's pending pairs (no constraint), as the C++
+        header does."""
+        key = tuple(submap_id)
+        self._matchers.pop(key, _MatcherCache._close)  # a 3D matcher, then its grids
+        self._metrics.num_submap_scan_matchers.Set(len(self._matchers))
+        self._samplers.pop(key, None)
+        before = len(self._pending)
+        self._pending = [p for p in self._pending if p.submap_id != key]
+        if len(self._pending) != before:
+            print(f"{self._name}: DeleteScanMatcher dropped {before - len(self._pending)} "
+                  "pending pairs of a deleted submap", file=sys.stderr)
+
+    @property
+    def num_submap_scan_matchers(self) -> int:  # kNumSubmapScanMatchersMetric
+        return len(self._matchers)
+
+    @staticmethod
+    def _bytes_of(matcher):
+        return matcher.device_bytes()
+
+    def _sample(self, submap_id) -> bool:
+        """MaybeAddConstraint's per-submap FixedRatioSampler."""
+        sampler = self._samplers.setdefault(tuple(submap_id),
+                                            FixedRatioSampler(self.options.sampling_ratio))
+        return sampler.Pulse()
+
+    def _enqueue(self, p):
+        self._constraints.append(None)
+        self._metrics.queue_length.Set(len(self._constraints))
+        p.slot = len(self._constraints) - 1
+        # DispatchScanMatcherConstruction at enqueue, via the cache.
+        self._matchers.get(p.submap_id, lambda: self._make_matcher(p), self._bytes_of)
+        self._matchers.pinned.discard(p.submap_id)
+        self._matchers.trim()
+        self._metrics.num_submap_scan_matchers.Set(len(self._matchers))
+        self._pending.append(p)
+
+    def _flush(self):
+        pending, self._pending = self._pending, []
+        if pending:
+            for part, held in _budget_parts(pending, lambda p: p.submap_id, self._matchers,
+                                            self._make_matcher, self._bytes_of):
+                self._search(part, held)
+        self._finished_nodes = self._started_nodes
+
+    def _note_scores(self, p, scores):
+        (self.global_constraint_scores if p.full else self.constraint_scores).append(scores[0])
+
+    def _search(self, pending, held):
+        """One batch over the matchers in ``held``, then the walk over it."""
+        m = self._metrics
+        failed = 0
+        for p, (status, scores, constraint, line) in zip(pending, self._run_batch(pending, held)):
+            if status < 0:
+                # Not searchable on the device (CSM_ERANGE, DESIGN.md §8):
+                # no constraint, counted, never fatal (as the C++ header).
+                self.constraints_failed += 1
+                self.last_error = status
+                failed += 1
+                continue
+            if p.full:
+                self.global_constraints_searched += 1
+                m.global_searched.Increment()
+            else:
+                self.constraints_searched += 1
+                m.searched.Increment()
+            if status != CSM_OK:
+                continue
+            if p.full:
+                self.global_constraints_found += 1
+                m.global_found.Increment()
+            else:
+                self.constraints_found += 1
+                m.found.Increment()
+            self._note_scores(p, scores)
+            for metric, histogram, v in zip(m.scores[p.full], self._histograms, scores):
+                metric.Observe(v)
+                histogram.Add(v)
+            self._constraints[p.slot] = constraint
+            if self.options.log_matches:
+                self.log_sink(line)
+        if failed:
+            print(f"{self._name}: {failed} of {len(pending)} pairs skipped "
+                  f"({strerror(self.last_error)})", file=sys.stderr)
+
+
 @dataclass
 class Submap2D:
     """What the builder reads of a Submap2D: its grid and local pose
@@ -307,10 +450,11 @@ class _Pending:
     cloud: np.ndarray
     full: bool
     initial: Tuple[float, float, float]
-    slot: int
+    slot: int = -1  # set at enqueue
 
 
-class ConstraintBuilder2D:
+class ConstraintBuilder2D(_ConstraintBuilderBase):
+    _name = "ConstraintBuilder2D"
     _metrics = _BuilderMetrics(False)
 
     @classmethod
@@ -320,27 +464,9 @@ class ConstraintBuilder2D:
         cls._metrics.register(factory, "2d")
 
     def __init__(self, options: ConstraintBuilderOptions, context: Optional[Context] = None):
-        self.options = options
-        self.score_histogram = _metrics.ScoreHistogram()  # score_histogram_ (:239)
-        self.log_sink = _LOG.info  # where the log_matches lines go (LOG(INFO))
-        self.context = context or default_context()
-        self._matchers = _MatcherCache(options.matcher_cache_bytes)
-        self._samplers: Dict[Tuple[int, int], FixedRatioSampler] = {}
-        self._constraints: List[Optional[Constraint]] = []
-        self._pending: List[_Pending] = []
+        super().__init__(options, context)
         self._scans: Optional[ScanSet] = None  # node clouds resident across flushes
         self._scan_cache: Dict[Tuple[int, int], tuple] = {}  # node -> (cloud, index, points)
-        self._started_nodes = 0
-        self._finished_nodes = 0
-        # Metrics (constraint_builder_2d.cc:46-53).
-        self.constraints_searched = 0
-        self.constraints_found = 0
-        self.global_constraints_searched = 0
-        self.global_constraints_found = 0
-        self.constraints_failed = 0  # pairs skipped on a device error status
-        self.last_error = CSM_OK
-        self.constraint_scores: List[float] = []
-        self.global_constraint_scores: List[float] = []
 
     # -- public interface (constraint_builder_2d.h:63-110) ------------------
     def MaybeAddConstraint(self, submap_id, submap: Submap2D, node_id, cloud,
@@ -348,55 +474,23 @@ class ConstraintBuilder2D:
         if math.hypot(initial_relative_pose[0], initial_relative_pose[1]) > \
                 self.options.max_constraint_distance:
             return
-        sampler = self._samplers.setdefault(tuple(submap_id),
-                                            FixedRatioSampler(self.options.sampling_ratio))
-        if not sampler.Pulse():
+        if not self._sample(submap_id):
             return
-        self._enqueue(submap_id, submap, node_id, cloud, False,
-                      rigid2d_compose(submap.local_pose, initial_relative_pose))
+        self._enqueue(_Pending(tuple(submap_id), submap, tuple(node_id), cloud, False,
+                               tuple(rigid2d_compose(submap.local_pose, initial_relative_pose))))
 
     def MaybeAddGlobalConstraint(self, submap_id, submap: Submap2D, node_id, cloud):
-        self._enqueue(submap_id, submap, node_id, cloud, True, (0.0, 0.0, 0.0))
-
-    def NotifyEndOfNode(self):
-        self._started_nodes += 1
-        if len(self._pending) >= self.options.flush_pairs:
-            self._flush()
-
-    def WhenDone(self, callback: Callable[[List[Constraint]], None]):
-        self._flush()
-        result = [c for c in self._constraints if c is not None]
-        if self.options.log_matches:  # RunWhenDoneCallback (:289-293)
-            self.log_sink(f"{len(self._constraints)} computations resulted in {len(result)} "
-                          "additional constraints.")
-            self.log_sink("Score histogram:\n" + self.score_histogram.ToString(10))
-        self._constraints = []
-        self._metrics.queue_length.Set(len(self._constraints))
-        callback(result)
-
-    def GetNumFinishedNodes(self) -> int:
-        return self._finished_nodes
-
-    def DeleteScanMatcher(self, submap_id):
-        """Also drops the submap's pending pairs (no constraint), as the C++
-        header does."""
-        key = tuple(submap_id)
-        self._matchers.pop(key, lambda m: m.close())
-        self._metrics.num_submap_scan_matchers.Set(len(self._matchers))
-        self._samplers.pop(key, None)
-        before = len(self._pending)
-        self._pending = [p for p in self._pending if p.submap_id != key]
-        if len(self._pending) != before:
-            print(f"ConstraintBuilder2D: DeleteScanMatcher dropped {before - len(self._pending)} "
-                  "pending pairs of a deleted submap", file=sys.stderr)
-
-    @property
-    def num_submap_scan_matchers(self) -> int:  # kNumSubmapScanMatchersMetric
-        return len(self._matchers)
+        self._enqueue(_Pending(tuple(submap_id), submap, tuple(node_id), cloud, True,
+                               (0.0, 0.0, 0.0)))
 
     @property
     def matcher_cache(self) -> _MatcherCache:
         return self._matchers
+
+    def _log_when_done(self, computations, constraints):  # RunWhenDoneCallback (:289-293)
+        self.log_sink(f"{computations} computations resulted in {constraints} "
+                      "additional constraints.")
+        self.log_sink("Score histogram:\n" + self.score_histogram.ToString(10))
 
     # -- internals ----------------------------------------------------------
     def _make_matcher(self, p):
@@ -447,104 +541,58 @@ class ConstraintBuilder2D:
                     self._scan_cache[key] = (cloud, first - 1 - k, pts)
         return index
 
-    def _enqueue(self, submap_id, submap, node_id, cloud, full, initial):
-        key = tuple(submap_id)
-        self._constraints.append(None)
-        self._metrics.queue_length.Set(len(self._constraints))  # (:98, :123)
-        p = _Pending(key, submap, tuple(node_id), cloud, full, tuple(initial),
-                     len(self._constraints) - 1)
-        # DispatchScanMatcherConstruction at enqueue (:165-186), via the cache.
-        self._matchers.get(key, lambda: self._make_matcher(p), lambda m: m.device_bytes())
-        self._matchers.pinned.discard(key)
-        self._matchers.trim()
-        self._metrics.num_submap_scan_matchers.Set(len(self._matchers))
-        self._pending.append(p)
-
-    def _flush(self):
-        pending, self._pending = self._pending, []
-        if pending:
-            for part, held in _budget_parts(pending, lambda p: p.submap_id, self._matchers,
-                                            self._make_matcher, lambda m: m.device_bytes()):
-                self._search(part, held)
-        self._finished_nodes = self._started_nodes
-
-    def _search(self, pending, held):
+    def _run_batch(self, pending, held):
         """One batch (and its Ceres refinement) over the matchers in ``held``."""
-        if pending:
-            matchers, slot_of = [], {}
-            submap_idx = []
-            for p in pending:
-                if p.submap_id not in slot_of:
-                    slot_of[p.submap_id] = len(matchers)
-                    matchers.append(held[p.submap_id])
-                submap_idx.append(slot_of[p.submap_id])
-            scans = self._resident_scans()
-            scan_idx = self._scan_indices(pending, scans)
-            pairs = make_pairs(submap_idx, scan_idx, 0.0, full_submap=True)
-            for i, p in enumerate(pending):
-                pairs[i]["full_submap"] = 1 if p.full else 0
-                pairs[i]["min_score"] = (self.options.global_localization_min_score if p.full
-                                         else self.options.min_score)
-                pairs[i]["x"], pairs[i]["y"], pairs[i]["theta"] = p.initial
-            try:
-                results = match_batch(matchers, scans, pairs, self.context)
-                refined = {}
-                ok = [i for i, r in enumerate(results) if int(r["status"]) == CSM_OK]
-                if self.options.refine_with_ceres and ok:
-                    # ceres_scan_matcher_.Match(pose.translation(), pose, cloud, grid)
-                    init = [(float(results[i]["x"]), float(results[i]["y"]),
-                             float(results[i]["theta"])) for i in ok]
-                    poses, _ = ceres_refine_batch(
-                        matchers, scans, [submap_idx[i] for i in ok], [scan_idx[i] for i in ok],
-                        init, [q[:2] for q in init], self.options.ceres_scan_matcher_options,
-                        self.context)
-                    refined = {i: tuple(float(v) for v in poses[k]) for k, i in enumerate(ok)}
-            except BaseException:
-                self._drop_scans()
-                raise
-            failed = 0
-            for i, (p, r) in enumerate(zip(pending, results)):
-                if int(r["status"]) < 0:
-                    # Not searchable on the device (CSM_ERANGE, DESIGN.md §8):
-                    # no constraint, counted, never fatal (as the C++ header).
-                    self.constraints_failed += 1
-                    self.last_error = int(r["status"])
-                    failed += 1
-                    continue
-                m = self._metrics
-                if p.full:
-                    self.global_constraints_searched += 1
-                    m.global_searched.Increment()
-                else:
-                    self.constraints_searched += 1
-                    m.searched.Increment()
-                if int(r["status"]) != CSM_OK:
-                    continue
-                score = float(r["score"])
-                if p.full:
-                    self.global_constraints_found += 1
-                    self.global_constraint_scores.append(score)
-                    m.global_found.Increment()
-                else:
-                    self.constraints_found += 1
-                    self.constraint_scores.append(score)
-                    m.found.Increment()
-                m.scores[p.full][0].Observe(score)
-                self.score_histogram.Add(score)
-                pose = refined.get(i, (float(r["x"]), float(r["y"]), float(r["theta"])))
-                if self.options.log_matches:
-                    self._log_match(p, pose, score)
-                self._constraints[p.slot] = Constraint(
-                    submap_id=p.submap_id, node_id=p.node_id,
-                    relative_pose=rigid2d_compose(rigid2d_inverse(p.submap.local_pose), pose),
-                    translation_weight=self.options.loop_closure_translation_weight,
-                    rotation_weight=self.options.loop_closure_rotation_weight,
-                    score=score)
-            if failed:
-                print(f"ConstraintBuilder2D: {failed} of {len(pending)} pairs skipped "
-                      f"({strerror(self.last_error)})", file=sys.stderr)
+        matchers, slot_of = [], {}
+        submap_idx = []
+        for p in pending:
+            if p.submap_id not in slot_of:
+                slot_of[p.submap_id] = len(matchers)
+                matchers.append(held[p.submap_id])
+            submap_idx.append(slot_of[p.submap_id])
+        scans = self._resident_scans()
+        scan_idx = self._scan_indices(pending, scans)
+        pairs = make_pairs(submap_idx, scan_idx, 0.0, full_submap=True)
+        for i, p in enumerate(pending):
+            pairs[i]["full_submap"] = 1 if p.full else 0
+            pairs[i]["min_score"] = (self.options.global_localization_min_score if p.full
+                                     else self.options.min_score)
+            pairs[i]["x"], pairs[i]["y"], pairs[i]["theta"] = p.initial
+        try:
+            results = match_batch(matchers, scans, pairs, self.context)
+            refined = {}
+            ok = [i for i, r in enumerate(results) if int(r["status"]) == CSM_OK]
+            if self.options.refine_with_ceres and ok:
+                # ceres_scan_matcher_.Match(pose.translation(), pose, cloud, grid)
+                init = [(float(results[i]["x"]), float(results[i]["y"]),
+                         float(results[i]["theta"])) for i in ok]
+                poses, _ = ceres_refine_batch(
+                    matchers, scans, [submap_idx[i] for i in ok], [scan_idx[i] for i in ok],
+                    init, [q[:2] for q in init], self.options.ceres_scan_matcher_options,
+                    self.context)
+                refined = {i: tuple(float(v) for v in poses[k]) for k, i in enumerate(ok)}
+        except BaseException:
+            self._drop_scans()
+            raise
+        outcomes = []
+        for i, (p, r) in enumerate(zip(pending, results)):
+            if int(r["status"]) != CSM_OK:
+                outcomes.append((int(r["status"]), None, None, None))
+                continue
+            score = float(r["score"])
+            pose = refined.get(i, (float(r["x"]), float(r["y"]), float(r["theta"])))
+            constraint = Constraint(
+                submap_id=p.submap_id, node_id=p.node_id,
+                relative_pose=rigid2d_compose(rigid2d_inverse(p.submap.local_pose), pose),
+                translation_weight=self.options.loop_closure_translation_weight,
+                rotation_weight=self.options.loop_closure_rotation_weight,
+                score=score)
+            line = self._match_line(p, pose, score) if self.options.log_matches else None
+            outcomes.append((CSM_OK, (score,), constraint, line))
+        return outcomes
 
-    def _log_match(self, p, pose, score):
+    @staticmethod
+    def _match_line(p, pose, score):
         """ComputeConstraint's log_matches line (:260-276); `pose` is the
         refined pose estimate (map <- node), p.initial the search start."""
         info = (f"Node ({p.node_id[0]}, {p.node_id[1]}) with {len(p.cloud)} points on submap "
@@ -555,7 +603,7 @@ class ConstraintBuilder2D:
             d = rigid2d_compose(rigid2d_inverse(p.initial), pose)
             info += " differs by translation %.2f rotation %.3f" % (
                 math.hypot(d[0], d[1]), abs(_normalize_angle_difference(d[2])))
-        self.log_sink(info + " with score %.1f%%." % (100.0 * score))
+        return info + " with score %.1f%%." % (100.0 * score)
 
 
 # ---------------------------------------------------------------------------
@@ -612,11 +660,13 @@ class _Pending3D:
     full: bool
     node_pose: tuple
     submap_pose: tuple
-    slot: int
+    slot: int = -1  # set at enqueue
 
 
-class ConstraintBuilder3D:
+class ConstraintBuilder3D(_ConstraintBuilderBase):
+    _name = "ConstraintBuilder3D"
     _metrics = _BuilderMetrics(True)
+    _num_scores = 3
 
     @classmethod
     def RegisterMetrics(cls, factory):
@@ -624,28 +674,10 @@ class ConstraintBuilder3D:
         cls._metrics.register(factory, "3d")
 
     def __init__(self, options: ConstraintBuilderOptions, context: Optional[Context] = None):
-        self.options = options
-        # score_histogram_, rotational_score_histogram_, low_resolution_score_histogram_ (:257-259)
-        self.score_histogram = _metrics.ScoreHistogram()
-        self.rotational_score_histogram = _metrics.ScoreHistogram()
-        self.low_resolution_score_histogram = _metrics.ScoreHistogram()
-        self.log_sink = _LOG.info
-        self.context = context or default_context()
-        self._matchers = _MatcherCache(options.matcher_cache_bytes)  # key -> (high, low, m)
+        super().__init__(options, context)  # the cache holds (high, low, matcher) per submap
+        # rotational_score_histogram_, low_resolution_score_histogram_ (:257-259)
+        self.rotational_score_histogram, self.low_resolution_score_histogram = self._histograms[1:]
         self._submaps: Dict[Tuple[int, int], Submap3D] = {}  # for rebuilds of dropped matchers
-        self._samplers: Dict[Tuple[int, int], FixedRatioSampler] = {}
-        self._constraints: List[Optional[Constraint3D]] = []
-        self._pending: List[_Pending3D] = []
-        self._started_nodes = 0
-        self._finished_nodes = 0
-        self.constraints_searched = 0
-        self.constraints_found = 0
-        self.global_constraints_searched = 0
-        self.global_constraints_found = 0
-        self.constraints_failed = 0  # pairs skipped on a device error status
-        self.last_error = CSM_OK
-        self.constraint_scores: List[float] = []
-        self.global_constraint_scores: List[float] = []
         self.rotational_scores: List[float] = []
         self.low_resolution_scores: List[float] = []
 
@@ -656,59 +688,37 @@ class ConstraintBuilder3D:
                                                                       np.float64)
         if float(np.linalg.norm(d)) > self.options.max_constraint_distance:
             return
-        sampler = self._samplers.setdefault(tuple(submap_id),
-                                            FixedRatioSampler(self.options.sampling_ratio))
-        if not sampler.Pulse():
+        if not self._sample(submap_id):
             return
-        self._enqueue(submap_id, submap, node_id, constant_data, False,
-                      global_node_pose, global_submap_pose)
+        self._submaps[tuple(submap_id)] = submap
+        self._enqueue(_Pending3D(tuple(submap_id), tuple(node_id), constant_data, False,
+                                 global_node_pose, global_submap_pose))
 
     def MaybeAddGlobalConstraint(self, submap_id, submap: Submap3D, node_id,
                                  constant_data: NodeData3D, global_node_rotation,
                                  global_submap_rotation):
-        self._enqueue(submap_id, submap, node_id, constant_data, True,
-                      ((0.0, 0.0, 0.0), tuple(global_node_rotation)),
-                      ((0.0, 0.0, 0.0), tuple(global_submap_rotation)))
-
-    def NotifyEndOfNode(self):
-        self._started_nodes += 1
-        if len(self._pending) >= self.options.flush_pairs:
-            self._flush()
-
-    def WhenDone(self, callback: Callable[[List[Constraint3D]], None]):
-        self._flush()
-        result = [c for c in self._constraints if c is not None]
-        if self.options.log_matches:  # RunWhenDoneCallback (:317-326)
-            self.log_sink(f"{len(self._constraints)} computations resulted in {len(result)} "
-                          "additional constraints.\nScore histogram:\n"
-                          + self.score_histogram.ToString(10)
-                          + "\nRotational score histogram:\n"
-                          + self.rotational_score_histogram.ToString(10)
-                          + "\nLow resolution score histogram:\n"
-                          + self.low_resolution_score_histogram.ToString(10))
-        self._constraints = []
-        self._metrics.queue_length.Set(len(self._constraints))
-        callback(result)
-
-    def GetNumFinishedNodes(self) -> int:
-        return self._finished_nodes
+        self._submaps[tuple(submap_id)] = submap
+        self._enqueue(_Pending3D(tuple(submap_id), tuple(node_id), constant_data, True,
+                                 ((0.0, 0.0, 0.0), tuple(global_node_rotation)),
+                                 ((0.0, 0.0, 0.0), tuple(global_submap_rotation))))
 
     def DeleteScanMatcher(self, submap_id):
-        """Also drops the submap's pending pairs (no constraint)."""
-        key = tuple(submap_id)
-        self._matchers.pop(key, _MatcherCache._close)  # matcher, then its grids
-        self._metrics.num_submap_scan_matchers.Set(len(self._matchers))
-        self._samplers.pop(key, None)
-        self._submaps.pop(key, None)
-        before = len(self._pending)
-        self._pending = [p for p in self._pending if p.submap_id != key]
-        if len(self._pending) != before:
-            print(f"ConstraintBuilder3D: DeleteScanMatcher dropped {before - len(self._pending)} "
-                  "pending pairs of a deleted submap", file=sys.stderr)
+        super().DeleteScanMatcher(submap_id)
+        self._submaps.pop(tuple(submap_id), None)
 
-    @property
-    def num_submap_scan_matchers(self) -> int:  # kNumSubmapScanMatchersMetric
-        return len(self._matchers)
+    def _log_when_done(self, computations, constraints):  # RunWhenDoneCallback (:317-326)
+        self.log_sink(f"{computations} computations resulted in {constraints} "
+                      "additional constraints.\nScore histogram:\n"
+                      + self.score_histogram.ToString(10)
+                      + "\nRotational score histogram:\n"
+                      + self.rotational_score_histogram.ToString(10)
+                      + "\nLow resolution score histogram:\n"
+                      + self.low_resolution_score_histogram.ToString(10))
+
+    def _note_scores(self, p, scores):
+        super()._note_scores(p, scores)
+        self.rotational_scores.append(scores[1])
+        self.low_resolution_scores.append(scores[2])
 
     # -- internals ----------------------------------------------------------
     def _make_matcher(self, p):
@@ -727,116 +737,65 @@ class ConstraintBuilder3D:
     def _bytes_of(entry):
         return sum(obj.device_bytes() for obj in entry)
 
-    def _enqueue(self, submap_id, submap, node_id, data, full, node_pose, submap_pose):
-        key = tuple(submap_id)
-        self._submaps[key] = submap
-        self._constraints.append(None)
-        self._metrics.queue_length.Set(len(self._constraints))  # (:101, :127)
-        p = _Pending3D(key, tuple(node_id), data, full, node_pose, submap_pose,
-                       len(self._constraints) - 1)
-        self._matchers.get(key, lambda: self._make_matcher(p), self._bytes_of)
-        self._matchers.pinned.discard(key)
-        self._matchers.trim()
-        self._metrics.num_submap_scan_matchers.Set(len(self._matchers))
-        self._pending.append(p)
-
-    def _flush(self):
-        pending, self._pending = self._pending, []
-        if pending:
-            for part, held in _budget_parts(pending, lambda p: p.submap_id, self._matchers,
-                                            self._make_matcher, self._bytes_of):
-                self._search(part, held)
-        self._finished_nodes = self._started_nodes
-
-    def _search(self, pending, held):
+    def _run_batch(self, pending, held):
         """One batch (and its Ceres refinement) over the matchers in ``held``."""
-        if pending:
-            matchers, slot_of, nodes, node_of = [], {}, [], {}
-            for p in pending:
-                if p.submap_id not in slot_of:
-                    slot_of[p.submap_id] = len(matchers)
-                    matchers.append(held[p.submap_id][2])
-                if id(p.data) not in node_of:  # a node's data uploads once
-                    node_of[id(p.data)] = len(nodes)
-                    nodes.append(p.data)
-            pairs = make_pairs_3d(
-                [slot_of[p.submap_id] for p in pending], [node_of[id(p.data)] for p in pending],
-                [self.options.global_localization_min_score if p.full else self.options.min_score
-                 for p in pending],
-                [p.full for p in pending],
-                node_q=[p.node_pose[1] for p in pending], node_t=[p.node_pose[0] for p in pending],
-                submap_q=[p.submap_pose[1] for p in pending],
-                submap_t=[p.submap_pose[0] for p in pending])
-            results = match_batch_3d(matchers, nodes, pairs, self.context)
-            refined = {}
-            ok = [i for i, r in enumerate(results) if int(r["status"]) == CSM_OK]
-            if self.options.refine_with_ceres and ok:
-                # ceres_scan_matcher_.Match(pose.translation(), pose, {high, low clouds and grids})
-                grids = []
-                for key in slot_of:
-                    grids.extend(held[key][:2])
-                items = []
-                for i in ok:
-                    p, r = pending[i], results[i]
-                    t = tuple(float(v) for v in r["t"])
-                    q = tuple(float(v) for v in r["q"])
-                    slot = slot_of[p.submap_id]
-                    items.append((2 * slot, 2 * slot + 1, node_of[id(p.data)], (t, q), t))
-                poses, _ = ceres_refine_batch_3d(grids, nodes, items,
-                                                 self.options.ceres_scan_matcher_options_3d,
-                                                 self.context)
-                refined = dict(zip(ok, poses))
-            failed = 0
-            for i, (p, r) in enumerate(zip(pending, results)):
-                if int(r["status"]) < 0:
-                    # Not searchable on the device (CSM_ERANGE, DESIGN.md §8):
-                    # no constraint, counted, never fatal (as the C++ header).
-                    self.constraints_failed += 1
-                    self.last_error = int(r["status"])
-                    failed += 1
-                    continue
-                m = self._metrics
-                if p.full:
-                    self.global_constraints_searched += 1
-                    m.global_searched.Increment()
-                else:
-                    self.constraints_searched += 1
-                    m.searched.Increment()
-                if int(r["status"]) != CSM_OK:
-                    continue
-                score = float(r["score"])
-                rot, low = float(r["rotational_score"]), float(r["low_resolution_score"])
-                if p.full:
-                    self.global_constraints_found += 1
-                    self.global_constraint_scores.append(score)
-                    m.global_found.Increment()
-                else:
-                    self.constraints_found += 1
-                    self.constraint_scores.append(score)
-                    m.found.Increment()
-                for h, v in zip(m.scores[p.full], (score, rot, low)):
-                    h.Observe(v)
-                self.score_histogram.Add(score)
-                self.rotational_score_histogram.Add(rot)
-                self.low_resolution_score_histogram.Add(low)
-                self.rotational_scores.append(rot)
-                self.low_resolution_scores.append(low)
-                pose = refined.get(i, (tuple(float(v) for v in r["t"]),
-                                       tuple(float(v) for v in r["q"])))
-                self._constraints[p.slot] = Constraint3D(
-                    submap_id=p.submap_id, node_id=p.node_id,
-                    relative_pose=(tuple(pose[0]), tuple(pose[1])),
-                    translation_weight=self.options.loop_closure_translation_weight,
-                    rotation_weight=self.options.loop_closure_rotation_weight,
-                    score=score, rotational_score=float(r["rotational_score"]),
-                    low_resolution_score=float(r["low_resolution_score"]))
-                if self.options.log_matches:
-                    self._log_match(p, self._constraints[p.slot].relative_pose, score)
-            if failed:
-                print(f"ConstraintBuilder3D: {failed} of {len(pending)} pairs skipped "
-                      f"({strerror(self.last_error)})", file=sys.stderr)
+        matchers, slot_of, nodes, node_of = [], {}, [], {}
+        for p in pending:
+            if p.submap_id not in slot_of:
+                slot_of[p.submap_id] = len(matchers)
+                matchers.append(held[p.submap_id][2])
+            if id(p.data) not in node_of:  # a node's data uploads once
+                node_of[id(p.data)] = len(nodes)
+                nodes.append(p.data)
+        pairs = make_pairs_3d(
+            [slot_of[p.submap_id] for p in pending], [node_of[id(p.data)] for p in pending],
+            [self.options.global_localization_min_score if p.full else self.options.min_score
+             for p in pending],
+            [p.full for p in pending],
+            node_q=[p.node_pose[1] for p in pending], node_t=[p.node_pose[0] for p in pending],
+            submap_q=[p.submap_pose[1] for p in pending],
+            submap_t=[p.submap_pose[0] for p in pending])
+        results = match_batch_3d(matchers, nodes, pairs, self.context)
+        refined = {}
+        ok = [i for i, r in enumerate(results) if int(r["status"]) == CSM_OK]
+        if self.options.refine_with_ceres and ok:
+            # ceres_scan_matcher_.Match(pose.translation(), pose, {high, low clouds and grids})
+            grids = []
+            for key in slot_of:
+                grids.extend(held[key][:2])
+            items = []
+            for i in ok:
+                p, r = pending[i], results[i]
+                t = tuple(float(v) for v in r["t"])
+                q = tuple(float(v) for v in r["q"])
+                slot = slot_of[p.submap_id]
+                items.append((2 * slot, 2 * slot + 1, node_of[id(p.data)], (t, q), t))
+            poses, _ = ceres_refine_batch_3d(grids, nodes, items,
+                                             self.options.ceres_scan_matcher_options_3d,
+                                             self.context)
+            refined = dict(zip(ok, poses))
+        outcomes = []
+        for i, (p, r) in enumerate(zip(pending, results)):
+            if int(r["status"]) != CSM_OK:
+                outcomes.append((int(r["status"]), None, None, None))
+                continue
+            scores = (float(r["score"]), float(r["rotational_score"]),
+                      float(r["low_resolution_score"]))
+            pose = refined.get(i, (tuple(float(v) for v in r["t"]),
+                                   tuple(float(v) for v in r["q"])))
+            constraint = Constraint3D(
+                submap_id=p.submap_id, node_id=p.node_id,
+                relative_pose=(tuple(pose[0]), tuple(pose[1])),
+                translation_weight=self.options.loop_closure_translation_weight,
+                rotation_weight=self.options.loop_closure_rotation_weight,
+                score=scores[0], rotational_score=scores[1], low_resolution_score=scores[2])
+            line = (self._match_line(p, constraint.relative_pose, scores[0])
+                    if self.options.log_matches else None)
+            outcomes.append((CSM_OK, scores, constraint, line))
+        return outcomes
 
-    def _log_match(self, p, constraint, score):
+    @staticmethod
+    def _match_line(p, constraint, score):
         """ComputeConstraint's log_matches line (:284-303): difference =
         global_node_pose^-1 * global_submap_pose * constraint, its angle
         transform::GetAngle."""
@@ -852,4 +811,4 @@ class ConstraintBuilder3D:
             angle = 2.0 * math.atan2(math.sqrt(q[1] ** 2 + q[2] ** 2 + q[3] ** 2), abs(q[0]))
             info += " differs by translation %.2f rotation %.3f" % (
                 math.sqrt(sum(c * c for c in d[0])), angle)
-        self.log_sink(info + " with score %.1f%%." % (100.0 * score))
+        return info + " with score %.1f%%." % (100.0 * score)

@@ -34,22 +34,20 @@
 // (constraint_gather.h). Rank 0's callback gets the whole
 // result, the other ranks' callbacks an empty one; the metric counters are
 // summed over the ranks and last_error reduced over them at every WhenDone.
+//
+// All of that but the 2D types, the device batch, the resident scan set and
+// the log texts lives in ConstraintBuilderBase (constraint_builder_base.h).
 #ifndef CARTOGRAPHER_AMD_CONSTRAINT_BUILDER_2D_H_
 #define CARTOGRAPHER_AMD_CONSTRAINT_BUILDER_2D_H_
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <functional>
 #include <map>
 #include <memory>
 #include <string>
-#include <utility>
 #include <vector>
 
-#include "constraint_builder_common.h"
-#include "constraint_gather.h"
-#include "metrics.h"
+#include "constraint_builder_base.h"
 #include "scan_matching.h"
 
 namespace cartographer_amd {
@@ -80,30 +78,30 @@ inline Rigid2d Inverse(const Rigid2d& a) {
   return Rigid2d{-(c * a.x + (-s) * a.y), -(s * a.x + c * a.y), -a.theta};
 }
 
-class ConstraintBuilder2D {
- public:
-  using Result = std::vector<Constraint>;
+struct ConstraintBuilder2DTraits {
+  using Constraint = cartographer_amd::Constraint;
+  using Record = ConstraintRecord;
+  using Matcher = FastCorrelativeScanMatcher2D;
+  struct Payload {
+    const Submap2DView* submap;
+    const PointCloud* cloud;
+    Rigid2d initial;  // the search start, map <- node
+  };
+  static constexpr const char* kName = "ConstraintBuilder2D";
+  static constexpr const char* kMetricPrefix = "mapping_constraints_constraint_builder_2d";
+  static constexpr const char* kScoreKinds[] = {nullptr};
+  static constexpr int kClaimNamespace = 0;
+};
 
+class ConstraintBuilder2D
+    : public ConstraintBuilderBase<ConstraintBuilder2D, ConstraintBuilder2DTraits> {
+ public:
   explicit ConstraintBuilder2D(const ConstraintBuilderOptions& options,
                                csm_context* context = nullptr)
-      : options_(options),
-        context_(context ? context : ThreadContext()),
-        matchers_(options.matcher_cache_bytes) {}
+      : ConstraintBuilderBase(options, context) {}
 
   ~ConstraintBuilder2D() {
     if (scans_) csm_scan_set_destroy(scans_);
-  }
-
-  // Shards the search over the ranks of `comm` (not owned; outlives the
-  // builder). Call before the first MaybeAdd*. kClaim needs
-  // csm_comm_claim_open on `comm`; builders that share a communicator in
-  // kClaim mode need distinct `claim_namespace`s (their counters' keys).
-  void set_communicator(csm_comm* comm, Sharding sharding = Sharding::kStatic,
-                        int chunk_submaps = 4, int claim_namespace = 0) {
-    comm_ = comm;
-    sharding_ = sharding;
-    chunk_submaps_ = chunk_submaps;
-    claim_key_ = static_cast<int64_t>(claim_namespace) << 40;
   }
 
   void MaybeAddConstraint(const SubmapId& submap_id, const Submap2DView* submap,
@@ -112,217 +110,52 @@ class ConstraintBuilder2D {
     if (std::hypot(initial_relative_pose.x, initial_relative_pose.y) >
         options_.max_constraint_distance)
       return;
-    auto it = samplers_.emplace(submap_id, FixedRatioSampler(options_.sampling_ratio)).first;
-    if (!it->second.Pulse()) return;
-    Enqueue(submap_id, submap, node_id, cloud, false,
-            Compose(submap->local_pose, initial_relative_pose));
+    if (!Sample(submap_id)) return;
+    Enqueue(submap_id, node_id, false,
+            Payload{submap, cloud, Compose(submap->local_pose, initial_relative_pose)});
   }
 
   void MaybeAddGlobalConstraint(const SubmapId& submap_id, const Submap2DView* submap,
                                 const NodeId& node_id, const PointCloud* cloud) {
-    Enqueue(submap_id, submap, node_id, cloud, true, Rigid2d::Identity());
+    Enqueue(submap_id, node_id, true, Payload{submap, cloud, Rigid2d::Identity()});
   }
-
-  void NotifyEndOfNode() {
-    ++num_started_nodes_;
-    if (static_cast<int>(pending_.size()) >= options_.flush_pairs) Flush();
-  }
-
-  void WhenDone(const std::function<void(const Result&)>& callback) {
-    Flush();
-    Result result;
-    if (comm_ && csm_comm_size(comm_) > 1) {
-      GatherToRoot(&result);
-    } else {
-      for (auto& c : constraints_)
-        if (c) result.push_back(*c);
-    }
-    if (options_.log_matches) {  // RunWhenDoneCallback (:289-293)
-      log_(std::to_string(constraints_.size()) + " computations resulted in " +
-           std::to_string(result.size()) + " additional constraints.");
-      log_("Score histogram:\n" + score_histogram_.ToString(10));
-    }
-    constraints_.clear();
-    Metrics().queue_length->Set(constraints_.size());
-    callback(result);
-  }
-
-  int GetNumFinishedNodes() const { return num_finished_nodes_; }
-
-  // Also drops the submap's pairs still pending (they yield no constraint):
-  // the reference's tasks would read the deleted matcher, and a pending pair
-  // must not make the builder rebuild it from a submap the caller is trimming.
-  void DeleteScanMatcher(const SubmapId& submap_id) {
-    matchers_.Erase(submap_id);
-    samplers_.erase(submap_id);
-    Metrics().num_submap_scan_matchers->Set(matchers_.size());
-    const size_t before = pending_.size();
-    pending_.erase(std::remove_if(pending_.begin(), pending_.end(),
-                                  [&](const Pending& p) {
-                                    return !(p.submap_id < submap_id) &&
-                                           !(submap_id < p.submap_id);
-                                  }),
-                   pending_.end());
-    if (pending_.size() != before)
-      std::fprintf(stderr,
-                   "ConstraintBuilder2D: DeleteScanMatcher dropped %zu pending pairs of a "
-                   "deleted submap\n",
-                   before - pending_.size());
-  }
-
-  // kNumSubmapScanMatchersMetric, and the cache's device bytes and churn.
-  int num_submap_scan_matchers() const { return static_cast<int>(matchers_.size()); }
-  int64_t matcher_cache_bytes() const { return matchers_.bytes(); }
-  int64_t matcher_builds() const { return matchers_.builds; }
-  int64_t matcher_evictions() const { return matchers_.evictions; }
-
-  // The metric families (constraint_builder_2d.cc:318-343): the same names
-  // and labels. Until called, the metrics are Null ones (:46-53). Shared by
-  // every ConstraintBuilder2D of the process, as the reference's statics.
-  static void RegisterMetrics(metrics::FamilyFactory* factory) {
-    MetricSet& m = Metrics();
-    auto* counts = factory->NewCounterFamily("mapping_constraints_constraint_builder_2d_constraints",
-                                             "Constraints computed");
-    m.searched = counts->Add({{"search_region", "local"}, {"matcher", "searched"}});
-    m.found = counts->Add({{"search_region", "local"}, {"matcher", "found"}});
-    m.global_searched = counts->Add({{"search_region", "global"}, {"matcher", "searched"}});
-    m.global_found = counts->Add({{"search_region", "global"}, {"matcher", "found"}});
-    m.queue_length = factory->NewGaugeFamily("mapping_constraints_constraint_builder_2d_queue_length",
-                                             "Queue length")->Add({});
-    auto* scores = factory->NewHistogramFamily("mapping_constraints_constraint_builder_2d_scores",
-                                               "Constraint scores built",
-                                               metrics::Histogram::FixedWidth(0.05, 20));
-    m.scores = scores->Add({{"search_region", "local"}});
-    m.global_scores = scores->Add({{"search_region", "global"}});
-    m.num_submap_scan_matchers =
-        factory->NewGaugeFamily("mapping_constraints_constraint_builder_2d_num_submap_scan_matchers",
-                                "Current number of constructed submap scan matchers")->Add({});
-  }
-
-  // score_histogram_ (:239): every accepted match's score, over the builder's life.
-  const ScoreHistogram& score_histogram() const { return score_histogram_; }
-  // Where the log_matches lines go (LOG(INFO) in the reference).
-  void set_log_sink(LogSink sink) { log_ = std::move(sink); }
-
-  // Counters of this builder (the metric counters above are process-wide).
-  int64_t constraints_searched = 0, constraints_found = 0;
-  int64_t global_constraints_searched = 0, global_constraints_found = 0;
-  // Pairs skipped because the device search returned an error (not counted
-  // as searched), and the last such status.
-  int64_t constraints_failed = 0;
-  // Sharding::kClaim: chunks this rank searched (not summed over ranks).
-  int64_t chunks_claimed = 0;
-  int last_error = CSM_OK;
 
  private:
-  struct Pending {
-    SubmapId submap_id;
-    const Submap2DView* submap;
-    NodeId node_id;
-    const PointCloud* cloud;
-    bool full;
-    Rigid2d initial;
-    size_t slot;
-  };
+  friend class ConstraintBuilderBase<ConstraintBuilder2D, ConstraintBuilder2DTraits>;
 
-  bool Claiming() const {
-    return comm_ && csm_comm_size(comm_) > 1 && sharding_ == Sharding::kClaim;
-  }
-  bool Owned(const SubmapId& id) const {
-    return !comm_ || csm_comm_size(comm_) <= 1 || sharding_ == Sharding::kClaim ||
-           ShardOwner(id.trajectory_id, id.submap_index, csm_comm_size(comm_)) ==
-               csm_comm_rank(comm_);
+  // DispatchScanMatcherConstruction (constraint_builder_2d.cc:165-186).
+  std::shared_ptr<FastCorrelativeScanMatcher2D> MakeMatcher(const Payload& p) {
+    return std::make_shared<FastCorrelativeScanMatcher2D>(
+        p.submap->grid, options_.fast_correlative_scan_matcher_options, context_);
   }
 
-  // DispatchScanMatcherConstruction (constraint_builder_2d.cc:165-186), through
-  // the budgeted cache (a dropped matcher is rebuilt from the submap's grid).
-  std::shared_ptr<FastCorrelativeScanMatcher2D> EnsureMatcher(const SubmapId& submap_id,
-                                                              const Submap2DView* submap) {
-    auto m = matchers_.Get(
-        submap_id,
-        [&] {
-          return std::make_shared<FastCorrelativeScanMatcher2D>(
-              submap->grid, options_.fast_correlative_scan_matcher_options, context_);
-        },
-        [](const FastCorrelativeScanMatcher2D& m) { return m.device_bytes(); });
-    Metrics().num_submap_scan_matchers->Set(matchers_.size());
-    return m;
+  static ConstraintRecord ToRecord(const Constraint& c) {
+    ConstraintRecord r{};
+    r.submap_trajectory = c.submap_id.trajectory_id;
+    r.submap_index = c.submap_id.submap_index;
+    r.node_trajectory = c.node_id.trajectory_id;
+    r.node_index = c.node_id.node_index;
+    r.x = c.relative_pose.x;
+    r.y = c.relative_pose.y;
+    r.theta = c.relative_pose.theta;
+    r.score = c.score;
+    r.tag = static_cast<int32_t>(c.tag);
+    return r;
+  }
+  static Constraint FromRecord(const ConstraintRecord& r) {
+    Constraint c;
+    c.submap_id = SubmapId{r.submap_trajectory, r.submap_index};
+    c.node_id = NodeId{r.node_trajectory, r.node_index};
+    c.relative_pose = Rigid2d{r.x, r.y, r.theta};
+    c.tag = static_cast<Constraint::Tag>(r.tag);
+    c.score = r.score;
+    return c;
   }
 
-  // Rank 0 receives every rank's accepted constraints in slot order; the
-  // metric deltas since the last WhenDone are summed over the ranks.
-  void GatherToRoot(Result* result) {
-    CheckSameSubmissions(comm_, static_cast<int64_t>(constraints_.size()));
-    last_error = ReduceLastError(comm_, last_error);
-    std::vector<ConstraintRecord> local;
-    for (size_t slot = 0; slot < constraints_.size(); ++slot) {
-      const Constraint* c = constraints_[slot].get();
-      if (!c) continue;
-      ConstraintRecord r{};
-      r.slot = static_cast<int64_t>(slot);
-      r.submap_trajectory = c->submap_id.trajectory_id;
-      r.submap_index = c->submap_id.submap_index;
-      r.node_trajectory = c->node_id.trajectory_id;
-      r.node_index = c->node_id.node_index;
-      r.x = c->relative_pose.x;
-      r.y = c->relative_pose.y;
-      r.theta = c->relative_pose.theta;
-      r.score = c->score;
-      r.tag = static_cast<int32_t>(c->tag);
-      local.push_back(r);
-    }
-    const std::vector<ConstraintRecord> all = GatherConstraintRecords(comm_, local);
-    int64_t d[5] = {constraints_searched - reduced_[0], constraints_found - reduced_[1],
-                    global_constraints_searched - reduced_[2],
-                    global_constraints_found - reduced_[3], constraints_failed - reduced_[4]};
-    CommCheck(csm_comm_allreduce_i64(comm_, d, 5, CSM_REDUCE_SUM), "csm_comm_allreduce_i64");
-    int64_t* counters[5] = {&constraints_searched, &constraints_found, &global_constraints_searched,
-                            &global_constraints_found, &constraints_failed};
-    for (int k = 0; k < 5; ++k) {
-      reduced_[k] += d[k];
-      *counters[k] = reduced_[k];
-    }
-    for (const ConstraintRecord& r : all) {
-      Constraint c;
-      c.submap_id = SubmapId{r.submap_trajectory, r.submap_index};
-      c.node_id = NodeId{r.node_trajectory, r.node_index};
-      c.relative_pose = Rigid2d{r.x, r.y, r.theta};
-      c.translation_weight = options_.loop_closure_translation_weight;
-      c.rotation_weight = options_.loop_closure_rotation_weight;
-      c.tag = static_cast<Constraint::Tag>(r.tag);
-      c.score = r.score;
-      result->push_back(c);
-    }
-  }
-
-  void Enqueue(const SubmapId& submap_id, const Submap2DView* submap, const NodeId& node_id,
-               const PointCloud* cloud, bool full, const Rigid2d& initial) {
-    constraints_.emplace_back();
-    Metrics().queue_length->Set(constraints_.size());  // (:98, :123)
-    if (!Owned(submap_id)) return;  // another rank searches it; the slot keeps submission order
-    if (!Claiming()) EnsureMatcher(submap_id, submap);  // claimed chunks build theirs
-    pending_.push_back(Pending{submap_id, submap, node_id, cloud, full, initial,
-                               constraints_.size() - 1});
-  }
-
-  void Flush() {
-    if (pending_.empty()) {
-      num_finished_nodes_ = num_started_nodes_;
-      return;
-    }
-    if (Claiming()) {
-      const std::vector<std::vector<size_t>> chunks = ClaimChunks(pending_, chunk_submaps_);
-      ForClaimedChunks(comm_, claim_key_++, chunks.size(), [&](size_t c) {
-        ++chunks_claimed;
-        Search(chunks[c]);
-      });
-    } else {
-      std::vector<size_t> all(pending_.size());
-      for (size_t i = 0; i < all.size(); ++i) all[i] = i;
-      Search(all);
-    }
-    pending_.clear();
-    num_finished_nodes_ = num_started_nodes_;
+  void LogWhenDone(size_t computations, size_t constraints) {  // RunWhenDoneCallback (:289-293)
+    log_(std::to_string(computations) + " computations resulted in " +
+         std::to_string(constraints) + " additional constraints.");
+    log_("Score histogram:\n" + score_histograms_[0].ToString(10));
   }
 
   // Device index of every pending_[which_pending[k]]'s cloud in scans_, which
@@ -395,44 +228,8 @@ class ConstraintBuilder2D {
     return index;
   }
 
-  // Cuts pending_[which] into sub-batches whose matchers fit the matcher
-  // cache's budget together (one batch when unbounded or when they fit),
-  // whole submaps per sub-batch, and searches each.
-  void Search(const std::vector<size_t>& which_pending) {
-    std::vector<size_t> order(which_pending);
-    if (matchers_.bounded())
-      std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        return pending_[a].submap_id < pending_[b].submap_id;
-      });
-    std::vector<size_t> part;
-    Held held;
-    int64_t held_bytes = 0;
-    for (size_t i : order) {
-      const Pending& p = pending_[i];
-      if (!held.count(p.submap_id)) {
-        auto m = EnsureMatcher(p.submap_id, p.submap);
-        const int64_t b = m->device_bytes();
-        if (!part.empty() && matchers_.bounded() && held_bytes + b > matchers_.budget()) {
-          SearchBatch(part, held);
-          part.clear();
-          held.clear();
-          held_bytes = 0;
-          matchers_.Trim();  // the searched part's matchers are no longer held
-        }
-        held.emplace(p.submap_id, std::move(m));
-        held_bytes += b;
-      }
-      part.push_back(i);
-    }
-    if (!part.empty()) SearchBatch(part, held);
-    held.clear();
-    matchers_.Trim();
-  }
-
-  using Held = std::map<SubmapId, std::shared_ptr<FastCorrelativeScanMatcher2D>>;
-
   // Searches (and refines) pending_[which] as one batch over `held`'s matchers.
-  void SearchBatch(const std::vector<size_t>& which_pending, const Held& held) {
+  std::vector<Outcome> RunBatch(const std::vector<size_t>& which_pending, const Held& held) {
     const std::vector<int32_t> scan_index = ResidentScans(which_pending);
     std::vector<csm_fast2d*> handles;
     std::map<SubmapId, int> slot_of;
@@ -477,28 +274,15 @@ class ConstraintBuilder2D {
                 "csm_ceres2d_refine_batch");
       for (size_t k = 0; k < which.size(); ++k) results[which[k]].pose = out[k];
     }
-    int64_t failed_this_flush = 0;
-    for (size_t i = 0; i < which_pending.size(); ++i) {
+    std::vector<Outcome> outcomes(results.size());
+    for (size_t i = 0; i < results.size(); ++i) {
       const Pending& p = pending_[which_pending[i]];
-      if (results[i].status < 0) {
-        // A pair the device path could not search (CSM_ERANGE: a cloud or
-        // window past the kernels' limits) yields no
-        // constraint; it is counted and reported, never fatal.
-        ++constraints_failed;
-        ++failed_this_flush;
-        last_error = results[i].status;
-        continue;
-      }
-      MetricSet& m = Metrics();
-      (p.full ? global_constraints_searched : constraints_searched) += 1;
-      (p.full ? m.global_searched : m.searched)->Increment();
-      if (results[i].status != CSM_OK) continue;
-      (p.full ? global_constraints_found : constraints_found) += 1;
-      (p.full ? m.global_found : m.found)->Increment();
-      (p.full ? m.global_scores : m.scores)->Observe(results[i].score);
-      score_histogram_.Add(results[i].score);
+      Outcome& o = outcomes[i];
+      o.status = results[i].status;
+      if (o.status != CSM_OK) continue;
+      o.scores[0] = results[i].score;
       const Rigid2d pose{results[i].pose.x, results[i].pose.y, results[i].pose.theta};
-      Constraint c;
+      Constraint& c = o.constraint;
       c.submap_id = p.submap_id;
       c.node_id = p.node_id;
       c.relative_pose = Compose(Inverse(p.submap->local_pose), pose);
@@ -506,18 +290,14 @@ class ConstraintBuilder2D {
       c.rotation_weight = options_.loop_closure_rotation_weight;
       c.tag = Constraint::INTER_SUBMAP;
       c.score = results[i].score;
-      constraints_[p.slot].reset(new Constraint(c));
-      if (options_.log_matches) LogMatch(p, pose, results[i].score);
+      if (options_.log_matches) o.match_line = MatchLine(p, pose, results[i].score);
     }
-    if (failed_this_flush)
-      std::fprintf(stderr, "ConstraintBuilder2D: %lld of %zu pairs skipped (%s)\n",
-                   static_cast<long long>(failed_this_flush), which_pending.size(),
-                   csm_strerror(last_error));
+    return outcomes;
   }
 
   // ComputeConstraint's log_matches line (:260-276); `pose` is the refined
   // pose_estimate (map <- node), p.initial the search start.
-  void LogMatch(const Pending& p, const Rigid2d& pose, float score) {
+  static std::string MatchLine(const Pending& p, const Rigid2d& pose, float score) {
     char buf[160];
     std::string info = "Node (" + std::to_string(p.node_id.trajectory_id) + ", " +
                        std::to_string(p.node_id.node_index) + ") with " +
@@ -536,33 +316,9 @@ class ConstraintBuilder2D {
       info += buf;
     }
     std::snprintf(buf, sizeof(buf), " with score %.1f%%.", 100. * score);
-    log_(info + buf);
+    return info + buf;
   }
 
-  // The process-wide metrics (the reference's static k*Metric pointers).
-  struct MetricSet {
-    metrics::Counter* searched = metrics::Counter::Null();
-    metrics::Counter* found = metrics::Counter::Null();
-    metrics::Counter* global_searched = metrics::Counter::Null();
-    metrics::Counter* global_found = metrics::Counter::Null();
-    metrics::Gauge* queue_length = metrics::Gauge::Null();
-    metrics::Histogram* scores = metrics::Histogram::Null();
-    metrics::Histogram* global_scores = metrics::Histogram::Null();
-    metrics::Gauge* num_submap_scan_matchers = metrics::Gauge::Null();
-  };
-  static MetricSet& Metrics() {
-    static MetricSet m;
-    return m;
-  }
-
-  ConstraintBuilderOptions options_;
-  csm_context* context_;
-  ScoreHistogram score_histogram_;
-  LogSink log_ = DefaultLogSink("ConstraintBuilder2D");
-  MatcherCache<FastCorrelativeScanMatcher2D> matchers_;
-  std::map<SubmapId, FixedRatioSampler> samplers_;
-  std::vector<std::unique_ptr<Constraint>> constraints_;
-  std::vector<Pending> pending_;
   struct CachedScan {
     const PointCloud* cloud = nullptr;
     size_t size = 0;
@@ -573,12 +329,6 @@ class ConstraintBuilder2D {
   csm_scan_set* scans_ = nullptr;         // node clouds resident across flushes
   std::map<NodeId, CachedScan> scan_cache_;
   int64_t cached_points_ = 0;
-  int num_started_nodes_ = 0, num_finished_nodes_ = 0;
-  csm_comm* comm_ = nullptr;
-  Sharding sharding_ = Sharding::kStatic;
-  int chunk_submaps_ = 4;
-  int64_t claim_key_ = 0;                  // kClaim: the next flush's counter
-  int64_t reduced_[5] = {0, 0, 0, 0, 0};  // counter totals over ranks at the last WhenDone
 };
 
 }  // namespace cartographer_amd

@@ -29,22 +29,21 @@
 // ranks. The score lists (constraint_scores, global_constraint_scores,
 // rotational_scores, low_resolution_scores) are appended at WhenDone from the
 // delivered result, in submission order, so on rank 0 they cover every rank.
+//
+// All of that but the 3D types, the device batch, the score lists and the log
+// texts lives in ConstraintBuilderBase (constraint_builder_base.h).
 #ifndef CARTOGRAPHER_AMD_CONSTRAINT_BUILDER_3D_H_
 #define CARTOGRAPHER_AMD_CONSTRAINT_BUILDER_3D_H_
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <functional>
 #include <map>
 #include <memory>
 #include <string>
-#include <utility>
 #include <vector>
 
-#include "constraint_builder_common.h"
-#include "constraint_gather.h"
-#include "metrics.h"
+#include "constraint_builder_base.h"
 #include "scan_matching_3d.h"
 
 namespace cartographer_amd {
@@ -67,27 +66,38 @@ struct Constraint3D {
   bool global = false;  // found by MaybeAddGlobalConstraint (the metrics split)
 };
 
-class ConstraintBuilder3D {
- public:
-  using Result = std::vector<Constraint3D>;
+// SubmapScanMatcher (constraint_builder_3d.h:117-123): device grids and the
+// matcher built from them.
+struct SubmapScanMatcher3D {
+  std::unique_ptr<HybridGrid3D> high, low;
+  std::unique_ptr<FastCorrelativeScanMatcher3D> matcher;
+  int64_t device_bytes() const {
+    return high->device_bytes() + low->device_bytes() + matcher->device_bytes();
+  }
+};
 
+struct ConstraintBuilder3DTraits {
+  using Constraint = Constraint3D;
+  using Record = ConstraintRecord3D;
+  using Matcher = SubmapScanMatcher3D;
+  struct Payload {
+    const Submap3DView* submap;
+    const TrajectoryNodeData3D* data;
+    Rigid3d node_pose, submap_pose;
+  };
+  static constexpr const char* kName = "ConstraintBuilder3D";
+  static constexpr const char* kMetricPrefix = "mapping_constraints_constraint_builder_3d";
+  static constexpr const char* kScoreKinds[] = {"score", "rotational_score",
+                                                "low_resolution_score"};
+  static constexpr int kClaimNamespace = 1;
+};
+
+class ConstraintBuilder3D
+    : public ConstraintBuilderBase<ConstraintBuilder3D, ConstraintBuilder3DTraits> {
+ public:
   explicit ConstraintBuilder3D(const ConstraintBuilderOptions& options,
                                csm_context* context = nullptr)
-      : options_(options),
-        context_(context ? context : ThreadContext()),
-        matchers_(options.matcher_cache_bytes) {}
-
-  // Shards the search over the ranks of `comm` (not owned; outlives the
-  // builder). Call before the first MaybeAdd*. kClaim needs
-  // csm_comm_claim_open on `comm`; builders that share a communicator in
-  // kClaim mode need distinct `claim_namespace`s.
-  void set_communicator(csm_comm* comm, Sharding sharding = Sharding::kStatic,
-                        int chunk_submaps = 4, int claim_namespace = 1) {
-    comm_ = comm;
-    sharding_ = sharding;
-    chunk_submaps_ = chunk_submaps;
-    claim_key_ = static_cast<int64_t>(claim_namespace) << 40;
-  }
+      : ConstraintBuilderBase(options, context) {}
 
   void MaybeAddConstraint(const SubmapId& submap_id, const Submap3DView* submap,
                           const NodeId& node_id, const TrajectoryNodeData3D* constant_data,
@@ -96,299 +106,98 @@ class ConstraintBuilder3D {
                  dy = global_node_pose.t[1] - global_submap_pose.t[1],
                  dz = global_node_pose.t[2] - global_submap_pose.t[2];
     if (std::sqrt(dx * dx + dy * dy + dz * dz) > options_.max_constraint_distance) return;
-    auto it = samplers_.emplace(submap_id, FixedRatioSampler(options_.sampling_ratio)).first;
-    if (!it->second.Pulse()) return;
-    Enqueue(submap_id, submap, node_id, constant_data, false, global_node_pose,
-            global_submap_pose);
+    if (!Sample(submap_id)) return;
+    Enqueue(submap_id, node_id, false,
+            Payload{submap, constant_data, global_node_pose, global_submap_pose});
   }
 
   void MaybeAddGlobalConstraint(const SubmapId& submap_id, const Submap3DView* submap,
                                 const NodeId& node_id, const TrajectoryNodeData3D* constant_data,
                                 const Quaterniond& global_node_rotation,
                                 const Quaterniond& global_submap_rotation) {
-    Enqueue(submap_id, submap, node_id, constant_data, true,
-            Rigid3d::Rotation(global_node_rotation), Rigid3d::Rotation(global_submap_rotation));
+    Enqueue(submap_id, node_id, true,
+            Payload{submap, constant_data, Rigid3d::Rotation(global_node_rotation),
+                    Rigid3d::Rotation(global_submap_rotation)});
   }
 
-  void NotifyEndOfNode() {
-    ++num_started_nodes_;
-    if (static_cast<int>(pending_.size()) >= options_.flush_pairs) Flush();
-  }
-
+  // The base's WhenDone, and the score lists (constraint_builder_3d.cc:46-59)
+  // appended from the delivered result in submission order.
   void WhenDone(const std::function<void(const Result&)>& callback) {
-    Flush();
-    Result result;
-    if (comm_ && csm_comm_size(comm_) > 1) {
-      GatherToRoot(&result);
-    } else {
-      for (auto& c : constraints_)
-        if (c) result.push_back(*c);
-    }
-    if (options_.log_matches) {  // RunWhenDoneCallback (:317-326)
-      log_(std::to_string(constraints_.size()) + " computations resulted in " +
-           std::to_string(result.size()) + " additional constraints.\nScore histogram:\n" +
-           score_histogram_.ToString(10) + "\nRotational score histogram:\n" +
-           rotational_score_histogram_.ToString(10) + "\nLow resolution score histogram:\n" +
-           low_resolution_score_histogram_.ToString(10));
-    }
-    constraints_.clear();
-    Metrics().queue_length->Set(constraints_.size());
-    // The score lists (constraint_builder_3d.cc:46-59), submission order.
-    for (const Constraint3D& c : result) {
-      (c.global ? global_constraint_scores : constraint_scores).push_back(c.score);
-      rotational_scores.push_back(c.rotational_score);
-      low_resolution_scores.push_back(c.low_resolution_score);
-    }
-    callback(result);
+    ConstraintBuilderBase::WhenDone([&](const Result& result) {
+      for (const Constraint3D& c : result) {
+        (c.global ? global_constraint_scores : constraint_scores).push_back(c.score);
+        rotational_scores.push_back(c.rotational_score);
+        low_resolution_scores.push_back(c.low_resolution_score);
+      }
+      callback(result);
+    });
   }
 
-  int GetNumFinishedNodes() const { return num_finished_nodes_; }
+  // rotational_score_histogram_, low_resolution_score_histogram_ (:257-259).
+  const ScoreHistogram& rotational_score_histogram() const { return score_histograms_[1]; }
+  const ScoreHistogram& low_resolution_score_histogram() const { return score_histograms_[2]; }
 
-  // Also drops the submap's pairs still pending (no constraint; see
-  // ConstraintBuilder2D::DeleteScanMatcher).
-  void DeleteScanMatcher(const SubmapId& submap_id) {
-    matchers_.Erase(submap_id);
-    samplers_.erase(submap_id);
-    Metrics().num_submap_scan_matchers->Set(matchers_.size());
-    const size_t before = pending_.size();
-    pending_.erase(std::remove_if(pending_.begin(), pending_.end(),
-                                  [&](const Pending& p) {
-                                    return !(p.submap_id < submap_id) &&
-                                           !(submap_id < p.submap_id);
-                                  }),
-                   pending_.end());
-    if (pending_.size() != before)
-      std::fprintf(stderr,
-                   "ConstraintBuilder3D: DeleteScanMatcher dropped %zu pending pairs of a "
-                   "deleted submap\n",
-                   before - pending_.size());
-  }
-
-  // The metric families (constraint_builder_3d.cc:351-386), same names and
-  // labels; Null metrics until called (:46-59); process-wide like the
-  // reference's statics.
-  static void RegisterMetrics(metrics::FamilyFactory* factory) {
-    MetricSet& m = Metrics();
-    auto* counts = factory->NewCounterFamily("mapping_constraints_constraint_builder_3d_constraints",
-                                             "Constraints computed");
-    m.searched = counts->Add({{"search_region", "local"}, {"matcher", "searched"}});
-    m.found = counts->Add({{"search_region", "local"}, {"matcher", "found"}});
-    m.global_searched = counts->Add({{"search_region", "global"}, {"matcher", "searched"}});
-    m.global_found = counts->Add({{"search_region", "global"}, {"matcher", "found"}});
-    m.queue_length = factory->NewGaugeFamily("mapping_constraints_constraint_builder_3d_queue_length",
-                                             "Queue length")->Add({});
-    auto* scores = factory->NewHistogramFamily("mapping_constraints_constraint_builder_3d_scores",
-                                               "Constraint scores built",
-                                               metrics::Histogram::FixedWidth(0.05, 20));
-    for (int g = 0; g < 2; ++g) {
-      const std::string region = g ? "global" : "local";
-      m.scores[g][0] = scores->Add({{"search_region", region}, {"kind", "score"}});
-      m.scores[g][1] = scores->Add({{"search_region", region}, {"kind", "rotational_score"}});
-      m.scores[g][2] = scores->Add({{"search_region", region}, {"kind", "low_resolution_score"}});
-    }
-    m.num_submap_scan_matchers =
-        factory->NewGaugeFamily("mapping_constraints_constraint_builder_3d_num_submap_scan_matchers",
-                                "Current number of constructed submap scan matchers")->Add({});
-  }
-
-  // score_histogram_, rotational_score_histogram_, low_resolution_score_histogram_ (:257-259).
-  const ScoreHistogram& score_histogram() const { return score_histogram_; }
-  const ScoreHistogram& rotational_score_histogram() const { return rotational_score_histogram_; }
-  const ScoreHistogram& low_resolution_score_histogram() const {
-    return low_resolution_score_histogram_;
-  }
-  void set_log_sink(LogSink sink) { log_ = std::move(sink); }
-
-  // Counters of this builder (the metric counters above are process-wide).
-  int64_t constraints_searched = 0, constraints_found = 0;
-  int64_t global_constraints_searched = 0, global_constraints_found = 0;
-  // Pairs skipped because the device search returned an error (not counted
-  // as searched), and the last such status.
-  int64_t constraints_failed = 0;
-  // Sharding::kClaim: chunks this rank searched (not summed over ranks).
-  int64_t chunks_claimed = 0;
-  int last_error = CSM_OK;
   std::vector<float> constraint_scores, global_constraint_scores;
   std::vector<float> rotational_scores, low_resolution_scores;
-  int num_submap_scan_matchers() const { return static_cast<int>(matchers_.size()); }
-  int64_t matcher_cache_bytes() const { return matchers_.bytes(); }
-  int64_t matcher_builds() const { return matchers_.builds; }
-  int64_t matcher_evictions() const { return matchers_.evictions; }
 
  private:
-  // SubmapScanMatcher (constraint_builder_3d.h:117-123): device grids and the
-  // matcher built from them.
-  struct SubmapScanMatcher {
-    std::unique_ptr<HybridGrid3D> high, low;
-    std::unique_ptr<FastCorrelativeScanMatcher3D> matcher;
-    int64_t device_bytes() const {
-      return high->device_bytes() + low->device_bytes() + matcher->device_bytes();
-    }
-  };
-
-  struct Pending {
-    SubmapId submap_id;
-    const Submap3DView* submap;
-    NodeId node_id;
-    const TrajectoryNodeData3D* data;
-    bool full;
-    Rigid3d node_pose, submap_pose;
-    size_t slot;
-  };
-
-  bool Claiming() const {
-    return comm_ && csm_comm_size(comm_) > 1 && sharding_ == Sharding::kClaim;
-  }
-  bool Owned(const SubmapId& id) const {
-    return !comm_ || csm_comm_size(comm_) <= 1 || sharding_ == Sharding::kClaim ||
-           ShardOwner(id.trajectory_id, id.submap_index, csm_comm_size(comm_)) ==
-               csm_comm_rank(comm_);
-  }
-
-  // Rank 0 receives every rank's accepted constraints in slot order; the
-  // metric counter deltas since the last WhenDone are summed over the ranks.
-  void GatherToRoot(Result* result) {
-    CheckSameSubmissions(comm_, static_cast<int64_t>(constraints_.size()));
-    last_error = ReduceLastError(comm_, last_error);
-    std::vector<ConstraintRecord3D> local;
-    for (size_t slot = 0; slot < constraints_.size(); ++slot) {
-      const Constraint3D* c = constraints_[slot].get();
-      if (!c) continue;
-      ConstraintRecord3D r{};
-      r.slot = static_cast<int64_t>(slot);
-      r.submap_trajectory = c->submap_id.trajectory_id;
-      r.submap_index = c->submap_id.submap_index;
-      r.node_trajectory = c->node_id.trajectory_id;
-      r.node_index = c->node_id.node_index;
-      for (int a = 0; a < 3; ++a) r.t[a] = c->relative_pose.t[a];
-      const Quaterniond& q = c->relative_pose.rotation;
-      r.q[0] = q.w;
-      r.q[1] = q.x;
-      r.q[2] = q.y;
-      r.q[3] = q.z;
-      r.score = c->score;
-      r.rotational_score = c->rotational_score;
-      r.low_resolution_score = c->low_resolution_score;
-      r.tag = static_cast<int32_t>(c->tag);
-      r.global = c->global ? 1 : 0;
-      local.push_back(r);
-    }
-    const std::vector<ConstraintRecord3D> all = GatherRecords(comm_, local);
-    int64_t d[5] = {constraints_searched - reduced_[0], constraints_found - reduced_[1],
-                    global_constraints_searched - reduced_[2],
-                    global_constraints_found - reduced_[3], constraints_failed - reduced_[4]};
-    CommCheck(csm_comm_allreduce_i64(comm_, d, 5, CSM_REDUCE_SUM), "csm_comm_allreduce_i64");
-    int64_t* counters[5] = {&constraints_searched, &constraints_found, &global_constraints_searched,
-                            &global_constraints_found, &constraints_failed};
-    for (int k = 0; k < 5; ++k) {
-      reduced_[k] += d[k];
-      *counters[k] = reduced_[k];
-    }
-    for (const ConstraintRecord3D& r : all) {
-      Constraint3D c;
-      c.submap_id = SubmapId{r.submap_trajectory, r.submap_index};
-      c.node_id = NodeId{r.node_trajectory, r.node_index};
-      for (int a = 0; a < 3; ++a) c.relative_pose.t[a] = r.t[a];
-      c.relative_pose.rotation = Quaterniond{r.q[0], r.q[1], r.q[2], r.q[3]};
-      c.translation_weight = options_.loop_closure_translation_weight;
-      c.rotation_weight = options_.loop_closure_rotation_weight;
-      c.tag = static_cast<Constraint3D::Tag>(r.tag);
-      c.score = r.score;
-      c.rotational_score = r.rotational_score;
-      c.low_resolution_score = r.low_resolution_score;
-      c.global = r.global != 0;
-      result->push_back(c);
-    }
-  }
-
-  void Enqueue(const SubmapId& submap_id, const Submap3DView* submap, const NodeId& node_id,
-               const TrajectoryNodeData3D* data, bool full, const Rigid3d& node_pose,
-               const Rigid3d& submap_pose) {
-    constraints_.emplace_back();
-    Metrics().queue_length->Set(constraints_.size());  // (:101, :127)
-    if (!Owned(submap_id)) return;  // another rank searches it; the slot keeps submission order
-    if (!Claiming()) EnsureMatcher(submap_id, submap);  // claimed chunks build theirs
-    pending_.push_back(Pending{submap_id, submap, node_id, data, full, node_pose, submap_pose,
-                               constraints_.size() - 1});
-  }
+  friend class ConstraintBuilderBase<ConstraintBuilder3D, ConstraintBuilder3DTraits>;
+  using SubmapScanMatcher = SubmapScanMatcher3D;
 
   // DispatchScanMatcherConstruction (constraint_builder_3d.cc:170-198).
-  // Through the budgeted cache (MatcherCache): a dropped matcher is rebuilt
-  // from the submap's grids and histogram on its next use.
-  std::shared_ptr<SubmapScanMatcher> EnsureMatcher(const SubmapId& submap_id,
-                                                   const Submap3DView* submap) {
-    auto held = matchers_.Get(
-        submap_id,
-        [&] {
-          auto m = std::make_shared<SubmapScanMatcher>();
-          m->high.reset(new HybridGrid3D(submap->high_resolution_hybrid_grid, context_));
-          m->low.reset(new HybridGrid3D(submap->low_resolution_hybrid_grid, context_));
-          m->matcher.reset(new FastCorrelativeScanMatcher3D(
-              *m->high, m->low.get(), &submap->rotational_scan_matcher_histogram,
-              options_.fast_correlative_scan_matcher_options_3d, context_));
-          return m;
-        },
-        [](const SubmapScanMatcher& m) { return m.device_bytes(); });
-    Metrics().num_submap_scan_matchers->Set(matchers_.size());
-    return held;
+  std::shared_ptr<SubmapScanMatcher> MakeMatcher(const Payload& p) {
+    auto m = std::make_shared<SubmapScanMatcher>();
+    m->high.reset(new HybridGrid3D(p.submap->high_resolution_hybrid_grid, context_));
+    m->low.reset(new HybridGrid3D(p.submap->low_resolution_hybrid_grid, context_));
+    m->matcher.reset(new FastCorrelativeScanMatcher3D(
+        *m->high, m->low.get(), &p.submap->rotational_scan_matcher_histogram,
+        options_.fast_correlative_scan_matcher_options_3d, context_));
+    return m;
   }
 
-  void Flush() {
-    if (pending_.empty()) {
-      num_finished_nodes_ = num_started_nodes_;
-      return;
-    }
-    if (Claiming()) {
-      const std::vector<std::vector<size_t>> chunks = ClaimChunks(pending_, chunk_submaps_);
-      ForClaimedChunks(comm_, claim_key_++, chunks.size(), [&](size_t c) {
-        ++chunks_claimed;
-        Search(chunks[c]);
-      });
-    } else {
-      std::vector<size_t> all(pending_.size());
-      for (size_t i = 0; i < all.size(); ++i) all[i] = i;
-      Search(all);
-    }
-    pending_.clear();
-    num_finished_nodes_ = num_started_nodes_;
+  static ConstraintRecord3D ToRecord(const Constraint3D& c) {
+    ConstraintRecord3D r{};
+    r.submap_trajectory = c.submap_id.trajectory_id;
+    r.submap_index = c.submap_id.submap_index;
+    r.node_trajectory = c.node_id.trajectory_id;
+    r.node_index = c.node_id.node_index;
+    for (int a = 0; a < 3; ++a) r.t[a] = c.relative_pose.t[a];
+    const Quaterniond& q = c.relative_pose.rotation;
+    r.q[0] = q.w;
+    r.q[1] = q.x;
+    r.q[2] = q.y;
+    r.q[3] = q.z;
+    r.score = c.score;
+    r.rotational_score = c.rotational_score;
+    r.low_resolution_score = c.low_resolution_score;
+    r.tag = static_cast<int32_t>(c.tag);
+    r.global = c.global ? 1 : 0;
+    return r;
+  }
+  static Constraint3D FromRecord(const ConstraintRecord3D& r) {
+    Constraint3D c;
+    c.submap_id = SubmapId{r.submap_trajectory, r.submap_index};
+    c.node_id = NodeId{r.node_trajectory, r.node_index};
+    for (int a = 0; a < 3; ++a) c.relative_pose.t[a] = r.t[a];
+    c.relative_pose.rotation = Quaterniond{r.q[0], r.q[1], r.q[2], r.q[3]};
+    c.tag = static_cast<Constraint3D::Tag>(r.tag);
+    c.score = r.score;
+    c.rotational_score = r.rotational_score;
+    c.low_resolution_score = r.low_resolution_score;
+    c.global = r.global != 0;
+    return c;
   }
 
-  // Sub-batches whose matchers fit the cache budget together (as
-  // ConstraintBuilder2D::Search), each searched and refined as one batch.
-  void Search(const std::vector<size_t>& which_pending) {
-    std::vector<size_t> order(which_pending);
-    if (matchers_.bounded())
-      std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        return pending_[a].submap_id < pending_[b].submap_id;
-      });
-    std::vector<size_t> part;
-    std::map<SubmapId, std::shared_ptr<SubmapScanMatcher>> held;
-    int64_t held_bytes = 0;
-    for (size_t i : order) {
-      const Pending& p = pending_[i];
-      if (!held.count(p.submap_id)) {
-        auto m = EnsureMatcher(p.submap_id, p.submap);
-        const int64_t b = m->device_bytes();
-        if (!part.empty() && matchers_.bounded() && held_bytes + b > matchers_.budget()) {
-          SearchBatch(part, held);
-          part.clear();
-          held.clear();
-          held_bytes = 0;
-          matchers_.Trim();  // the searched part's matchers are no longer held
-        }
-        held.emplace(p.submap_id, std::move(m));
-        held_bytes += b;
-      }
-      part.push_back(i);
-    }
-    if (!part.empty()) SearchBatch(part, held);
-    held.clear();
-    matchers_.Trim();
+  void LogWhenDone(size_t computations, size_t constraints) {  // RunWhenDoneCallback (:317-326)
+    log_(std::to_string(computations) + " computations resulted in " +
+         std::to_string(constraints) + " additional constraints.\nScore histogram:\n" +
+         score_histograms_[0].ToString(10) + "\nRotational score histogram:\n" +
+         score_histograms_[1].ToString(10) + "\nLow resolution score histogram:\n" +
+         score_histograms_[2].ToString(10));
   }
 
   // Searches (and refines) pending_[which] as one batch over `held`'s matchers.
-  void SearchBatch(const std::vector<size_t>& which_pending,
-                   const std::map<SubmapId, std::shared_ptr<SubmapScanMatcher>>& held) {
+  std::vector<Outcome> RunBatch(const std::vector<size_t>& which_pending, const Held& held) {
     std::vector<csm_fast3d*> handles;
     std::vector<const SubmapScanMatcher*> keep;
     std::map<SubmapId, int> slot_of;
@@ -453,31 +262,16 @@ class ConstraintBuilder3D {
                 "csm_ceres3d_refine_batch");
       for (size_t k = 0; k < which.size(); ++k) results[which[k]].pose = out[k];
     }
-    int64_t failed_this_flush = 0;
-    for (size_t i = 0; i < which_pending.size(); ++i) {
+    std::vector<Outcome> outcomes(results.size());
+    for (size_t i = 0; i < results.size(); ++i) {
       const Pending& p = pending_[which_pending[i]];
-      if (results[i].status < 0) {
-        // A pair the device path could not search (CSM_ERANGE: a cloud or
-        // window past the kernels' limits) yields no
-        // constraint; it is counted and reported, never fatal.
-        ++constraints_failed;
-        ++failed_this_flush;
-        last_error = results[i].status;
-        continue;
-      }
-      MetricSet& m = Metrics();
-      (p.full ? global_constraints_searched : constraints_searched) += 1;
-      (p.full ? m.global_searched : m.searched)->Increment();
-      if (results[i].status != CSM_OK) continue;
-      (p.full ? global_constraints_found : constraints_found) += 1;
-      (p.full ? m.global_found : m.found)->Increment();
-      m.scores[p.full][0]->Observe(results[i].score);
-      m.scores[p.full][1]->Observe(results[i].rotational_score);
-      m.scores[p.full][2]->Observe(results[i].low_resolution_score);
-      score_histogram_.Add(results[i].score);
-      rotational_score_histogram_.Add(results[i].rotational_score);
-      low_resolution_score_histogram_.Add(results[i].low_resolution_score);
-      Constraint3D c;
+      Outcome& o = outcomes[i];
+      o.status = results[i].status;
+      if (o.status != CSM_OK) continue;
+      o.scores[0] = results[i].score;
+      o.scores[1] = results[i].rotational_score;
+      o.scores[2] = results[i].low_resolution_score;
+      Constraint3D& c = o.constraint;
       c.submap_id = p.submap_id;
       c.node_id = p.node_id;
       c.relative_pose = Rigid3d::FromC(results[i].pose);
@@ -488,19 +282,15 @@ class ConstraintBuilder3D {
       c.rotational_score = results[i].rotational_score;
       c.low_resolution_score = results[i].low_resolution_score;
       c.global = p.full;
-      constraints_[p.slot].reset(new Constraint3D(c));
-      if (options_.log_matches) LogMatch(p, c.relative_pose, results[i].score);
+      if (options_.log_matches) o.match_line = MatchLine(p, c.relative_pose, results[i].score);
     }
-    if (failed_this_flush)
-      std::fprintf(stderr, "ConstraintBuilder3D: %lld of %zu pairs skipped (%s)\n",
-                   static_cast<long long>(failed_this_flush), which_pending.size(),
-                   csm_strerror(last_error));
+    return outcomes;
   }
 
   // ComputeConstraint's log_matches line (:284-303). difference =
   // global_node_pose^-1 * global_submap_pose * constraint_transform; its
   // angle is transform::GetAngle (2 atan2(|vec|, |w|)).
-  void LogMatch(const Pending& p, const Rigid3d& constraint, float score) {
+  static std::string MatchLine(const Pending& p, const Rigid3d& constraint, float score) {
     char buf[160];
     std::string info = "Node (" + std::to_string(p.node_id.trajectory_id) + ", " +
                        std::to_string(p.node_id.node_index) + ") with " +
@@ -519,7 +309,7 @@ class ConstraintBuilder3D {
       info += buf;
     }
     std::snprintf(buf, sizeof(buf), " with score %.1f%%.", 100. * score);
-    log_(info + buf);
+    return info + buf;
   }
   // transform::Rigid3d operator* and inverse (rigid_transform.h:163-200) in double.
   static Quaterniond QMul(const Quaterniond& a, const Quaterniond& b) {
@@ -552,38 +342,6 @@ class ConstraintBuilder3D {
     for (int k = 0; k < 3; ++k) r.t[k] = -r.t[k];
     return r;
   }
-
-  struct MetricSet {  // the reference's static k*Metric pointers (:46-59)
-    metrics::Counter* searched = metrics::Counter::Null();
-    metrics::Counter* found = metrics::Counter::Null();
-    metrics::Counter* global_searched = metrics::Counter::Null();
-    metrics::Counter* global_found = metrics::Counter::Null();
-    metrics::Gauge* queue_length = metrics::Gauge::Null();
-    // [local, global][score, rotational_score, low_resolution_score]
-    metrics::Histogram* scores[2][3] = {
-        {metrics::Histogram::Null(), metrics::Histogram::Null(), metrics::Histogram::Null()},
-        {metrics::Histogram::Null(), metrics::Histogram::Null(), metrics::Histogram::Null()}};
-    metrics::Gauge* num_submap_scan_matchers = metrics::Gauge::Null();
-  };
-  static MetricSet& Metrics() {
-    static MetricSet m;
-    return m;
-  }
-
-  ConstraintBuilderOptions options_;
-  csm_context* context_;
-  ScoreHistogram score_histogram_, rotational_score_histogram_, low_resolution_score_histogram_;
-  LogSink log_ = DefaultLogSink("ConstraintBuilder3D");
-  MatcherCache<SubmapScanMatcher> matchers_;
-  std::map<SubmapId, FixedRatioSampler> samplers_;
-  std::vector<std::unique_ptr<Constraint3D>> constraints_;
-  std::vector<Pending> pending_;
-  int num_started_nodes_ = 0, num_finished_nodes_ = 0;
-  csm_comm* comm_ = nullptr;
-  Sharding sharding_ = Sharding::kStatic;
-  int chunk_submaps_ = 4;
-  int64_t claim_key_ = 0;                  // kClaim: the next flush's counter
-  int64_t reduced_[5] = {0, 0, 0, 0, 0};  // counter totals over ranks at the last WhenDone
 };
 
 }  // namespace cartographer_amd
