@@ -72,6 +72,37 @@ __device__ __forceinline__ uint64_t LoadBest(const uint64_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Cell coordinates (x, y) of a pair's scan point i under rotation q, as the
+// doubles before any range test (inv_res = 1.0 / sm.resolution). The one copy
+// of this arithmetic in device code: its users must stay bit-equal. Each
+// keeps its own rule for a coordinate past kIndexLimit: the search zeroes
+// both indices and flags the pair, DiscretizeRotation writes 0x80008000,
+// fast2d_rotation_bounds zeroes each axis on its own.
+__device__ __forceinline__ double2 ScanCellCoords(const PairDesc& pd, const SubmapDesc& sm, float2 q,
+                                                  double inv_res, const float* __restrict__ points,
+                                                  int i) {
+  const float* p = points + 3 * (pd.point_offset + i);
+  float x, y;
+  RotateZDev(pd.pre_w, pd.pre_s, p[0], p[1], &x, &y);
+  RotateZDev(q.x, q.y, x, y, &x, &y);
+  const float px = __fadd_rn(pd.tx, x);
+  const float py = __fadd_rn(pd.ty, y);
+  return make_double2(CellCoordFast(sm.max_y, py, sm.resolution, inv_res),
+                      CellCoordFast(sm.max_x, px, sm.resolution, inv_res));
+}
+
+// The ShrinkToFit clamp (correlative_scan_matcher_2d.cc:73-91): the linear
+// window (b0, b1, b2, b3) = (min_x, max_x, min_y, max_y) of offsets that keep
+// some scan cell, of [min_x, max_x] x [min_y, max_y], inside the nx by ny
+// grid, clamped to +-num_linear.
+__device__ __forceinline__ int4 ShrinkToFitBounds(int min_x, int max_x, int min_y, int max_y, int nx,
+                                                  int ny, int num_linear) {
+  const int lo_x = min(0, -max_x), hi_x = max(0, nx - 1 - min_x);
+  const int lo_y = min(0, -max_y), hi_y = max(0, ny - 1 - min_y);
+  return make_int4(max(-num_linear, lo_x), min(num_linear, hi_x), max(-num_linear, lo_y),
+                   min(num_linear, hi_y));
+}
+
 // ---------------------------------------------------------------- K1 -------
 
 // Level 0: quantized probability of every cell (ComputeCellValue of
@@ -298,13 +329,6 @@ __global__ void pyramid_hex(const uint8_t* __restrict__ mlev, int mw, int mh, in
 // sums meet through LDS atomics (C3 launch 571.4 -> 569.0 ms, profiles/r5ba).
 constexpr int kMaxRotChunk = kV4MaxRotChunk;
 constexpr int kLists = kMaxClusterShift + 1;
-#ifndef CSM_PART_SWIZZLE
-// The children sums' LDS layout (V4Shared::PartIndex): 1 rotates a node's
-// row so that the scoring lanes' atomics, consecutive nodes at one child
-// index, fall on 32 different banks; 0 is the plain [node][child] array,
-// whose rows of 16 dwords put them on 2 (EXPERIMENTS.md).
-#define CSM_PART_SWIZZLE 1
-#endif
 
 // kKids: children sums per node, 4 (quad batches only, v4) or 16 (v5: hex
 // batches, and the virtual roots' quad batches in the first 4 columns).
@@ -317,13 +341,14 @@ struct V4Shared {
   uint2 stack[kStackLds];  // w0: xo | yo << 16; w1: sum | rot << 22 | level << 27
   // Children sums, accumulated by the 4 waves (LDS atomics): child `kid` of
   // batch node `node` at PartIndex(node, kid). A row is rotated by node /
-  // (32 / kKids): 32 consecutive nodes' dwords of one child index then lie on
-  // 32 different banks (plain rows: kKids dwords apart, 32 / kKids banks),
-  // and a row still holds its kKids children, so the combine pass's lanes
-  // (node, child) read whole rows.
+  // (32 / kKids): the scoring lanes' atomics, consecutive nodes at one child
+  // index, then fall on 32 different banks (plain [node][child] rows: kKids
+  // dwords apart, 32 / kKids banks; EXPERIMENTS.md), and a row still holds
+  // its kKids children, so the combine pass's lanes (node, child) read whole
+  // rows.
   int part[kBatchNodes * kKids];
   static __device__ __forceinline__ int PartIndex(int node, int kid) {
-    return node * kKids + (CSM_PART_SWIZZLE ? (kid + node / (32 / kKids)) & (kKids - 1) : kid);
+    return node * kKids + ((kid + node / (32 / kKids)) & (kKids - 1));
   }
   int batch_hex;                 // the batch's nodes score 16 grandchildren (v5)
   int head;                      // FIFO: LDS ring position of the oldest entry
@@ -661,27 +686,17 @@ __device__ __forceinline__ uint32_t ClusterMask(int sl) {
   return h | (h << 16);
 }
 
-// kHex = false: v4 (every node scores its 4 children from the quad planes).
-// kHex = true: v5 (nodes of the levels in SubmapDesc::hex_mask score their
-// 16 grandchildren from hex planes, the others their 4 children from quad
-// planes; a batch holds one kind).
-//
-// kFifo = false: the stack is LIFO with the deepest level on top (depth-first,
-// early leaves). kFifo = true: a FIFO ring (level by level: batches fill up
-// with the whole frontier of a level; leaves come last).
 #ifndef CSM_BEST_REFRESH
 #define CSM_BEST_REFRESH 1  // batches between reads of the pair's global best (power of 2; profiles/r3ap)
 #endif
 #ifndef CSM_LIFO_LEVEL
 #define CSM_LIFO_LEVEL 2  // FIFO order: levels pushed depth-first (0: none; profiles/r3an)
 #endif
-#ifndef CSM_XFAST
-// Children and roots enter the stack x-fastest, so consecutive lanes of the
-// next batch score nodes adjacent in x: adjacent entries of a polyphase plane
-// (DESIGN.md §5).
-#define CSM_XFAST 1
+#ifndef CSM_V4_WAVES
+// Waves per SIMD the register budget targets: 6 workgroups per CU (v5 with
+// its 256-entry LDS ring fits 6 in LDS too; measured best, DESIGN.md §5).
+#define CSM_V4_WAVES 6
 #endif
-#ifndef CSM_ORIGIN_ALIGN
 // The node lattice of a rotation starts at its ShrinkToFit corner (b0, b2)
 // rounded down to a multiple of this power of two (>= the largest cluster,
 // 2^kMaxClusterShift), and nodes wholly below the corner are dropped, so the
@@ -691,21 +706,210 @@ __device__ __forceinline__ uint32_t ClusterMask(int sl) {
 // lists can address lie in one residue class: 1/16 of the level-2..4 planes
 // and 1/64 of the level-6 hex plane, the same class for every pair and
 // rotation, instead of all of them across a chunk's items. The planes'
-// touched footprint shrinks to what one XCD's L2 holds. 1: the reference's
-// corner (no alignment).
-#define CSM_ORIGIN_ALIGN 8
+// touched footprint shrinks to what one XCD's L2 holds.
+constexpr int kOriginAlign = 8;
+static_assert((kOriginAlign & (kOriginAlign - 1)) == 0, "kOriginAlign: a power of two");
+
+// ---- fast2d_search_v4's phases ---------------------------------------------
+// The kernel's phases each carry a header saying which threads run it, which
+// fields of `sh` (the workgroup's V4Shared) it reads and writes, and which
+// barrier (__syncthreads of the whole workgroup) must follow. The phases below
+// are functions; the others are written out in the kernel under the same kind
+// of header, because the kernel sits on its register budget (80 VGPRs at 6
+// waves per SIMD, the hex forms spilling already) and as functions they
+// changed the kernel's device code (phase map). Either way a
+// change to a phase is checked against the whole kernel's device assembly and
+// spill counts, and lane and wave come from the kernel, not from threadIdx.
+
+// CSM_KPROF's clock marks and line counters; without CSM_KPROF every function
+// compiles to nothing and the kernel's cycles[] and t_mark are dead. Thread 0
+// keeps the cycles: Lap adds those since the previous mark to slot k (0 setup,
+// 1 control, 2 score), Since those since t0 = Now() (3: the entry lists, a
+// part of setup).
+struct V4Prof {
+  static __device__ __forceinline__ long long Now() {
+#ifdef CSM_KPROF
+    return clock64();
+#else
+    return 0;
 #endif
-static_assert((CSM_ORIGIN_ALIGN & (CSM_ORIGIN_ALIGN - 1)) == 0, "CSM_ORIGIN_ALIGN: a power of two");
-#ifndef CSM_TIE_PRUNE
-// 1: the main search stops expanding nodes bounded by a sum its witness keys
-// already show tied (FindsConstraints-like inputs: every leaf ties).
-#define CSM_TIE_PRUNE 1
+  }
+  static __device__ __forceinline__ void Lap(long long* cycles, long long& t_mark, int k) {
+#ifdef CSM_KPROF
+    if (threadIdx.x == 0) {
+      const long long now = clock64();
+      cycles[k] += now - t_mark;
+      t_mark = now;
+    }
 #endif
-#ifndef CSM_V4_WAVES
-// Waves per SIMD the register budget targets: 6 workgroups per CU (v5 with
-// its 256-entry LDS ring fits 6 in LDS too; measured best, DESIGN.md §5).
-#define CSM_V4_WAVES 6
+  }
+  static __device__ __forceinline__ void Since(long long* cycles, int k, long long t0) {
+#ifdef CSM_KPROF
+    if (threadIdx.x == 0) cycles[k] += clock64() - t0;
 #endif
+  }
+  // The gathers' line counters in sh (CountLines); the caller owes a barrier.
+  template <typename Shared>
+  static __device__ __forceinline__ void ResetLines(Shared& sh) {
+#ifdef CSM_KPROF
+    const int tid = threadIdx.x;
+    if (tid < kMaxLevels) {
+      sh.kp_lines[tid] = 0; sh.kp_instr[tid] = 0; sh.kp_qlines[tid] = 0;
+      sh.kp_active[tid] = 0; sh.kp_oob[tid] = 0;
+    }
+#endif
+  }
+  static __device__ __forceinline__ void FlushCycles(const long long* cycles, unsigned long long* stats) {
+#ifdef CSM_KPROF
+    for (int k = 0; k < 4; ++k) atomicAdd(&stats[2 + 2 * kMaxLevels + k], static_cast<unsigned long long>(cycles[k]));
+#endif
+  }
+  template <typename Shared>
+  static __device__ __forceinline__ void FlushLines(const Shared& sh, unsigned long long* stats) {
+#ifdef CSM_KPROF
+    const int tid = threadIdx.x;
+    if (stats && tid < kMaxLevels) {
+      atomicAdd(&stats[kStatLines + tid], sh.kp_lines[tid]);
+      atomicAdd(&stats[kStatLines + kMaxLevels + tid], sh.kp_instr[tid]);
+      atomicAdd(&stats[kStatLines + 2 * kMaxLevels + tid], sh.kp_qlines[tid]);
+      atomicAdd(&stats[kStatLines + 3 * kMaxLevels + tid], sh.kp_active[tid]);
+      atomicAdd(&stats[kStatLines + 4 * kMaxLevels + tid], sh.kp_oob[tid]);
+    }
+#endif
+  }
+};
+
+// K2, level cache. Threads 0 .. max(levels, 4 kMaxRotChunk) - 1. Writes
+// sh.lv (the submap's per-level quad layout) and resets sh.mm and
+// sh.range_error for the scan discretization. A barrier follows.
+template <typename Shared>
+__device__ __forceinline__ void V4CacheLevels(Shared& sh, const SubmapDesc& sm) {
+  const int tid = threadIdx.x;
+  if (tid < kMaxRotChunk * 4) sh.mm[tid >> 2][tid & 3] = (tid & 1) ? -0x7fffffff : 0x7fffffff;
+  if (tid == 0) sh.range_error = 0;
+  if (tid < sm.levels) {
+    const int d = tid;
+    sh.lv[d][0] = sm.quad_w[d];
+    sh.lv[d][1] = sm.quad_h[d];
+    sh.lv[d][2] = sm.quad_off[d];
+    sh.lv[d][3] = sm.quad_pws[d] * sm.quad_es[d];
+    sh.lv[d][4] = sm.quad_pws[d] * sm.quad_pph[d] * sm.quad_es[d];
+    sh.lv[d][5] = sm.quad_bias[d];
+    sh.lv[d][6] = sm.cshift[d];
+  }
+}
+
+// Entry lists, the long-run sweep. All threads; does nothing unless
+// sh.long_runs names a rotation. One wave per (such rotation, cluster shift)
+// overwrites sh.list_len[r][1..3] with RunList's counts; then its own barrier.
+template <typename Shared>
+__device__ __forceinline__ void V4CountLongRuns(Shared& sh, int lane, int wave,
+                                                const uint32_t* cells, int npad, int n, int nrot) {
+  if (const int lr = sh.long_runs) {
+    for (int t = wave; t < nrot * kMaxClusterShift; t += kWaves) {
+      const int r = t / kMaxClusterShift, sl = 1 + t % kMaxClusterShift;
+      if (lr >> r & 1) {
+        const int len = RunList<false>(cells + r * npad, n, ClusterMask(sl), nullptr, nullptr);
+        if (lane == 0) sh.list_len[r][sl] = len;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Per-item reset. Thread 0. Flags the pair if sh.range_error; turns
+// sh.root_prefix into the prefix sums of the rotations' root counts; empties
+// the stack (sh.sp, sh.ovf, sh.head, sh.vnext); loads sh.best from the pair's
+// global best; clears sh.tie_sum, sh.batch_no, sh.nodes, sh.done. A barrier
+// follows.
+template <typename Shared>
+__device__ __forceinline__ void V4ResetItem(Shared& sh, int nrot, int32_t* status, int pair_index,
+                                            const uint64_t* pair_best) {
+  if (threadIdx.x == 0) {
+    if (sh.range_error) atomicOr(&status[pair_index], kStatusRange);
+    sh.root_prefix[0] = 0;
+    for (int r = 0; r < nrot; ++r) sh.root_prefix[r + 1] += sh.root_prefix[r];
+    sh.vnext = 0;
+    sh.sp = 0;
+    sh.ovf = 0;
+    sh.head = 0;
+    sh.best = LoadBest(pair_best);
+    sh.tie_sum = -1;
+    sh.batch_no = 0;
+    sh.nodes = 0;
+    sh.done = 0;
+  }
+}
+
+// Combine, the LIFO push. The pass's whole wave; `push`: this lane's child
+// survived and takes stack slot sp + kept - 1 - rank with `entry`. Entries
+// past the LDS stack go to this workgroup's spill region in global memory
+// (StackPut); past that the pair is flagged. Writes sh.stack.
+template <typename Shared>
+__device__ __forceinline__ void V4PushLifo(Shared& sh, int lane, uint2* spill, bool push, int sp,
+                                           int kept, int rank, uint2 entry, int32_t* status,
+                                           int pair_index) {
+  if (push && sp + kept <= Shared::kStackCapacity) StackPut(sh, spill, sp + kept - 1 - rank, entry);
+  if (lane == 0 && sp + kept > Shared::kStackCapacity) atomicOr(&status[pair_index], kStatusRange);
+}
+
+// Combine, the FIFO push. The pass's whole wave; `ring`: this lane's child
+// takes ring slot `slot` after sh.head, `deep`: it goes to the overflow stack.
+// Ring slots past the LDS ring's capacity go to the overflow stack too (the
+// workgroup's spill region in global memory, popped when the ring is empty);
+// past that the pair is flagged. Writes sh.stack, sh.ovf; reads sh.head.
+template <typename Shared>
+__device__ __forceinline__ void V4PushFifo(Shared& sh, int lane, uint2* spill, bool ring, bool deep,
+                                           int slot, uint2 entry, int32_t* status,
+                                           int pair_index) {
+  constexpr int kRing = Shared::kStackLds;
+  if (ring && slot < kRing) sh.stack[(sh.head + slot) & (kRing - 1)] = entry;
+  const bool over = (ring && slot >= kRing) || deep;
+  const unsigned long long om = __ballot(over);
+  if (om) {
+    int ob = 0;
+    if (lane == 0) ob = atomicAdd(&sh.ovf, __popcll(om));
+    ob = __shfl(ob, 0, 64) + __popcll(om & ((1ull << lane) - 1));
+    if (over && ob < kSpill2) spill[ob] = entry;
+    if (over && ob >= kSpill2) atomicOr(&status[pair_index], kStatusRange);
+  }
+}
+
+// Statistics flush, once per workgroup after its last item. Thread 0 adds its
+// counts and sh.high_water, wave 0's lane l the counts of level l (and, under
+// CSM_KPROF, thread 0's cycles and the line counters in sh).
+template <typename Shared>
+__device__ __forceinline__ void V4FlushStats(const Shared& sh, unsigned long long* stats,
+                                             unsigned long long cands, unsigned long long lookups,
+                                             unsigned long long lv_cands,
+                                             unsigned long long lv_batches, const long long* cycles) {
+  const int tid = threadIdx.x;
+  if (stats && tid == 0) {
+    atomicAdd(&stats[0], cands);
+    atomicAdd(&stats[1], lookups);
+    V4Prof::FlushCycles(cycles, stats);
+  }
+  if (stats && tid < kMaxLevels) {  // wave 0's lane l: level l
+    atomicAdd(&stats[2 + tid], lv_cands);
+    atomicAdd(&stats[2 + kMaxLevels + tid], lv_batches);
+  }
+  if (stats && tid == 0) atomicMax(&stats[kStatHighWater], static_cast<unsigned long long>(sh.high_water));
+  V4Prof::FlushLines(sh, stats);
+}
+
+// The search kernel. Per item (pair, rotation chunk): K2 discretizes the
+// chunk's scans into LDS and builds their entry lists, then K3/K4 runs the
+// batched best-first search over the chunk.
+//
+// kHex = false: v4 (every node scores its 4 children from the quad planes).
+// kHex = true: v5 (nodes of the levels in SubmapDesc::hex_mask score their
+// 16 grandchildren from hex planes, the others their 4 children from quad
+// planes; a batch holds one kind).
+//
+// kFifo = false: the stack is LIFO with the deepest level on top (depth-first,
+// early leaves). kFifo = true: a FIFO ring (level by level: batches fill up
+// with the whole frontier of a level; leaves come last).
+//
 // kCollect: the tie-enumeration launch (PairDesc::collect_sum, csm_host.cc
 // ResolveTies), its own symbol so profiles tell it from the search.
 template <bool kHex, bool kFifo, bool kCollect>
@@ -727,7 +931,8 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
   // lists packed in [rc * npad + r * capc, + capc).
   constexpr int kKids = kHex ? 16 : 4;
   extern __shared__ __align__(16) uint32_t cells[];
-  __shared__ V4Shared<kKids> sh;
+  using Shared = V4Shared<kKids>;
+  __shared__ Shared sh;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int rc = queues.rot_chunk;
   // Counts of the cluster lists only (the raw scans weigh 1): entry at cell
@@ -738,22 +943,17 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
   for (int k = tid; k < kBatchNodes * kKids; k += kSearchThreads) sh.part[k] = 0;
   if (tid == 0) sh.batch_hex = 0;
   if (tid == 0) sh.high_water = 0;
-  unsigned long long local_cands = 0, local_lookups = 0;
-#ifdef CSM_KPROF
-  long long kprof[4] = {0, 0, 0, 0};  // thread 0: setup, control, score cycles; lists (part of setup)
-#endif
+  unsigned long long local_cands = 0, local_lookups = 0;  // thread 0
+  long long cycles[4] = {0, 0, 0, 0};  // V4Prof
   if (tid == 0) sh.queue = blockIdx.x % kNumXcd;
   unsigned long long lv_cands = 0, lv_batches = 0;  // wave 0, lane l: child level l
-#ifdef CSM_KPROF
-  if (tid < kMaxLevels) {
-    sh.kp_lines[tid] = 0; sh.kp_instr[tid] = 0; sh.kp_qlines[tid] = 0;
-    sh.kp_active[tid] = 0; sh.kp_oob[tid] = 0;
-  }
-#endif
+  V4Prof::ResetLines(sh);
   int tries = 0;
   __syncthreads();
   for (;;) {
-    // ---- claim (pair, rotation chunk) from an XCD-affine queue ------------
+    // ---- Claim: thread 0 takes (pair, rotation chunk) from an XCD-affine
+    // queue into sh.item_pair, sh.item_chunk, sh.queue; a barrier follows. (As
+    // a function it doubled the kernel's VGPR spills in every form tried.)
     if (tid == 0) {
       int q = sh.queue, pair = -1, chunk = 0;
       while (tries < kNumXcd) {
@@ -785,43 +985,28 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
     const int step = 1 << top_level;
     const uint32_t hex_mask = kHex ? static_cast<uint32_t>(Uniform(sm.hex_mask)) : 0u;
 
-    // ---- K2: discretize the chunk's rotated scans into LDS ----------------
-#ifdef CSM_KPROF
-    long long t_mark = clock64();
-#endif
-    if (tid < kMaxRotChunk * 4) sh.mm[tid >> 2][tid & 3] = (tid & 1) ? -0x7fffffff : 0x7fffffff;
-    if (tid == 0) sh.range_error = 0;
-    if (tid < sm.levels) {
-      const int d = tid;
-      sh.lv[d][0] = sm.quad_w[d];
-      sh.lv[d][1] = sm.quad_h[d];
-      sh.lv[d][2] = sm.quad_off[d];
-      sh.lv[d][3] = sm.quad_pws[d] * sm.quad_es[d];
-      sh.lv[d][4] = sm.quad_pws[d] * sm.quad_pph[d] * sm.quad_es[d];
-      sh.lv[d][5] = sm.quad_bias[d];
-      sh.lv[d][6] = sm.cshift[d];
-    }
+    // ---- K2: the chunk's scans, entry lists, windows and roots into LDS ------
+    long long t_mark = V4Prof::Now();
+    V4CacheLevels(sh, sm);
     __syncthreads();
+    // ---- Scan discretization: all threads. Writes the chunk's rotated scans
+    // as packed cells (int16 x | int16 y << 16) to cells[r * npad + i], their
+    // extent to sh.mm[r] (min_x, max_x, min_y, max_y; LDS atomics) and sets
+    // sh.range_error when a coordinate passes kIndexLimit (both indices of
+    // that point become 0); a barrier follows.
     const double inv_res = 1.0 / sm.resolution;  // CellCoordFast
     bool range_error = false;
     for (int r = 0; r < nrot; ++r) {
       const float2 q = rot_table[pd.rot_offset + rot0 + r];
       int mnx = 0x7fffffff, mxx = -0x7fffffff, mny = 0x7fffffff, mxy = -0x7fffffff;
       for (int i = tid; i < n; i += kSearchThreads) {
-        const float* p = points + 3 * (pd.point_offset + i);
-        float x, y;
-        RotateZDev(pd.pre_w, pd.pre_s, p[0], p[1], &x, &y);
-        RotateZDev(q.x, q.y, x, y, &x, &y);
-        const float px = __fadd_rn(pd.tx, x);
-        const float py = __fadd_rn(pd.ty, y);
-        const double cx = CellCoordFast(sm.max_y, py, sm.resolution, inv_res);
-        const double cy = CellCoordFast(sm.max_x, px, sm.resolution, inv_res);
+        const double2 c = ScanCellCoords(pd, sm, q, inv_res, points, i);
         int ix = 0, iy = 0;
-        if (fabs(cx) > kIndexLimit || fabs(cy) > kIndexLimit) {
+        if (fabs(c.x) > kIndexLimit || fabs(c.y) > kIndexLimit) {
           range_error = true;
         } else {
-          ix = static_cast<int>(cx);
-          iy = static_cast<int>(cy);
+          ix = static_cast<int>(c.x);
+          iy = static_cast<int>(c.y);
         }
         mnx = min(mnx, ix); mxx = max(mxx, ix);
         mny = min(mny, iy); mxy = max(mxy, iy);
@@ -834,156 +1019,130 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
       }
     }
     if (range_error) sh.range_error = 1;
-#ifdef CSM_DBG
-    if (range_error) printf("discretize range\n");
-#endif
     __syncthreads();
     // ---- Entry lists: k = 1 is the discretized scan itself (one point per
     // entry; it scores the leaves only), k = 2, 4, 8 are run lists of cluster
-    // keys. All threads count the runs of all three; the lists are packed
-    // into the rotation's capc region coarsest first (one that does not fit
-    // aliases the next finer list); then one wave per (rotation, list) sweep
-    // writes them -------------------------------------------------------------
-    {
-#ifdef CSM_KPROF
-      const long long t_lists = clock64();
-#endif
-      // A rotation whose coarsest keys repeat 255 points apart may hold a run
-      // past 255 points (split entries): its lists are counted by a sweep.
-      if (tid < nrot * kLists) sh.list_len[tid / kLists][tid % kLists] = tid % kLists == 0 ? n : 0;
-      if (tid == 0) sh.long_runs = 0;
-      __syncthreads();
-      for (int r = 0; r < nrot; ++r) {
-        const uint32_t* raw = cells + r * npad;
-        uint32_t c1 = 0, c23 = 0;  // run heads of k = 2 | k = 4, k = 8 (16-bit fields)
-        bool long_run = false;
-        for (int i = tid; i < n; i += kSearchThreads) {
-          const uint32_t v = raw[i];
-          const uint32_t d = i == 0 ? 0xffffffffu : v ^ raw[i - 1];
-          c1 += (d & ClusterMask(1)) != 0u;
-          c23 += ((d & ClusterMask(2)) != 0u) | (static_cast<uint32_t>((d & ClusterMask(3)) != 0u) << 16);
-          long_run |= i >= 255 && ((v ^ raw[i - 255]) & ClusterMask(kMaxClusterShift)) == 0u;
-        }
-        c1 = DppSum(c1);
-        c23 = DppSum(c23);
-        if (lane == 0) {
-          atomicAdd(&sh.list_len[r][1], static_cast<int>(c1));
-          atomicAdd(&sh.list_len[r][2], static_cast<int>(c23 & 0xffff));
-          atomicAdd(&sh.list_len[r][3], static_cast<int>(c23 >> 16));
-        }
-        if (__ballot(long_run) && lane == 0) atomicOr(&sh.long_runs, 1 << r);
+    // keys. Four steps with a barrier after each; reads the raw cells and
+    // sh.lv[..][6], leaves sh.list_off, sh.list_len and the lists' cells and
+    // counts.
+    const long long t_lists = V4Prof::Now();
+    if (tid < nrot * kLists) sh.list_len[tid / kLists][tid % kLists] = tid % kLists == 0 ? n : 0;
+    if (tid == 0) sh.long_runs = 0;
+    __syncthreads();
+    // Run counts: all threads add the run heads of the k = 2, 4, 8 cluster
+    // keys to sh.list_len[r][1..3] and set bit r of sh.long_runs for a rotation
+    // whose coarsest keys repeat 255 points apart: it may hold a run past 255
+    // points (split entries), so V4CountLongRuns counts its lists by a sweep.
+    for (int r = 0; r < nrot; ++r) {
+      const uint32_t* raw = cells + r * npad;
+      uint32_t c1 = 0, c23 = 0;  // run heads of k = 2 | k = 4, k = 8 (16-bit fields)
+      bool long_run = false;
+      for (int i = tid; i < n; i += kSearchThreads) {
+        const uint32_t v = raw[i];
+        const uint32_t d = i == 0 ? 0xffffffffu : v ^ raw[i - 1];
+        c1 += (d & ClusterMask(1)) != 0u;
+        c23 += ((d & ClusterMask(2)) != 0u) | (static_cast<uint32_t>((d & ClusterMask(3)) != 0u) << 16);
+        long_run |= i >= 255 && ((v ^ raw[i - 255]) & ClusterMask(kMaxClusterShift)) == 0u;
       }
-      __syncthreads();
-      if (const int lr = sh.long_runs) {
-        for (int t = wave; t < nrot * kMaxClusterShift; t += kWaves) {
-          const int r = t / kMaxClusterShift, sl = 1 + t % kMaxClusterShift;
-          if (lr >> r & 1) {
-            const int len = RunList<false>(cells + r * npad, n, ClusterMask(sl), nullptr, nullptr);
-            if (lane == 0) sh.list_len[r][sl] = len;
-          }
-        }
-        __syncthreads();
+      c1 = DppSum(c1);
+      c23 = DppSum(c23);
+      if (lane == 0) {
+        atomicAdd(&sh.list_len[r][1], static_cast<int>(c1));
+        atomicAdd(&sh.list_len[r][2], static_cast<int>(c23 & 0xffff));
+        atomicAdd(&sh.list_len[r][3], static_cast<int>(c23 >> 16));
       }
-      // The cluster sizes some level scores with (SubmapDesc::cshift); an
-      // unused list is not written and aliases the next finer one.
-      uint32_t used_sl = 0;
-      for (int d = 0; d < sm.levels; ++d) used_sl |= 1u << sh.lv[d][6];
-      if (tid < nrot) {
-        const int r = tid;
-        sh.list_off[r][0] = r * npad;
-        int used = 0;
-        int off[kLists] = {r * npad, -1, -1, -1};
-        for (int sl = kMaxClusterShift; sl >= 1; --sl)
-          if ((used_sl >> sl & 1u) && used + sh.list_len[r][sl] <= capc) {
-            off[sl] = rc * npad + r * capc + used;
-            used += sh.list_len[r][sl];
-          }
-        for (int sl = 1; sl < kLists; ++sl) {
-          if (off[sl] >= 0) {
-            sh.list_off[r][sl] = off[sl];
-          } else {  // does not fit: the finer list bounds this level too
-            sh.list_off[r][sl] = sh.list_off[r][sl - 1];
-            sh.list_len[r][sl] = sh.list_len[r][sl - 1] | (1 << 30);
-          }
-        }
-      }
-      __syncthreads();
-      // Tasks (rotation, used list) dealt to the waves.
-      const int nused = __popc(used_sl & 0xeu);
-      for (int t = wave; t < nrot * nused; t += kWaves) {
-        const int r = t / nused;
-        int sl = 0;
-        for (int k = t % nused, m = used_sl & 0xe; k >= 0; --k) {
-          sl = __ffs(m) - 1;
-          m &= m - 1;
-        }
-        if (!(sh.list_len[r][sl] & (1 << 30)))
-          RunList<true>(cells + r * npad, n, ClusterMask(sl), cells + sh.list_off[r][sl],
-                        cnts + (sh.list_off[r][sl] - raw_end));
-      }
-      __syncthreads();
-      if (tid < nrot * kLists) sh.list_len[tid / kLists][tid % kLists] &= ~(1 << 30);
-      __syncthreads();
-#ifdef CSM_KPROF
-      if (tid == 0) kprof[3] += clock64() - t_lists;
-#endif
+      if (__ballot(long_run) && lane == 0) atomicOr(&sh.long_runs, 1 << r);
     }
-    // ---- ShrinkToFit per rotation; root counts ------------------------------
+    __syncthreads();
+    V4CountLongRuns(sh, lane, wave, cells, npad, n, nrot);
+    // The cluster sizes some level scores with (SubmapDesc::cshift); an
+    // unused list is not written and aliases the next finer one.
+    uint32_t used_sl = 0;
+    for (int d = 0; d < sm.levels; ++d) used_sl |= 1u << sh.lv[d][6];
+    // Packing: thread r < nrot packs rotation r's used lists into its capc
+    // region coarsest first and writes sh.list_off[r]; a list that does not
+    // fit aliases the next finer one (offset and length, the length flagged
+    // with bit 30 until the lists are written).
     if (tid < nrot) {
       const int r = tid;
-      const int lo_x = min(0, -sh.mm[r][1]), hi_x = max(0, sm.nx - 1 - sh.mm[r][0]);
-      const int lo_y = min(0, -sh.mm[r][3]), hi_y = max(0, sm.ny - 1 - sh.mm[r][2]);
-      const int b0 = max(-pd.num_linear, lo_x), b1 = min(pd.num_linear, hi_x);
-      const int b2 = max(-pd.num_linear, lo_y), b3 = min(pd.num_linear, hi_y);
-      sh.bounds[r][0] = b0; sh.bounds[r][1] = b1; sh.bounds[r][2] = b2; sh.bounds[r][3] = b3;
-      const int a0 = b0 & -CSM_ORIGIN_ALIGN, a2 = b2 & -CSM_ORIGIN_ALIGN;  // lattice origin
-      const int tnx = (b1 - a0 + step) / step, tny = (b3 - a2 + step) / step;
+      sh.list_off[r][0] = r * npad;
+      int used = 0;
+      int off[kLists] = {r * npad, -1, -1, -1};
+      for (int sl = kMaxClusterShift; sl >= 1; --sl)
+        if ((used_sl >> sl & 1u) && used + sh.list_len[r][sl] <= capc) {
+          off[sl] = rc * npad + r * capc + used;
+          used += sh.list_len[r][sl];
+        }
+      for (int sl = 1; sl < kLists; ++sl) {
+        if (off[sl] >= 0) {
+          sh.list_off[r][sl] = off[sl];
+        } else {  // does not fit: the finer list bounds this level too
+          sh.list_off[r][sl] = sh.list_off[r][sl - 1];
+          sh.list_len[r][sl] = sh.list_len[r][sl - 1] | (1 << 30);
+        }
+      }
+    }
+    __syncthreads();
+    // The writes: tasks (rotation, used list) dealt to the waves, one RunList
+    // sweep each writes the list's cells and counts at sh.list_off[r][sl].
+    const int nused = __popc(used_sl & 0xeu);
+    for (int t = wave; t < nrot * nused; t += kWaves) {
+      const int r = t / nused;
+      int sl = 0;
+      for (int k = t % nused, m = used_sl & 0xe; k >= 0; --k) {
+        sl = __ffs(m) - 1;
+        m &= m - 1;
+      }
+      if (!(sh.list_len[r][sl] & (1 << 30)))
+        RunList<true>(cells + r * npad, n, ClusterMask(sl), cells + sh.list_off[r][sl],
+                      cnts + (sh.list_off[r][sl] - raw_end));
+    }
+    __syncthreads();
+    if (tid < nrot * kLists) sh.list_len[tid / kLists][tid % kLists] &= ~(1 << 30);
+    __syncthreads();
+    V4Prof::Since(cycles, 3, t_lists);
+    // ---- ShrinkToFit and root counts: thread r < nrot reads sh.mm[r] and
+    // writes sh.bounds[r], sh.vny[r] and rotation r's root count to
+    // sh.root_prefix[r + 1]; a barrier follows.
+    if (tid < nrot) {
+      const int r = tid;
+      const int4 b = ShrinkToFitBounds(sh.mm[r][0], sh.mm[r][1], sh.mm[r][2], sh.mm[r][3], sm.nx,
+                                       sm.ny, pd.num_linear);
+      sh.bounds[r][0] = b.x; sh.bounds[r][1] = b.y; sh.bounds[r][2] = b.z; sh.bounds[r][3] = b.w;
+      const int a0 = b.x & -kOriginAlign, a2 = b.z & -kOriginAlign;  // lattice origin
+      const int tnx = (b.y - a0 + step) / step, tny = (b.w - a2 + step) / step;
       sh.vny[r] = (tny + 1) >> 1;
       sh.root_prefix[r + 1] = ((tnx + 1) >> 1) * sh.vny[r];
     }
     __syncthreads();
-    if (tid == 0) {
-      if (sh.range_error) atomicOr(&status[pair_index], kStatusRange);
-      sh.root_prefix[0] = 0;
-      for (int r = 0; r < nrot; ++r) sh.root_prefix[r + 1] += sh.root_prefix[r];
-      sh.vnext = 0;
-      sh.sp = 0;
-      sh.ovf = 0;
-      sh.head = 0;
-      sh.best = LoadBest(pair_best);
-      sh.tie_sum = -1;
-      sh.batch_no = 0;
-      sh.nodes = 0;
-      sh.done = 0;
-    }
+    V4ResetItem(sh, nrot, status, pair_index, pair_best);
     __syncthreads();
     const int vtotal = Uniform(sh.root_prefix[nrot]);
-#ifdef CSM_KPROF
-    if (tid == 0) {
-      const long long now = clock64();
-      kprof[0] += now - t_mark;
-      t_mark = now;
-    }
-#endif
+    V4Prof::Lap(cycles, t_mark, 0);
 
     // ---- K3/K4: batched best-first DFS over the chunk -----------------------
     for (;;) {
+      // ---- (a) Combine the previous batch: prune, record leaves, push
+      // survivors. All waves take passes in parallel and claim stack space
+      // atomically: 16 nodes' children per pass (one per lane); hex batches: 4
+      // nodes' 16 grandchildren per pass. Reads sh.nodes, sh.batch_hex, the
+      // batch's sh.node_* and sh.part (which it zeroes again), sh.bounds,
+      // sh.best; writes sh.sp, sh.high_water and what the leaves and the push
+      // write; a barrier follows.
       {
-        // (a) Combine the previous batch: prune, record leaves, push survivors.
-        // 16 nodes' children per pass (one per lane); the waves take the
-        // passes in parallel and claim stack space atomically.
-        // Hex batches: 4 nodes' 16 grandchildren per pass, child c = (a, b)
-        // at (xo + a h, yo + b h), a = c >> 2, b = c & 3.
         const int pn = sh.nodes;
         const bool hexb = kHex && sh.batch_hex;
         const int lk = hexb ? 4 : 2;  // log2 children per node
         const int per_pass = 64 >> lk;
         for (int pass = wave; pass * per_pass < pn; pass += kWaves) {
           const int nd = pass * per_pass + (lane >> lk), cl = lane & ((1 << lk) - 1);
-          // Child c = (a, b) at (xo + a h, yo + b h) sits in lane (b, a)
-          // order when CSM_XFAST (x fastest), else (a, b).
+          // Child c = (a, b) at (xo + a h, yo + b h), a = c >> hb, b = c &
+          // (2^hb - 1), sits in lane (b, a): children (and roots, below) enter
+          // the stack x-fastest, so consecutive lanes of the next batch score
+          // nodes adjacent in x: adjacent entries of a polyphase plane
+          // (DESIGN.md §5).
           const int hb = lk >> 1;
-          const int c = CSM_XFAST ? (((cl & ((1 << hb) - 1)) << hb) | (cl >> hb)) : cl;
+          const int c = ((cl & ((1 << hb) - 1)) << hb) | (cl >> hb);
           int sum = 0, xo = 0, yo = 0, r = 0, clvl = 0;
           bool exists = false;
           if (nd < pn) {
@@ -1003,15 +1162,13 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
           const uint64_t cur = sh.best;
           const uint32_t cur_sum = static_cast<uint32_t>(cur >> kSumShift);
           const bool keep = exists && sum > s_min && static_cast<uint32_t>(sum) >= cur_sum;
-          // Leaves (child level 0) update the incumbent.
+          // Leaves (child level 0) raise the pair's global best and sh.best,
+          // the tie witness best_hi and sh.tie_sum, and are recorded in ties
+          // when at collect_sum (kCollect).
           uint64_t key = 0;
           if (keep && clvl == 0) {
-            if (xo < -kOffsetLimit || xo > kOffsetLimit || yo < -kOffsetLimit || yo > kOffsetLimit) {
+            if (xo < -kOffsetLimit || xo > kOffsetLimit || yo < -kOffsetLimit || yo > kOffsetLimit)
               atomicOr(&status[pair_index], kStatusRange);
-#ifdef CSM_DBG
-              printf("leaf range xo %d yo %d\n", xo, yo);
-#endif
-            }
             else
               key = PackLeafKey(sum, rot0 + r, xo, yo);
             // Tie enumeration: every leaf at the pair's maximum sum.
@@ -1035,22 +1192,22 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
               atomicMax(reinterpret_cast<unsigned long long*>(pair_best), key);
               atomicMax(reinterpret_cast<unsigned long long*>(&sh.best), key);
             }
-            // Two leaves at the pass's largest sum, or one at the best sum
-            // other than the best's: the pair ties there, so nodes bounded by
-            // that sum need not be expanded (sh.tie_sum; tie resolution
-            // searches those leaves again, ResolveTies).
-            // Only a real incumbent (cur != 0) can be the second leaf: with
-            // none yet, cur_sum is 0 and a single leaf at sum 0 (reachable
+            // Two leaves at the pass's largest sum, or one at the best sum other
+            // than the best's: the pair ties there, so the main search stops
+            // expanding nodes bounded by that sum (sh.tie_sum; tie resolution
+            // searches those leaves again, ResolveTies; FindsConstraints-like inputs:
+            // every leaf ties). Only a real incumbent (cur != 0) can be the second
+            // leaf: with none yet, cur_sum is 0 and a single leaf at sum 0 (reachable
             // when min_score lets sum 0 pass) would look tied.
-            if (CSM_TIE_PRUNE && !kCollect && lane == 0) {
+            if (!kCollect && lane == 0) {
               const uint32_t ks = static_cast<uint32_t>(key >> kSumShift);
               if (ks >= cur_sum &&
                   (hi != HighLeafKey(key) ||
                    (cur != 0 && key != cur && static_cast<uint32_t>(cur >> kSumShift) == ks)))
                 atomicMax(&sh.tie_sum, static_cast<int>(ks));
             }
-            // The largest-index leaf at the running maximum: a second maximal
-            // leaf shows as a different index at the final sum (ResolveTies).
+            // The largest-index leaf at the running maximum: a second maximal leaf
+            // shows as a different index at the final sum (ResolveTies).
             if (lane == 0 && static_cast<uint32_t>(hi >> kSumShift) >= cur_sum)
               atomicMax(reinterpret_cast<unsigned long long*>(best_hi + pair_index), hi);
           }
@@ -1084,45 +1241,29 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
               (static_cast<uint32_t>(xo) & 0xffff) | (static_cast<uint32_t>(yo) << 16),
               static_cast<uint32_t>(sum) | (static_cast<uint32_t>(r) << 22) |
                   (static_cast<uint32_t>(clvl) << 27));
-          if (kFifo) {
-            // Ring slots past the LDS ring's capacity go to the workgroup's
-            // overflow stack in global memory (popped when the ring is
-            // empty); past that the pair is flagged.
-            constexpr int kRing = decltype(sh)::kStackLds;
-            const int slot = sp + rank;
-            if (push && !deep && slot < kRing) sh.stack[(sh.head + slot) & (kRing - 1)] = entry;
-            const bool over = (push && !deep && slot >= kRing) || deep;
-            const unsigned long long om = __ballot(over);
-            if (om) {
-              int ob = 0;
-              if (lane == 0) ob = atomicAdd(&sh.ovf, __popcll(om));
-              ob = __shfl(ob, 0, 64) + __popcll(om & ((1ull << lane) - 1));
-              if (over && ob < kSpill2) spill[ob] = entry;
-              if (over && ob >= kSpill2) atomicOr(&status[pair_index], kStatusRange);
-#ifdef CSM_DBG
-              if (over && ob >= kSpill2 && (lane == 0 || ob == kSpill2)) printf("ovf overflow ob %d sp %d kept %d head %d\n", ob, sp, kept, sh.head);
-#endif
-            }
-          } else {
-            // Entries past the LDS stack go to this workgroup's spill region
-            // in global memory (StackPut); past that the pair is flagged.
-            if (push && sp + kept <= sh.kStackCapacity) StackPut(sh, spill, sp + kept - 1 - rank, entry);
-            if (lane == 0 && sp + kept > sh.kStackCapacity) atomicOr(&status[pair_index], kStatusRange);
-          }
+          if (kFifo)
+            V4PushFifo(sh, lane, spill, push && !deep, deep, sp + rank, entry, status, pair_index);
+          else
+            V4PushLifo(sh, lane, spill, push, sp, kept, rank, entry, status, pair_index);
         }
       }
       __syncthreads();
       if (wave == 0) {
-        // (b) Refill roots when the stack is empty. (An overflowed stack has
-        // flagged the pair; its result is discarded.)
-        constexpr int kRing = decltype(sh)::kStackLds;
-        int sp = min(sh.sp, kFifo ? kRing : sh.kStackCapacity);
+        // ---- (b) Refill roots when the stack is empty: wave 0. Reads sh.sp,
+        // sh.ovf, sh.vnext, sh.root_prefix, sh.vny, sh.bounds; writes up to
+        // kRootChunk virtual roots (one level above the top lattice, bound
+        // 0x3fffff) to sh.stack, advances sh.vnext and restarts the ring
+        // (sh.head). Leaves the stack's and the overflow stack's entry counts in
+        // sp and ovf for (c), not yet in sh. (An overflowed stack has flagged
+        // the pair; its result is discarded.)
+        constexpr int kRing = Shared::kStackLds;
+        int sp = min(sh.sp, kFifo ? kRing : Shared::kStackCapacity);
         int ovf = kFifo ? min(sh.ovf, kSpill2) : 0;
         // The collect pass abandons a pair once its tied leaves overflow the
         // record: the host resolves it with the ordered walk (fast2d_walk).
         const bool abandon =
             kCollect && Uniform(static_cast<int>(
-                            *reinterpret_cast<volatile int32_t*>(tie_count + pair_index) > kTieCap)) != 0;
+                            *reinterpret_cast<const volatile int32_t*>(tie_count + pair_index) > kTieCap)) != 0;
         if (abandon) {
           sp = 0;
           ovf = 0;
@@ -1136,14 +1277,11 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
             int r = 0;
             while (sh.root_prefix[r + 1] <= v) ++r;
             const int lv = v - sh.root_prefix[r];
-            int xi = lv / sh.vny[r], yi = lv % sh.vny[r];
-            if (CSM_XFAST) {
-              const int vnx = (sh.root_prefix[r + 1] - sh.root_prefix[r]) / sh.vny[r];
-              xi = lv % vnx;
-              yi = lv / vnx;
-            }
-            const int xo = (sh.bounds[r][0] & -CSM_ORIGIN_ALIGN) + xi * 2 * step;
-            const int yo = (sh.bounds[r][2] & -CSM_ORIGIN_ALIGN) + yi * 2 * step;
+            // x-fastest, as the children (a).
+            const int vnx = (sh.root_prefix[r + 1] - sh.root_prefix[r]) / sh.vny[r];
+            const int xi = lv % vnx, yi = lv / vnx;
+            const int xo = (sh.bounds[r][0] & -kOriginAlign) + xi * 2 * step;
+            const int yo = (sh.bounds[r][2] & -kOriginAlign) + yi * 2 * step;
             sh.stack[k] = make_uint2((static_cast<uint32_t>(xo) & 0xffff) | (static_cast<uint32_t>(yo) << 16),
                                      0x3fffffu | (static_cast<uint32_t>(r) << 22) |
                                          (static_cast<uint32_t>(top_level + 1) << 27));
@@ -1151,12 +1289,17 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
           sp = vc;
           if (lane == 0) sh.vnext = v0 + vc;
         }
-        // (c) Pop the next batch: up to 64 nodes, best first.
+        // ---- (c) Pop the next batch, up to 64 nodes, best first: wave 0.
+        // Reads sh.stack / the spill region, sh.head, sh.tie_sum, sh.lv,
+        // sh.list_off, sh.list_len; refreshes sh.best from the pair's global
+        // best; writes the batch (sh.node_*, sh.nodes, sh.batch_len,
+        // sh.batch_entries, sh.batch_hex), the stack's new state (sh.sp, sh.ovf,
+        // sh.head) and sh.done, and counts the batch per child level; a barrier
+        // follows.
         if (lane == 0 && (sh.batch_no++ & (CSM_BEST_REFRESH - 1)) == 0) {
-          // Every 8th batch also reads the tie witness: once it shows two
-          // leaves at the best sum, the search only has to find a larger sum,
-          // so nodes bounded by that sum are pruned (tie resolution searches
-          // those leaves again, ResolveTies).
+          // Every CSM_BEST_REFRESH-th batch (by default every batch) reads the
+          // pair's global best, which the workgroups searching the pair's other
+          // chunks raise too.
           const uint64_t fresh = LoadBest(pair_best);
           if (fresh > sh.best) sh.best = fresh;
         }
@@ -1249,13 +1392,9 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
         }
       }
       __syncthreads();
-#ifdef CSM_KPROF
-      if (tid == 0) {
-        const long long now = clock64();
-        kprof[1] += now - t_mark;
-        t_mark = now;
-      }
-#endif
+      V4Prof::Lap(cycles, t_mark, 1);
+      // ---- Score the batch's children into sh.part: all threads; a barrier
+      // follows.
       const int nodes = Uniform(sh.nodes);
       const int done = Uniform(sh.done);
       if (done) break;
@@ -1272,36 +1411,10 @@ fast2d_search_v4(const SubmapDesc* __restrict__ submaps,
                          static_cast<unsigned>(Uniform(sh.batch_entries));
       }
       __syncthreads();
-#ifdef CSM_KPROF
-      if (tid == 0) {
-        const long long now = clock64();
-        kprof[2] += now - t_mark;
-        t_mark = now;
-      }
-#endif
+      V4Prof::Lap(cycles, t_mark, 2);
     }
   }
-  if (stats && tid == 0) {
-    atomicAdd(&stats[0], local_cands);
-    atomicAdd(&stats[1], local_lookups);
-#ifdef CSM_KPROF
-    for (int k = 0; k < 4; ++k) atomicAdd(&stats[2 + 2 * kMaxLevels + k], static_cast<unsigned long long>(kprof[k]));
-#endif
-  }
-  if (stats && tid < kMaxLevels) {  // wave 0's lane l: level l
-    atomicAdd(&stats[2 + tid], lv_cands);
-    atomicAdd(&stats[2 + kMaxLevels + tid], lv_batches);
-  }
-  if (stats && tid == 0) atomicMax(&stats[kStatHighWater], static_cast<unsigned long long>(sh.high_water));
-#ifdef CSM_KPROF
-  if (stats && tid < kMaxLevels) {
-    atomicAdd(&stats[kStatLines + tid], sh.kp_lines[tid]);
-    atomicAdd(&stats[kStatLines + kMaxLevels + tid], sh.kp_instr[tid]);
-    atomicAdd(&stats[kStatLines + 2 * kMaxLevels + tid], sh.kp_qlines[tid]);
-    atomicAdd(&stats[kStatLines + 3 * kMaxLevels + tid], sh.kp_active[tid]);
-    atomicAdd(&stats[kStatLines + 4 * kMaxLevels + tid], sh.kp_oob[tid]);
-  }
-#endif
+  V4FlushStats(sh, stats, local_cands, local_lookups, lv_cands, lv_batches, cycles);
 }
 
 // One rotation of a pair's scan discretized into LDS exactly as the search
@@ -1314,17 +1427,10 @@ __device__ void DiscretizeRotation(uint32_t* __restrict__ cells, int npad, const
   for (int i = threadIdx.x; i < npad; i += blockDim.x) {
     uint32_t c = 0x80008000u;  // (-32768, -32768): outside every level
     if (i < pd.num_points) {
-      const float* p = points + 3 * (pd.point_offset + i);
-      float x, y;
-      RotateZDev(pd.pre_w, pd.pre_s, p[0], p[1], &x, &y);
-      RotateZDev(q.x, q.y, x, y, &x, &y);
-      const float px = __fadd_rn(pd.tx, x);
-      const float py = __fadd_rn(pd.ty, y);
-      const double cx = CellCoordFast(sm.max_y, py, sm.resolution, inv_res);
-      const double cy = CellCoordFast(sm.max_x, px, sm.resolution, inv_res);
-      if (fabs(cx) <= kIndexLimit && fabs(cy) <= kIndexLimit)
-        c = (static_cast<uint32_t>(static_cast<int>(cx)) & 0xffff) |
-            (static_cast<uint32_t>(static_cast<int>(cy)) << 16);
+      const double2 cc = ScanCellCoords(pd, sm, q, inv_res, points, i);
+      if (fabs(cc.x) <= kIndexLimit && fabs(cc.y) <= kIndexLimit)
+        c = (static_cast<uint32_t>(static_cast<int>(cc.x)) & 0xffff) |
+            (static_cast<uint32_t>(static_cast<int>(cc.y)) << 16);
     }
     cells[i] = c;
   }
@@ -1491,16 +1597,9 @@ fast2d_rotation_bounds(const SubmapDesc* __restrict__ submaps, const PairDesc* _
   int mnx = 0x7fffffff, mxx = -0x7fffffff, mny = 0x7fffffff, mxy = -0x7fffffff;
   const double inv_res = 1.0 / sm.resolution;  // CellCoordFast
   for (int i = threadIdx.x; i < pd.num_points; i += blockDim.x) {
-    const float* p = points + 3 * (pd.point_offset + i);
-    float x, y;
-    RotateZDev(pd.pre_w, pd.pre_s, p[0], p[1], &x, &y);
-    RotateZDev(q.x, q.y, x, y, &x, &y);
-    const float px = __fadd_rn(pd.tx, x);
-    const float py = __fadd_rn(pd.ty, y);
-    const double cx = CellCoordFast(sm.max_y, py, sm.resolution, inv_res);
-    const double cy = CellCoordFast(sm.max_x, px, sm.resolution, inv_res);
-    const int ix = fabs(cx) > kIndexLimit ? 0 : static_cast<int>(cx);
-    const int iy = fabs(cy) > kIndexLimit ? 0 : static_cast<int>(cy);
+    const double2 c = ScanCellCoords(pd, sm, q, inv_res, points, i);
+    const int ix = fabs(c.x) > kIndexLimit ? 0 : static_cast<int>(c.x);
+    const int iy = fabs(c.y) > kIndexLimit ? 0 : static_cast<int>(c.y);
     mnx = min(mnx, ix); mxx = max(mxx, ix);
     mny = min(mny, iy); mxy = max(mxy, iy);
   }
@@ -1510,12 +1609,8 @@ fast2d_rotation_bounds(const SubmapDesc* __restrict__ submaps, const PairDesc* _
     atomicMin(&mm[2], mny); atomicMax(&mm[3], mxy);
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const int lo_x = min(0, -mm[1]), hi_x = max(0, sm.nx - 1 - mm[0]);
-    const int lo_y = min(0, -mm[3]), hi_y = max(0, sm.ny - 1 - mm[2]);
-    bounds[blockIdx.x] = make_int4(max(-pd.num_linear, lo_x), min(pd.num_linear, hi_x),
-                                   max(-pd.num_linear, lo_y), min(pd.num_linear, hi_y));
-  }
+  if (threadIdx.x == 0)
+    bounds[blockIdx.x] = ShrinkToFitBounds(mm[0], mm[1], mm[2], mm[3], sm.nx, sm.ny, pd.num_linear);
 }
 
 // Grid cells -> float through a 32768-entry table (ValueConversionTables;

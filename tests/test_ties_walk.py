@@ -27,15 +27,31 @@ from conftest import assert_search_ok
 pytestmark = pytest.mark.gpu
 
 KERNELS = {"v5": {}, "v4-lifo": {"CSM_SEARCH_KERNEL": "4", "CSM_SEARCH_ORDER": "lifo"}}
+# The collect launch (fast2d_search_v4<kHex, kFifo, true>) in all four
+# (kHex, kFifo) forms: KERNELS has <hex, fifo> and <quad, lifo>.
+COLLECT_KERNELS = dict(KERNELS, **{
+    "v4-fifo": {"CSM_SEARCH_KERNEL": "4"},
+    "v5-mixed-lifo": {"CSM_HEX_LEVELS": "8,6,3", "CSM_SEARCH_ORDER": "lifo"}})
+
+
+def _select_kernel(request, monkeypatch):
+    for var in ("CSM_SEARCH_KERNEL", "CSM_HEX_LEVELS", "CSM_SEARCH_ORDER"):
+        monkeypatch.delenv(var, raising=False)
+    for var, val in COLLECT_KERNELS[request.param].items():
+        monkeypatch.setenv(var, val)
+    return request.param
 
 
 @pytest.fixture(params=list(KERNELS))
 def kernel(request, monkeypatch):
-    for var in ("CSM_SEARCH_KERNEL", "CSM_HEX_LEVELS", "CSM_SEARCH_ORDER"):
-        monkeypatch.delenv(var, raising=False)
-    for var, val in KERNELS[request.param].items():
-        monkeypatch.setenv(var, val)
-    return request.param
+    return _select_kernel(request, monkeypatch)
+
+
+@pytest.fixture(params=list(COLLECT_KERNELS))
+def collect_kernel(request, monkeypatch):
+    """All four forms, for the two tests on the all-unknown grid: the smallest
+    input that drives both the recorded-ties path and the overflow walk."""
+    return _select_kernel(request, monkeypatch)
 
 
 def _unknown_grid(csm):
@@ -71,7 +87,7 @@ def _assert_exact(res_k, ref):
         assert got == tuple(pose), ("pose differs from the reference's pick", got, pose)
 
 
-def test_finds_constraints_inputs_match_oracle(csm, oracle, kernel):
+def test_finds_constraints_inputs_match_oracle(csm, oracle, collect_kernel):
     """The FindsConstraints pairs: Match at the node pose (the two
     MaybeAddConstraint calls) and MatchFullSubmap (MaybeAddGlobalConstraint),
     min_score 0, default options (linear 7 m, angular 30 deg, depth 7)."""
@@ -99,7 +115,7 @@ def test_finds_constraints_inputs_match_oracle(csm, oracle, kernel):
                                              (res[1]["x"], res[1]["y"], res[1]["theta"]))
 
 
-def test_unknown_grid_full_submap_clouds(csm, oracle, kernel):
+def test_unknown_grid_full_submap_clouds(csm, oracle, collect_kernel):
     """MatchFullSubmap on an all-unknown grid at min_score 0 with clouds of 1,
     7 and 60 points and two depths: every leaf inside the grid ties."""
     limits, cells, grid = _unknown_grid(csm)
